@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- range-block matches/s of the MI355X grey encode hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (pool build + range prep + sweep + finalise + codebook
 gather) over one batch of synthetic grey input that is already resident in HBM.  Default
@@ -19,10 +19,17 @@ FIC_BENCH_TIMEOUT seconds, default 900 -- and exits with their worst code); unde
 `python -m torch.distributed.run ... bench.py --gpus N` the RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* environment is used as given.  Every rank carries a watchdog with the same deadline.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Beside the contract's keys:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step)
+and the headline's config.  A plain run does only what that line needs: set-up, W warm-up steps, exactly K timed steps,
+`--dump-outputs`, the line.  Also from the timed region, at no extra cost:
   roofline              the compute bound of the sweep kernel that ran (matrix-core FLOP/s against the dense MFMA peak, or
-                        VALU issue for the VALU-only sweeps): `frac` algorithmic, `executed_frac` what the matrix cores issue
+                        VALU issue for the VALU-only sweeps): `frac` algorithmic, `executed_frac` what the matrix cores issue;
+                        `clock_ghz` (a run of its own) only with --full
   roofline_hbm_logical  SURVEY 8d's byte model, which the sweep exceeds by the register-tile reuse factor
+`--dump-outputs DIR` writes what the last timed step computed -- the codebook records a caller of the path receives
+(rank 0's gathered records at N > 1), unpacked as fic_amd.unpack_records does -- to DIR/<name>.npy (float32 / float64;
+a fixed, seeded sample of range blocks when the whole would exceed 64 MB).  The inputs depend only on the arguments.
+`--full` adds everything else, each block outside the headline's timed region:
   verified              the codebook of the timed configuration, re-encoded after the timed region by the VALU-only sweep
                         (another kernel family) and compared record by record on the device
   sustained             the same step loop for >= 2 s of wall time, with the clock the chip held during it
@@ -63,7 +70,7 @@ WORKLOADS = {
 }
 OTHER_CONFIGS = ["cfg3", "cfg4", "cfg4iso1", "cfg5"]          # timed after the headline at N = 1 (`other_configs`)
 
-HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0        # MI355X: HBM3E 8.0 TB/s spec
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "i8": 5000.0}   # dense peaks, MI355X_MICROARCH.md "Matrix cores"
 PEAK_CLOCK_GHZ = 2.4                     # the clock those peaks are quoted at
 # Measured on MI355X (profiles/r01_valu_issue_rate_microbench.txt): v_dot4_u32_u8 -- like v_mad_i32_i24,
@@ -230,6 +237,33 @@ def cpu_baseline(wl, img, budget_s=12.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(dirpath, res, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: writes the result dict of the last timed step (numpy arrays with common leading dims: [planes, N], or
+    [N] for --inproc) as dirpath/<name>.npy -- float32 arrays as they are (bit for bit, NaN included), integer arrays as
+    float64 (exact).  When the whole would exceed `limit_bytes`, a fixed, seeded sample of (plane, range) rows is written
+    instead, flattened to [n, ...], beside `sample_index.npy` (the flat plane * N + range index of every row, float64).
+    Returns the names written."""
+    import numpy as np
+    out = {k: (np.ascontiguousarray(v, np.float32) if v.dtype == np.float32 else np.asarray(v, np.float64)) for k, v in res.items()}
+    nlead = min(v.ndim for v in out.values())
+    rows = int(np.prod(next(iter(out.values())).shape[:nlead]))
+    row_bytes = sum(v.nbytes // max(rows, 1) for v in out.values())
+    room = limit_bytes - 256 * (len(out) + 1)                       # the .npy headers
+    if rows * row_bytes > room:
+        n = max(1, room // (row_bytes + 8))                         # + 8: sample_index itself
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, n, replace=False))
+        out = {k: v.reshape((rows,) + v.shape[nlead:])[pick] for k, v in out.items()}
+        out["sample_index"] = pick.astype(np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+    return sorted(out)
+
+
 def probe(args, world, rank):
     """--probe: the launcher + rendezvous + codebook gather with synthetic records on the CPU (gloo), no GPU and no
     libfic_hip.so.  Used by tests/test_bench_launcher.py; its output is not a benchmark line."""
@@ -259,10 +293,17 @@ def probe(args, world, rank):
     return 0 if (ok or rank != 0) else 1
 
 
+def _positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{s}: must be at least 1")
+    return v
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=_positive_int, default=10, help="timed steps of the headline (exactly this many)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
@@ -280,6 +321,12 @@ def parse_args(argv=None):
                          "(bf16 / i8 operands); 6 = matrix-core sweep with the normalised f16 prune GEMM")
     ap.add_argument("--pipeline", type=int, default=1, choices=[1, 2],
                     help="contexts/streams that take the steps alternately (2: prep of step k+1 overlaps the tail of sweep k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: verified, sustained, valu_only, pipelined, single_image, "
+                         "other_configs, strong_cfg4, cpu_baseline and the in-kernel clock of `roofline` (the --no-* flags "
+                         "below leave parts out); without it a run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the extra timings (valu_only, pipelined, single_image, sustained, other_configs)")
     ap.add_argument("--no-extra", action="store_true", help="skip other_configs / strong_cfg4 only")
@@ -293,7 +340,10 @@ def parse_args(argv=None):
     ap.add_argument("--probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--probe-fail-rank", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--probe-hang-rank", type=int, default=None, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.full:                      # a plain run: the headline only
+        a.no_cpu_baseline = a.no_alt = a.no_extra = a.no_verify = True
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -377,6 +427,8 @@ class Run:
         self.stage = [None] * self.nbuf      # copies of this rank's span where it is not contiguous in `records`
         self.staged = [None] * self.nbuf
         self.gathered = [None] * self.nbuf
+        self.last_ci = 0                     # the context of the last step, and (N > 1, rank 0) the codebook it gathered
+        self.last_full = None
         self.step_no = 0
         self.depth = 1
         self.Nr, self.Nd = self.core.n_ranges, self.core.n_domains
@@ -414,6 +466,7 @@ class Run:
         k = self.step_no % self.nbuf
         ci = self.step_no % depth
         self.step_no += 1
+        self.last_ci = ci
         c_, compute = self.cores[ci], self.computes[ci]
         if env.world == 1:
             c_.encode(self.begin, self.count, compute)
@@ -432,9 +485,16 @@ class Run:
         cur = torch.cuda.current_stream()
         cur.wait_event(self.staged[k])
         rec = self.stage[k] if env.backend == "nccl" else self.stage[k].cpu()
-        env.fic_amd.gather_records(rec, self.spans, None, 0)
+        self.last_full = env.fic_amd.gather_records(rec, self.spans, None, 0)
         self.gathered[k] = torch.cuda.Event()
         self.gathered[k].record(cur)
+
+    def outputs(self):
+        """What the last step delivered to its caller, as a numpy result dict (fic_amd.unpack_records): at N = 1 the records
+        of the context that ran it, at N > 1 the codebook gathered on rank 0 (None on the other ranks)."""
+        self.env.torch.cuda.synchronize()
+        rec = self.records[self.last_ci] if self.env.world == 1 else self.last_full
+        return None if rec is None else self.env.fic_amd.unpack_records(rec.cpu().numpy())
 
     def sweep_times(self, reset=True):
         ms = n = 0
@@ -679,6 +739,9 @@ def main():
     for _ in range(max(args.warmup, depth) if args.warmup else 0):
         run.step()
     dt, sweep_ms, sweep_n = run.timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        watchdog.stage = "headline: --dump-outputs"
+        dump_outputs(args.dump_outputs, run.outputs())
     dt = env.max_over_ranks(dt)
     per_rank_sweep_ms = env.gather_floats(sweep_ms / max(sweep_n, 1))
     rccl_ranks = None
@@ -694,7 +757,7 @@ def main():
     if rank == 0:
         kind = info["sweep_kind"]
         clock_ghz = None
-        if kind == 6:
+        if kind == 6 and args.full:
             clock_ghz = measure_clock(run, max(5, min(args.steps, 20)))["clock_ghz"]
         avg_ms = sweep_ms / max(sweep_n, 1)
         roofline, hbm_logical, pair_evals = roofline_blocks(args, run, info, avg_ms, sweep_n, clock_ghz)
@@ -912,6 +975,8 @@ def bench_inproc(args, wl):
     for _ in range(args.steps):
         r = capi.encode_gray_multi(img, B, None, n_iso, args.gpus)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r)
     nr = r["idx_local"].size
     print(json.dumps({"metric": f"range-block matches/sec ({B}x{B} R, {2 * B}x{2 * B} D, {n_iso} iso), in-library multi-device entry",
                       "value": nr * args.steps / dt, "unit": "range-block matches/s", "n_gpus": args.gpus, "steps": args.steps,

@@ -79,7 +79,7 @@ def _bench(args, env=None):
 
 
 def test_bench_bare_single_gpu_line():
-    j = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--planes", "2", "--cpu-budget", "1"])
+    j = _bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--planes", "2", "--cpu-budget", "1"])
     assert j["n_gpus"] == 1 and j["value"] > 0 and j["unit"] == "range-block matches/s"
     assert j["roofline"]["bound"] in ("mfma", "valu") and 0 < j["roofline"]["frac"] < 1.5
     assert j["roofline_hbm_logical"]["frac"] > 0 and j["cpu_baseline"]["value"] > 0
@@ -96,10 +96,58 @@ def test_bench_self_launches_two_ranks():
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["value"] > 0
 
 
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY_KEYS = ("sustained", "valu_only", "pipelined", "single_image", "other_configs", "strong_cfg4")
+
+
+def _encoded(imgs, B, n_iso):
+    P, H, W = imgs.shape
+    with fic_amd.Encoder(W, H, B, None, n_iso, P) as enc:
+        enc.set_gray(imgs)
+        enc.encode()
+        return enc.results()
+
+
+def _same_as_dump(d, want):
+    names = sorted(f[:-4] for f in os.listdir(d))
+    assert names == ["a", "b", "idx_local", "iso", "qrows"], names
+    for k in names:
+        got = np.load(os.path.join(d, k + ".npy"))
+        assert got.dtype in (np.float32, np.float64) and got.shape == want[k].shape, (k, got.dtype, got.shape)
+        if want[k].dtype == np.float32:
+            assert got.dtype == np.float32 and same_f32(got, want[k]), k
+        else:
+            assert (got == want[k]).all(), k
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the headline only, and --dump-outputs writes the codebook of its last timed step: the
+    records of the batch bench.py builds (same seeds), equal to an encode of those images through the library."""
+    d = str(tmp_path / "out")
+    j = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--planes", "2", "--dump-outputs", d])
+    assert all(k in j for k in HEADLINE_KEYS) and j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert not any(k in j for k in FULL_ONLY_KEYS), sorted(j)
+    assert j["verified"] is None and j["cpu_baseline"] is None
+    assert j["roofline"]["bound"] == "mfma" and j["roofline"]["frac"] > 0 and j["roofline"]["clock_ghz"] is None
+    s = synth.SEEDS["cfg2"]
+    imgs = np.stack([synth.image_u(512, 512, s + 3 * p) for p in range(2)])
+    _same_as_dump(d, _encoded(imgs, 8, 8))
+
+
+def test_bench_two_ranks_dump_outputs_is_the_gathered_codebook(tmp_path):
+    """At N > 1 rank 0 dumps the codebook the gather delivered: config 4's image (shrunk) range-sharded over two ranks."""
+    d = str(tmp_path / "out")
+    j = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg4", "--size", "512", "--scaling", "strong",
+                "--dump-outputs", d], {"FIC_BENCH_BACKEND": "gloo"})
+    assert j["n_gpus"] == 2 and j["scaling"] == "strong"
+    want = _encoded(synth.image_u(512, 512, synth.SEEDS["cfg4"])[None], 8, 8)
+    _same_as_dump(d, {k: want[k] for k in ("idx_local", "a", "b", "iso", "qrows")})
+
+
 def test_bench_default_line_carries_every_block():
-    """The default line (what the driver runs at N = 1): the headline plus `verified`, `sustained`, `other_configs`
+    """The --full line at N = 1: the headline plus `verified`, `sustained`, `other_configs`
     (BASELINE configs 3, 4, 4 with 1 isometry, 5) and `strong_cfg4`.  The big images are shrunk for the test."""
-    j = _bench(["--steps", "2", "--warmup", "1", "--cpu-budget", "1", "--sustain", "0.3", "--extra-size", "512", "--extra-steps", "2"])
+    j = _bench(["--full", "--steps", "2", "--warmup", "1", "--cpu-budget", "1", "--sustain", "0.3", "--extra-size", "512", "--extra-steps", "2"])
     assert j["verified"] is True and j["verified_detail"]["against"] == "k_sweep_d4"
     assert j["config"]["sweep_kind"] == 6 and j["roofline"]["kernel"] == "k_sweep_q<4, 2, false>"
     assert 0 < j["roofline"]["executed_frac"] <= j["roofline"]["frac"]
@@ -113,9 +161,9 @@ def test_bench_default_line_carries_every_block():
 
 
 def test_bench_two_ranks_default_line_has_the_strong_scaling_block():
-    """`python bench.py --gpus 2` with no workload flags (what the driver runs on the multi-GPU node): weak cfg2 headline and
+    """`python bench.py --gpus 2 --full` with no workload flags: weak cfg2 headline and
     the strong-scaling block, config 4's range blocks sharded over the two ranks through the same gather."""
-    j = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--extra-size", "512", "--extra-steps", "2"], {"FIC_BENCH_BACKEND": "gloo"})
+    j = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--extra-size", "512", "--extra-steps", "2"], {"FIC_BENCH_BACKEND": "gloo"})
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["verified"] is True
     s4 = j["strong_cfg4"]
     assert s4["n_gpus"] == 2 and s4["scaling"] == "strong" and s4["verified"] is True and s4["value"] > 0

@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 if [ "$PART" = A ]; then
   timeout -k 10 700 python -m pytest tests -m gpu -x -q > $O/${TAG}_pytest.log 2>&1; rc=$?; echo "pytest rc=$rc" >> $O/${TAG}_pytest.log; tail -4 $O/${TAG}_pytest.log
   [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 400 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -20 $O/${TAG}_bench_default.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -20 $O/${TAG}_bench_default.err; exit 1; }
   echo "bench default ok"
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
   timeout -k 10 400 python tools/q_stats.py 512,8,8,64 512,8,8,64,U,5 512,8,8,64,S 512,8,1,64 512,8,1,64,S 512,8,8,1 512,8,1,1 \
@@ -22,12 +22,12 @@ if [ "$PART" = A ]; then
   timeout -k 10 200 python tools/decode_timing.py > $O/${TAG}_decode_timing.json 2> $O/${TAG}_decode.err || { tail $O/${TAG}_decode.err; exit 1; }
   FIC_FAKE_DEVICES=8 timeout -k 10 300 python bench.py --inproc --gpus 4 --workload cfg4 --size 2048 --steps 3 --warmup 1 > $O/${TAG}_inproc4_fake.json 2> $O/${TAG}_inproc.err || { tail $O/${TAG}_inproc.err; exit 1; }
   timeout -k 10 300 python bench.py --inproc --gpus 1 --workload cfg4 --size 2048 --steps 3 --warmup 1 > $O/${TAG}_inproc1.json 2>> $O/${TAG}_inproc.err || { tail $O/${TAG}_inproc.err; exit 1; }
-  FIC_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 5 --extra-size 2048 > $O/${TAG}_bench_gloo2.json 2> $O/${TAG}_bench_gloo2.err || { tail -20 $O/${TAG}_bench_gloo2.err; exit 1; }
+  FIC_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --extra-size 2048 > $O/${TAG}_bench_gloo2.json 2> $O/${TAG}_bench_gloo2.err || { tail -20 $O/${TAG}_bench_gloo2.err; exit 1; }
   echo "part A ok"
   exit 0
 fi
 if [ "$PART" = D ]; then       # after a late change: the bench line, the single image, the traffic stamp of the final csrc/
-  timeout -k 10 400 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -20 $O/${TAG}_bench_default.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -20 $O/${TAG}_bench_default.err; exit 1; }
   export TMPDIR=/tmp; cd /tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_single8 -- python3 $R/tools/single_image_trace.py 8 > $O/${TAG}_single8_under_rocprof.json 2> $O/${TAG}_prof_single8.err || exit 1
   cp "$(find $O/${TAG}_prof_single8 -name '*kernel_stats.csv' | head -1)" $O/${TAG}_single8_kernel_stats.csv && rm -rf $O/${TAG}_prof_single8
@@ -36,7 +36,7 @@ if [ "$PART" = D ]; then       # after a late change: the bench line, the single
 fi
 if [ "$PART" = C ]; then
   timeout -k 10 300 python tools/rgb_timing.py > $O/${TAG}_rgb.json 2> $O/${TAG}_rgb.err || { tail $O/${TAG}_rgb.err; exit 1; }
-  FIC_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 4 --steps 5 --extra-size 2048 > $O/${TAG}_bench_gloo4.json 2> $O/${TAG}_bench_gloo4.err || { tail -20 $O/${TAG}_bench_gloo4.err; exit 1; }
+  FIC_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 4 --steps 5 --extra-size 2048 > $O/${TAG}_bench_gloo4.json 2> $O/${TAG}_bench_gloo4.err || { tail -20 $O/${TAG}_bench_gloo4.err; exit 1; }
   bash tools/gpu_fuzz_soak.sh ${TAG} 40 301 302 303 304 305 306 || exit 1
   echo "part C ok"
   exit 0
