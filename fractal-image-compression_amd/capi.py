@@ -113,6 +113,8 @@ def lib():
         "fic_debug_decode_gray_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, f32p, ip, ip]),
         "fic_debug_sqrt_f64": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
         "fic_ctx_debug_pool_host": (C.c_int, [vp, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p]),
+        "fic_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -124,7 +126,12 @@ def lib():
 
 def has_xcheck():
     """True when the library was built with round 1's exact-covariance matrix-core sweeps ("sweep" = 3 / 4; build.py,
-    FIC_BUILD_XCHECK, on by default) -- the test-suite's independent cross-checks of the default sweep."""
+    FIC_BUILD_XCHECK, on by default) -- the test-suite's independent cross-checks of the default sweep.  False when the
+    library file does not exist (test modules ask this at import time, and a CPU-only run must still collect them); a
+    library that exists but fails to load raises, as every other entry does."""
+    so = os.environ.get("FIC_HIP_SO") or SO_PATH
+    if not os.path.exists(so):
+        return False
     return b"+xcheck" in lib().fic_version()
 
 
@@ -303,6 +310,19 @@ class RgbEncoder:
 
     def last_sweep(self):
         return check(lib().fic_rgb_ctx_last_sweep(self._h))
+
+    Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "amax")
+
+    def debug_q(self, which):
+        """Raw bytes (uint8 array) of one store of the matrix-core RGB sweep for the last plane encoded ("sweep" = 2):
+        "pool" / "rng" the A / B fragments, "flat" the flat-tile flags, "E" the per-range error bounds, "rng_st" {0,
+        varianzRange} per range, "amax" the largest domain-operand norm (fic_rgb_ctx_debug_q_host; tests/qmodel.py decodes them)."""
+        i = self.Q_STORES.index(which)
+        size = C.c_int64()
+        check(lib().fic_rgb_ctx_debug_q_host(self._h, i, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        check(lib().fic_rgb_ctx_debug_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
+        return out
 
     def results(self):
         P, N = self.planes, self.n_ranges

@@ -784,6 +784,9 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
     } else if (!strcmp(name, "q_shape")) {             // MFMA shape of the 1-isometry k_sweep_q at B = 8 / 16 (tests, A/B runs)
         if (value < 0 || value > 2) return fail(FIC_E_ARGUMENT, "q_shape must be 0 (by pool size), 1 (16x16x32) or 2 (32x32x16)");
         c->g.q_shape = value;
+    } else if (!strcmp(name, "q_eshift")) {            // diagnostic: k_sweep_q's E_r times 2^-value (> 0: below the derivation, WRONG codebooks)
+        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "q_eshift must be in -12..4");
+        c->g.q_eshift = value;
     } else if (!strcmp(name, "q_noflag")) {            // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
         c->opt_noflag = value ? 1 : 0;
     } else if (!strcmp(name, "time_sweep")) {
@@ -918,6 +921,33 @@ int fic_ctx_debug_pool_host(fic_ctx* c, uint8_t* pix, uint32_t* sum, uint32_t* v
         }
     }
     if (scaled) HIP_TRY(hipMemcpy(scaled, c->b.scaled, (size_t)g.planes * g.Ws * g.Hs, hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
+int fic_ctx_debug_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
+{
+    if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: null argument");
+    if (!c->encoded_any || !c->q_pool) return fail(FIC_E_STATE, "fic_ctx_debug_q_host: no encode through the default sweep (\"sweep\" = 6) yet");
+    const FicGeom& g = c->g;
+    const QShape q = q_shape(g);
+    const size_t P = (size_t)g.planes, NK = (size_t)g.n / 16;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (which) {                                   // the stores exactly as q_prep allocates them
+    case 0: src = c->q_pool; bytes = P * q.ndtiles_alloc * NK * 64 * 16; break;
+    case 1: src = c->q_flat; bytes = P * q.ndtiles_alloc * sizeof(uint32_t); break;
+    case 2: src = c->q_rng; bytes = P * q.nct_alloc * NK * 64 * 16; break;
+    case 3: src = c->q_E; bytes = P * g.Nr_pad * sizeof(float); break;
+    case 4: src = c->b.rng_st; bytes = P * g.Nr_pad * sizeof(FicRngStat); break;
+    case 5: src = c->q_rngC; bytes = P * g.Nr_pad * fic_q_cols_per_range(g.B, g.n_iso) * g.n; break;
+    default: return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: which must be 0..5");
+    }
+    *size = (int64_t)bytes;
+    if (!out) return FIC_OK;
+    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_q_host: %zu bytes needed", bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return FIC_OK;
 }
 

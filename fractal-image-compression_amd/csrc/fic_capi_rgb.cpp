@@ -243,7 +243,41 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         c->opt_chunks = value;
         return FIC_OK;
     }
+    if (!strcmp(name, "q_eshift")) {                   // diagnostic: the matrix-core sweep's E_r times 2^-value (> 0: WRONG codebooks)
+        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: q_eshift must be in -12..4");
+        c->g.q_eshift = value;
+        return FIC_OK;
+    }
     return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: unknown option '%s'", name);
+}
+
+int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
+{
+    if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_q_host: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any || c->last_sweep != 2 || !c->q.poolQ)
+        return fail(FIC_E_STATE, "fic_rgb_ctx_debug_q_host: no encode through the matrix-core sweep (\"sweep\" = 2) yet");
+    const FicGeom& g = c->g;
+    const FicRgbQ& q = c->q;
+    const size_t NK = (size_t)g.n / 16;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (which) {                                   // the stores exactly as rgb_q_setup allocates them (last plane encoded)
+    case 0: src = q.poolQ; bytes = (size_t)q.ndtiles_alloc * NK * 64 * 16; break;
+    case 1: src = q.dflat; bytes = (size_t)q.ndtiles_alloc * sizeof(uint32_t); break;
+    case 2: src = q.rngQ; bytes = (size_t)q.nct_alloc * NK * 64 * 16; break;
+    case 3: src = q.rngE; bytes = (size_t)g.Nr * sizeof(float); break;
+    case 4: src = q.qst; bytes = (size_t)g.Nr * sizeof(FicRngStat); break;
+    case 5: src = q.amax; bytes = sizeof(uint32_t); break;
+    default: return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_q_host: which must be 0..5");
+    }
+    *size = (int64_t)bytes;
+    if (!out) return FIC_OK;
+    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_rgb_ctx_debug_q_host: %zu bytes needed", bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return FIC_OK;
 }
 
 int fic_rgb_ctx_last_sweep(fic_rgb_ctx* c)

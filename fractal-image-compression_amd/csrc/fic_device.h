@@ -19,6 +19,7 @@ struct FicGeom {
     int Nd_pad;              // Nd + FIC_POOL_PAD (zero tail so the prefetch may over-read)
     int full;                // 1 when wK == Dw == Dh (window origin is (0,0) for every range)
     int q_shape;             // MFMA shape of the 1-isometry k_sweep_q at B = 8 / 16: 0 = by pool size, 1 = 16x16x32, 2 = 32x32x16 (option "q_shape")
+    int q_eshift;            // diagnostic (option "q_eshift", -12..4): k_sweep_q's error bound E_r is stored times 2^-q_eshift; > 0 gives WRONG codebooks
 };
 
 #define FIC_POOL_PAD 8

@@ -116,6 +116,11 @@ __device__ __forceinline__ void frag_slot(int shape16, int NK, int s, int lane, 
     }
 }
 
+// Option "q_eshift" (diagnostic): the stored E_r is scaled by 2^-q_eshift, an exact power of two (q_eshift = 0: times 1, the
+// bound of the header bit for bit).  Negative values widen the threshold (more pairs flagged, same codebooks); positive values
+// narrow it below the derivation and give WRONG codebooks -- tests/test_gpu_q_bound.py shows that the suite notices.
+__device__ __forceinline__ float q_escale(const FicGeom& g) { return __int_as_float((127 - g.q_eshift) << 23); }
+
 // two floats -> packed f16 pair (round to nearest even), element 0 in the low half
 __device__ __forceinline__ int f16_pair(float lo, float hi)
 {
@@ -328,7 +333,7 @@ __global__ __launch_bounds__(256) void k_range_q(const uint8_t* __restrict__ gra
                 st.rM = j < g.Nr ? rM : 0;
                 st.rem = j < g.Nr ? (int)S - (rM << g.lgn) : 0;
                 rng_st[o] = st;
-                rngE[o] = __fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), FIC_Q_ECOEF), FIC_Q_EABS);
+                rngE[o] = __fmul_rn(__fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), FIC_Q_ECOEF), FIC_Q_EABS), q_escale(g));
                 key[o] = FIC_KEY_NONE;
                 theta_g[o] = FIC_Q_THG_NONE;
             }
@@ -508,7 +513,7 @@ __device__ __forceinline__ void range_q8_body(int grp, int plane, const uint8_t*
                 st.rM = j < g.Nr ? rM : 0;
                 st.rem = j < g.Nr ? (int)S - (rM << 6) : 0;
                 rng_st[o] = st;
-                rngE[o] = __fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), FIC_Q_ECOEF), FIC_Q_EABS);
+                rngE[o] = __fmul_rn(__fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), FIC_Q_ECOEF), FIC_Q_EABS), q_escale(g));
                 key[o] = FIC_KEY_NONE;
                 theta_g[o] = FIC_Q_THG_NONE;
             }
@@ -1638,8 +1643,8 @@ __global__ __launch_bounds__(256) void k_range_qrgb(const int16_t* __restrict__ 
             st.rM = 0;
             st.rem = rst[j].vR;
             qst[j] = st;
-            rngE[j] = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(__fsqrt_rn((float)s2), 1.0001f), am), FIC_Q_ECOEF),
-                                __fmul_rn(FIC_Q_EABS, __fadd_rn(1.0f, am)));
+            rngE[j] = __fmul_rn(__fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(__fsqrt_rn((float)s2), 1.0001f), am), FIC_Q_ECOEF),
+                                          __fmul_rn(FIC_Q_EABS, __fadd_rn(1.0f, am))), q_escale(g));
             key[j] = FIC_KEY_NONE;
             theta_g[j] = FIC_Q_THG_NONE;
         }

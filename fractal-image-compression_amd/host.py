@@ -211,6 +211,19 @@ class Encoder:
                                                       capi.ptr(v, C.c_uint32), capi.ptr(sc, C.c_uint8)))
         return {"pix": pix, "sum": s, "var": v, "scaled": sc}
 
+    Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "rngC")
+
+    def debug_q(self, which):
+        """Raw bytes (uint8 array) of one store of k_sweep_q after an encode through it ("sweep" = 6): "pool" / "rng" the
+        A / B fragments, "flat" the flat-tile flags, "E" the per-range error bounds, "rng_st" {rM, rem} per range, "rngC" the
+        columns' copies as bytes (fic_ctx_debug_q_host; tests/qmodel.py decodes them)."""
+        i = self.Q_STORES.index(which)
+        size = C.c_int64()
+        capi.check(capi.lib().fic_ctx_debug_q_host(self._h, i, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        capi.check(capi.lib().fic_ctx_debug_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
+        return out
+
 
 def encode_rgb_per_channel(rgb, B, wK=None, n_iso=1, device=0, sweep=0):
     """BASELINE.json config 5: a batch of colour images encoded as 3 independent grey planes each (NOT the

@@ -216,6 +216,10 @@ FIC_API int fic_ctx_decode_host(fic_ctx* ctx, uint8_t* gray_out, float* avg_erro
  *                 launches and windowed search keep the VALU sweep, which is faster there)
  *   "q_shape"     matrix instruction of the 1-isometry k_sweep_q at B = 8 / 16: 0 by pool size (default: v_mfma_f32_16x16x32_f16
  *                 from 10^5 K-steps per range column, else 32x32x16), 1 = 16x16x32 (k_sweep_q16), 2 = 32x32x16; same codebooks
+ *   "q_eshift"    diagnostic, -12..4 (default 0): k_sweep_q stores its per-range error bound E_r times 2^-q_eshift.  Negative
+ *                 values widen the prune threshold (more pairs evaluated exactly, same codebooks); positive values narrow it
+ *                 below what the derivation in fic_q.hip allows and give WRONG codebooks (the tests show that they are caught).
+ *                 Like "q_noflag", not for production use.  fic_rgb_ctx_set_option takes it too (matrix-core RGB sweep).
  *   "chunks"      domain-pool chunks per range tile for the fast kernel (0 = auto)
  *   "time_sweep"  1: bracket every sweep launch with hipEvents on its stream */
 FIC_API int fic_ctx_set_option(fic_ctx* ctx, const char* name, int value);
@@ -265,6 +269,16 @@ FIC_API int fic_debug_gather_fallbacks(void);
 /* Test hook: copies the pool of the last encode to the host: pix u8 [planes][N_d][n],
  * sum u32 [planes][N_d], var u32 [planes][N_d], scaled u8 [planes][h/2][w/2]. NULLs allowed. */
 FIC_API int fic_ctx_debug_pool_host(fic_ctx* ctx, uint8_t* pix, uint32_t* sum, uint32_t* var, uint8_t* scaled);
+/* Test hook: raw bytes of one store of the default sweep k_sweep_q after an encode through it, as the prep kernels left them:
+ * which = 0 A fragments [planes][domain tiles + padding][NK][64] x 8 f16, 1 flat-tile flags u32 [planes][domain tiles + padding],
+ * 2 B fragments [planes][column tiles + padding][NK][64] x 8 f16, 3 E_r f32 [planes][padded N_r], 4 range statistics
+ * {rM, rem} i32 pairs [planes][padded N_r], 5 the columns' copies as bytes [planes][padded N_r][columns per range][n].
+ * *size = the store's size in bytes; out may be NULL (size only), else capacity must hold it. */
+FIC_API int fic_ctx_debug_q_host(fic_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
+/* Test hook, joint RGB: the same for the matrix-core RGB sweep ("sweep" = 2) of the LAST plane encoded: which = 0 A fragments
+ * [domain tiles + padding][NK][64] x 8 f16, 1 flat-tile flags, 2 B fragments [column tiles + padding][NK][64] x 8 f16, 3 E_r f32 [N_r],
+ * 4 {0, varianzRange} i32 pairs [N_r], 5 Amax (f32 bits, one u32). */
+FIC_API int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 
 #ifdef __cplusplus
 }
