@@ -115,6 +115,11 @@ def lib():
         "fic_ctx_debug_pool_host": (C.c_int, [vp, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p]),
         "fic_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "fic_encode_gray_quadtree_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_encode_gray_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_write_run_quadtree": (C.c_int64, [i32p] + [C.c_int] * 7 + [u8p, C.c_int64]),
+        "fic_decode_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_debug_quadtree_sse": (C.c_int, [u8p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -362,3 +367,72 @@ def write_run_gray(qrows, w, h, B, wK):
     n = lib().fic_write_run_gray(ptr(q, C.c_int32), q.shape[0], w, h, B, wK, ptr(out, C.c_uint8), out.size)
     check(int(n))
     return out.tobytes()
+
+
+QT_LEAF_FIELDS = ("x", "y", "B", "idx_local", "qa", "qb", "iso")
+
+
+def _qt_levels(B_max, B_min):
+    return [B for B in (16, 8, 4) if B_min <= B <= B_max]
+
+
+def encode_gray_quadtree(gray, B_max, B_min, wK=0, n_iso=1, threshold=float("inf"), device=0):
+    """Quadtree encode of `gray`: uint8 [H, W] (fic_encode_gray_quadtree_u8) or the int32 ARGB pixels of RasterImage.argb as
+    [H, W] (fic_encode_gray_quadtree_argb).  wK = 0: full search at every level.  Returns the leaf table int32 [n_leaves, 7] with the columns
+    QT_LEAF_FIELDS, in stream order (top-level blocks in scanline order, children TL, TR, BL, BR depth first)."""
+    g = np.asarray(gray)
+    if g.dtype == np.uint8:
+        g = np.ascontiguousarray(g)
+        h, w = g.shape
+        fn, p = lib().fic_encode_gray_quadtree_u8, ptr(g, C.c_uint8)
+    else:
+        g = np.ascontiguousarray(g, np.int32)
+        h, w = g.shape
+        fn, p = lib().fic_encode_gray_quadtree_argb, ptr(g, C.c_int32)
+    cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
+    out = np.zeros((max(cap, 1), 7), np.int32)
+    n = C.c_int()
+    check(fn(p, w, h, B_max, B_min, wK, n_iso, float(threshold), device, ptr(out, C.c_int32), out.shape[0], C.byref(n)))
+    return out[:n.value].copy()
+
+
+def debug_quadtree_sse(gray, B_max, B_min, wK=0, n_iso=1, device=0):
+    """Per-level collage SSE of the quadtree encode: {B: uint32 [Rh, Rw]} for B = B_max .. B_min (fic_debug_quadtree_sse)."""
+    g = np.ascontiguousarray(gray, np.uint8)
+    h, w = g.shape
+    levels = _qt_levels(B_max, B_min)
+    sizes = [(h // B) * (w // B) for B in levels]
+    out = np.zeros(max(sum(sizes), 1), np.uint32)
+    check(lib().fic_debug_quadtree_sse(ptr(g, C.c_uint8), w, h, B_max, B_min, wK, n_iso, device, ptr(out, C.c_uint32), out.size))
+    r, o = {}, 0
+    for B, n in zip(levels, sizes):
+        r[B] = out[o:o + n].reshape(h // B, w // B)
+        o += n
+    return r
+
+
+def write_run_quadtree(leaves, w, h, B_max, B_min, wK, n_iso):
+    """Quadtree stream (tag 2): header {2, w, h, B_max, B_min, wK, n_iso, n_leaves}, then {B, idx_local, qa, qb[, iso]} per
+    leaf, big-endian int32 (fic_write_run_quadtree).  `leaves`: int32 [n, 7] as encode_gray_quadtree returns it."""
+    q = np.ascontiguousarray(leaves, np.int32).reshape(-1, 7)
+    out = np.zeros(32 + 4 * (5 if n_iso == 8 else 4) * q.shape[0], np.uint8)
+    n = lib().fic_write_run_quadtree(ptr(q, C.c_int32), q.shape[0], w, h, B_max, B_min, wK, n_iso, ptr(out, C.c_uint8), out.size)
+    check(int(n))
+    return out.tobytes()
+
+
+def decode_quadtree_run(run, device=0, avg_error_in=0.0):
+    """Decoder of a quadtree stream on the GPU (fic_decode_quadtree_run).  Returns (gray uint8 [H,W], avgError float32 after the
+    call, iterations)."""
+    buf = np.frombuffer(bytes(run), np.uint8)
+    if buf.size < 32:
+        raise FicError(-3, "quadtree stream shorter than its header")
+    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
+    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
+    cap = max(w, 0) * max(h, 0)
+    out = np.zeros(max(cap, 1), np.uint8)
+    avg = C.c_float(avg_error_in)
+    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
+    check(lib().fic_decode_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_uint8), cap, C.byref(wo),
+                                        C.byref(ho), C.byref(avg), C.byref(it)))
+    return out[:cap].reshape(h, w), np.float32(avg.value), it.value

@@ -6,18 +6,16 @@ using namespace ficd;
 
 // ---- decoder (decodeGreyScale FC:356-421) ------------------------------------------------------
 namespace {
-// Device arenas of the stream decoders, kept between calls (the GUI decodes after every encode, CTL:178-179): one
-// allocation per (device, size class) instead of four hipMalloc/hipFree per call.  fic_release_cache() frees them.
-struct Arena {
-    int device = -1;
-    size_t bytes = 0;
-    char* base = nullptr;
-};
+// Device arenas of the stream decoders (struct Arena, fic_internal.h), kept between calls (the GUI decodes after every
+// encode, CTL:178-179): one allocation per (device, size class) instead of four hipMalloc/hipFree per call.
+// fic_release_cache() frees them.
 std::mutex g_arena_mu;
 std::vector<Arena> g_arenas;
 constexpr size_t kArenaSlots = 4;
 
-int arena_take(int device, size_t bytes, Arena* out)
+}  // namespace
+
+int ficd::arena_take(int device, size_t bytes, Arena* out)
 {
     {
         std::lock_guard<std::mutex> lk(g_arena_mu);
@@ -33,7 +31,7 @@ int arena_take(int device, size_t bytes, Arena* out)
     HIP_TRY(hipMalloc((void**)&out->base, bytes));
     return FIC_OK;
 }
-void arena_give(const Arena& a)
+void ficd::arena_give(const Arena& a)
 {
     Arena evict;
     {
@@ -46,7 +44,6 @@ void arena_give(const Arena& a)
     (void)hipSetDevice(evict.device);
     (void)hipFree(evict.base);
 }
-}  // namespace
 
 void ficd::release_decoder_arenas()
 {
@@ -60,26 +57,24 @@ void ficd::release_decoder_arenas()
 
 static thread_local int g_last_sum_fallbacks = 0;
 
-extern "C" {
-
 // Runs the reconstruction loop on the device.  The first 8 iterations are enqueued in one go, later ones in pairs, and the
 // per-plane loop state is read back after each group (a converging decode takes 6-9 iterations): one host sync per
-// group, none per iteration; iterations enqueued behind the last one exit at once.
-//   d_state [planes], d_sqbuf u32 [planes][W*H]: scratch of the caller
-static int run_decode_loop(const FicGeom& g, uint8_t* d_scaled, uint8_t* d_image, const int32_t* d_qrows,
-                           const int32_t* d_iso, FicDecodeState* d_state, uint32_t* d_sqbuf, const float* avg_in,
-                           float* avg_out, int* iters_out, int* seq_out, hipStream_t s)
+// group, none per iteration; iterations enqueued behind the last one exit at once.  `iteration(counter)` enqueues one
+// iteration (scale, paint, loop control) on s; d_image [planes][npix] starts grey 128.
+//   d_state [planes]: scratch of the caller
+int ficd::decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState* d_state, const float* avg_in, float* avg_out,
+                      int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration)
 {
-    const size_t P = (size_t)g.planes;
+    const size_t P = (size_t)planes;
     std::vector<FicDecodeState> st(P);
     memset(st.data(), 0, P * sizeof(FicDecodeState));
     for (size_t p = 0; p < P; p++) st[p].avg = avg_in ? avg_in[p] : 0.0f;   // static avgError is never reset (FC:20)
     int rc = FIC_OK;
     hipError_t e = hipMemcpyAsync(d_state, st.data(), P * sizeof(FicDecodeState), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_image, 128, P * g.W * g.H, s);        // generateGrayImage FC:1142-1148
+    if (e == hipSuccess) e = hipMemsetAsync(d_image, 128, P * npix, s);             // generateGrayImage FC:1142-1148
     if (e != hipSuccess) rc = fail(FIC_E_HIP, "decode init: %s", hipGetErrorString(e));
     for (int counter = 0; rc == FIC_OK && counter < 50; counter++) {
-        if (fic_launch_decode_iteration(d_scaled, d_image, d_qrows, d_iso, d_state, d_sqbuf, counter, g, s)) {
+        if (iteration(counter)) {
             rc = fail(FIC_E_HIP, "decode iteration launch failed");
             break;
         }
@@ -103,6 +98,18 @@ static int run_decode_loop(const FicGeom& g, uint8_t* d_scaled, uint8_t* d_image
         if (seq_out) seq_out[p] = st[p].seq_sums;
     }
     return FIC_OK;
+}
+
+extern "C" {
+
+//   d_state [planes], d_sqbuf u32 [planes][W*H]: scratch of the caller
+static int run_decode_loop(const FicGeom& g, uint8_t* d_scaled, uint8_t* d_image, const int32_t* d_qrows,
+                           const int32_t* d_iso, FicDecodeState* d_state, uint32_t* d_sqbuf, const float* avg_in,
+                           float* avg_out, int* iters_out, int* seq_out, hipStream_t s)
+{
+    return decode_loop(g.planes, (size_t)g.W * g.H, d_image, d_state, avg_in, avg_out, iters_out, seq_out, s, [&](int counter) {
+        return fic_launch_decode_iteration(d_scaled, d_image, d_qrows, d_iso, d_state, d_sqbuf, counter, g, s);
+    });
 }
 
 int fic_ctx_decode_host(fic_ctx* c, uint8_t* gray_out, float* avg_error_out, int* iterations_out)

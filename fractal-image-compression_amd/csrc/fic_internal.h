@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -50,6 +51,19 @@ fic_ctx* cache_take(int device, int w, int h, int B, int wK, int n_iso);
 void cache_give(fic_ctx* c);
 int encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device,
                    int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows);
+
+// device arenas of the stream decoders (fic_capi_decode.cpp): one allocation of at least `bytes` on `device`, returned after use
+struct Arena {
+    int device = -1;
+    size_t bytes = 0;
+    char* base = nullptr;
+};
+int arena_take(int device, size_t bytes, Arena* out);
+void arena_give(const Arena& a);
+// the decoder's loop control (decodeGreyScale FC:381-418, fic_capi_decode.cpp) around `iteration(counter)`, which enqueues one
+// iteration -- scale, paint, fic_launch_decode_step -- on s
+int decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState* d_state, const float* avg_in, float* avg_out,
+                int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration);
 
 // what fic_release_cache() frees besides the grey contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp

@@ -181,3 +181,20 @@ size_t fic_decode_sq_words(size_t planes, size_t wh);
 int fic_launch_decode_step(FicDecodeState* state, uint32_t* sqbuf, int counter, int wh, int planes, hipStream_t s);
 int fic_launch_decode_iteration(uint8_t* scaled, uint8_t* image, const int32_t* qrows, const int32_t* iso,
                                 FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
+
+// quadtree codec (fic_quadtree.hip).  One leaf of the decoder's per-level lists: position, global domain block (the level's
+// window_to_global), offset of its B*B squares in `sqbuf` (prefix sum of B^2 over the leaves before it), quantised row.
+struct FicQtLeaf {
+    int32_t x, y, gi, sqoff, qa, qb, iso, pad;
+};
+// sse u32 [g.Nr]: collage SSE of every range block of one level from its quantised rows (iso NULL: n_iso = 1)
+int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_t* qrows, const int32_t* iso, uint32_t* sse,
+                        const FicGeom& g, hipStream_t s);
+// split + compaction over nl levels (B_max >> l): counts int [Ntop], offs int [Ntop + 1] (offs[Ntop] = leaves), leaves int32
+// [leaves][7] {x, y, B, idx_local, qa, qb, iso} (NULL: count only); room for the largest possible count is the caller's
+int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
+                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
+                          hipStream_t s);
+// one paint of the n leaves of side g.B (one plane; g = that level's geometry)
+int fic_launch_decode_paint_leaves(const uint8_t* scaled, uint8_t* image, const FicQtLeaf* lv, int n, FicDecodeState* state,
+                                   uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);

@@ -1,0 +1,279 @@
+// fic_quadtree.hip -- quadtree (variable block size) grey codec on the device: collage error per range block, the split
+// decision + leaf compaction, and the decoder's paint of leaves of mixed size.  An extension like n_iso = 8: the
+// reference encodes with one block size (FC:14).  gfx950 (MI355X / CDNA4) only, wave64; -ffp-contract=off like every
+// other translation unit (the paint arithmetic is k_decode_paint's, one rounding per operation).  DESIGN.md section 4.13.
+//
+//   k_leaf_sse<B>            SSE of the quantised row of every range block of one level against the original image
+//   k_qt_count / k_qt_scan / k_qt_scatter
+//                            top-down split of every top-level (B_max) block, leaf count, exclusive scan, ordered scatter
+//   k_decode_paint_leaves<B> one decoder paint of the leaves of one level (three launches per iteration, one per level)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "fic_device.h"
+#include "fic_launch.h"
+#include "fic_devfn.h"
+
+// The quantised row's value at every pixel of a range block row, as k_decode_paint computes it (FC:394-402):
+//   a = (float) qa / 100f, b = (float) qb, value = clamp((int) fl(fl(a * d) + b)),
+// d the winner's domain pixel (isometry applied) in the 2:1-scaled image `scaled`.
+template <int B>
+__device__ __forceinline__ void qt_row_values(const uint8_t* __restrict__ scaled, const FicGeom& g, int gi, int k, int ry, float a,
+                                              float b, int (&value)[B])
+{
+    const int c = gi % g.Dw, r = gi / g.Dw;
+    const uint8_t* dom = scaled + (size_t)(r * g.abstand) * g.Ws + c * g.abstand;
+    uint8_t dpx[B];
+    if (k == 0) {
+        __builtin_memcpy(dpx, dom + (size_t)ry * g.Ws, B);
+    } else {
+        int ax, bx_, cx, ay, by_, cy;
+        iso_affine(k, B - 1, ax, bx_, cx, ay, by_, cy);
+        const int s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry, sx = ay * g.Ws + ax;
+#pragma unroll
+        for (int x = 0; x < B; x++) dpx[x] = dom[s0 + sx * x];
+    }
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        int v = java_f2i(__fadd_rn(__fmul_rn(a, (float)dpx[x]), b));
+        value[x] = v < 0 ? 0 : (v > 255 ? 255 : v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_leaf_sse<B>: sse[j] = sum over the block's pixels of (orig - value)^2, exact.  One thread per pixel row of a range block,
+// ordered like k_decode_paint (block row, pixel row, block column); the B row sums of a block meet in sse[j] (zeroed by the
+// launcher) through integer atomics, so the result does not depend on their order.  At most 256 * 255^2 < 2^32 per block.
+// ---------------------------------------------------------------------------------------------
+template <int B>
+__global__ __launch_bounds__(256) void k_leaf_sse(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ scaled,
+                                                  const int32_t* __restrict__ qrows, const int32_t* __restrict__ iso,
+                                                  uint32_t* __restrict__ sse, FicGeom g)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= g.Nr * B) return;
+    const int bx = t % g.Rw, row = t / g.Rw;
+    const int ry = row % B, by = row / B;
+    const int j = by * g.Rw + bx;
+    const int wloc = qrows[3 * j + 0];
+    const float a = __fdiv_rn((float)qrows[3 * j + 1], 100.0f);
+    const float b = (float)qrows[3 * j + 2];
+    const bool ok = wloc >= 0 && wloc < g.wK * g.wK;
+    const int gi = ok ? window_to_global(g, j, wloc) : -1;
+    if (gi < 0 || gi >= g.Nd) { atomicOr(&sse[j], 0xFFFFFFFFu); return; }   // never for an encoder's own rows: always split
+    int value[B];
+    qt_row_values<B>(scaled, g, gi, iso ? iso[j] : 0, ry, a, b, value);
+    const uint8_t* prow = gray + (size_t)row * g.W + bx * B;
+    uint32_t s = 0;
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        const int d = (int)prow[x] - value[x];
+        s += (uint32_t)(d * d);
+    }
+    if (s) atomicAdd(&sse[j], s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Split + compaction.  Level l = 0 .. nl-1 has block side B_max >> l; a block of level l is split iff l < nl - 1 and
+// (double) sse_l > (double) threshold * B * B.  Leaves are visited depth first, children TL, TR, BL, BR, top-level blocks in
+// scanline order.  One thread per top-level block walks its subtree (at most 1 + 4 + 16 nodes) with a small explicit stack:
+// k_qt_count counts the leaves, k_qt_scan (one workgroup) turns the counts into offsets, k_qt_scatter walks again and writes
+// the rows {x, y, B, idx_local, qa, qb, iso} at its offset.
+// ---------------------------------------------------------------------------------------------
+struct FicQtLevels {
+    const uint32_t* sse[3];
+    const int32_t* qrows[3];
+    const int32_t* iso[3];       // NULL: n_iso = 1 (iso 0)
+    int Rw[3];
+    int nl;                      // levels
+    int B_max;
+    int Rw_top, Ntop;
+    float threshold;
+};
+
+__device__ __forceinline__ bool qt_split(const FicQtLevels& L, int l, int x, int y)
+{
+    if (l >= L.nl - 1) return false;
+    const int B = L.B_max >> l;
+    const uint32_t s = L.sse[l][(y / B) * L.Rw[l] + x / B];
+    return (double)s > (double)L.threshold * (double)B * (double)B;
+}
+
+// Walks the subtree of top-level block t in DFS order; emit(x, y, l) per leaf.
+template <typename F>
+__device__ __forceinline__ void qt_walk(const FicQtLevels& L, int t, F emit)
+{
+    int sx[8], sy[8], sl[8];
+    int sp = 0;
+    sx[0] = (t % L.Rw_top) * L.B_max;
+    sy[0] = (t / L.Rw_top) * L.B_max;
+    sl[0] = 0;
+    sp = 1;
+    while (sp > 0) {
+        sp--;
+        const int x = sx[sp], y = sy[sp], l = sl[sp];
+        if (qt_split(L, l, x, y)) {
+            const int h = (L.B_max >> l) / 2;       // children pushed BR, BL, TR, TL: popped TL first
+            sx[sp] = x + h; sy[sp] = y + h; sl[sp] = l + 1; sp++;
+            sx[sp] = x;     sy[sp] = y + h; sl[sp] = l + 1; sp++;
+            sx[sp] = x + h; sy[sp] = y;     sl[sp] = l + 1; sp++;
+            sx[sp] = x;     sy[sp] = y;     sl[sp] = l + 1; sp++;
+        } else {
+            emit(x, y, l);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L, int* __restrict__ counts)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L.Ntop) return;
+    int n = 0;
+    qt_walk(L, t, [&](int, int, int) { n++; });
+    counts[t] = n;
+}
+
+// Exclusive scan of counts[0 .. n) into offs[0 .. n), offs[n] = the total.  One workgroup: every thread sums a contiguous
+// slice, the slice sums are scanned in LDS, then every thread writes its slice's offsets.
+#define FIC_QT_SCAN_THREADS 1024
+__global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __restrict__ counts, int* __restrict__ offs, int n)
+{
+    __shared__ int part[FIC_QT_SCAN_THREADS];
+    const int t = threadIdx.x;
+    const int per = (n + FIC_QT_SCAN_THREADS - 1) / FIC_QT_SCAN_THREADS;
+    const int i0 = t * per, i1 = i0 + per < n ? i0 + per : n;
+    int s = 0;
+    for (int i = i0; i < i1; i++) s += counts[i];
+    part[t] = s;
+    __syncthreads();
+    for (int stride = 1; stride < FIC_QT_SCAN_THREADS; stride <<= 1) {     // inclusive Hillis-Steele scan of the slice sums
+        const int v = t >= stride ? part[t - stride] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int i = i0; i < i1; i++) {
+        offs[i] = run;
+        run += counts[i];
+    }
+    if (t == FIC_QT_SCAN_THREADS - 1) offs[n] = part[t];
+}
+
+__global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __restrict__ offs, int32_t* __restrict__ leaves)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L.Ntop) return;
+    int o = offs[t];
+    qt_walk(L, t, [&](int x, int y, int l) {
+        const int B = L.B_max >> l;
+        const int j = (y / B) * L.Rw[l] + x / B;
+        int32_t* r = leaves + 7 * (size_t)o;
+        r[0] = x;
+        r[1] = y;
+        r[2] = B;
+        r[3] = L.qrows[l][3 * j + 0];
+        r[4] = L.qrows[l][3 * j + 1];
+        r[5] = L.qrows[l][3 * j + 2];
+        r[6] = L.iso[l] ? L.iso[l][j] : 0;
+        o++;
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_decode_paint_leaves<B>: one decoder paint (FC:385-407) of the n leaves of side B in `lv`.  Each entry carries the leaf's
+// position, its global domain block (window_to_global of its level, resolved by the reader), its offset in `sqbuf` (the
+// prefix sum of B^2 over the leaves before it, so the squares lie in leaf order, pixel rows within a leaf) and its row.  One
+// thread per pixel row of a leaf; the exact integer sum of the squares goes to state->ssd[counter] like k_decode_paint's.
+// ---------------------------------------------------------------------------------------------
+template <int B>
+__global__ __launch_bounds__(256) void k_decode_paint_leaves(const uint8_t* __restrict__ scaled, uint8_t* __restrict__ image,
+                                                             const FicQtLeaf* __restrict__ lv, int n, FicDecodeState* __restrict__ state,
+                                                             uint32_t* __restrict__ sqbuf, int counter, FicGeom g)
+{
+    FicDecodeState* st = state;
+    if (st->done) return;                                  // uniform
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long sq = 0;
+    if (t < n * B) {
+        const FicQtLeaf e = lv[t / B];
+        const int ry = t % B;
+        uint8_t* prow = image + (size_t)(e.y + ry) * g.W + e.x;
+        uint32_t* srow = sqbuf + (size_t)e.sqoff + (size_t)ry * B;
+        uint32_t old[B / 4], neu[B / 4], sqv[B];
+        __builtin_memcpy(old, prow, B);
+        int value[B];
+        qt_row_values<B>(scaled, g, e.gi, e.iso, ry, __fdiv_rn((float)e.qa, 100.0f), (float)e.qb, value);
+#pragma unroll
+        for (int q = 0; q < B / 4; q++) neu[q] = 0u;
+#pragma unroll
+        for (int x = 0; x < B; x++) {
+            const int dd = (int)((old[x >> 2] >> (8 * (x & 3))) & 0xffu) - value[x];
+            neu[x >> 2] |= (uint32_t)value[x] << (8 * (x & 3));
+            sqv[x] = (uint32_t)(dd * dd);
+            sq += sqv[x];
+        }
+        __builtin_memcpy(prow, neu, B);
+#pragma unroll
+        for (int q = 0; q < B / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    __shared__ unsigned long long s_part[4];
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+        if (tot) atomicAdd(&st->ssd[counter], tot);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host-side launchers
+// ---------------------------------------------------------------------------------------------
+int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_t* qrows, const int32_t* iso, uint32_t* sse,
+                        const FicGeom& g, hipStream_t s)
+{
+    if (hipMemsetAsync(sse, 0, (size_t)g.Nr * sizeof(uint32_t), s) != hipSuccess) return -1;
+    auto k = g.B == 4 ? k_leaf_sse<4> : (g.B == 8 ? k_leaf_sse<8> : k_leaf_sse<16>);
+    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, gray, scaled, qrows, iso, sse, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
+                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
+                          hipStream_t s)
+{
+    FicQtLevels L{};
+    for (int l = 0; l < nl; l++) {
+        L.sse[l] = sse[l];
+        L.qrows[l] = qrows[l];
+        L.iso[l] = iso[l];
+        L.Rw[l] = Rw[l];
+    }
+    L.nl = nl;
+    L.B_max = B_max;
+    L.Rw_top = Rw_top;
+    L.Ntop = Ntop;
+    L.threshold = threshold;
+    const int nb = (Ntop + 255) / 256;
+    hipLaunchKernelGGL(k_qt_count, dim3(nb), dim3(256), 0, s, L, counts);
+    FIC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, Ntop);
+    FIC_LAUNCH_CHECK();
+    if (leaves) {
+        hipLaunchKernelGGL(k_qt_scatter, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
+        FIC_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int fic_launch_decode_paint_leaves(const uint8_t* scaled, uint8_t* image, const FicQtLeaf* lv, int n, FicDecodeState* state,
+                                   uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
+{
+    if (n <= 0) return 0;
+    auto k = g.B == 4 ? k_decode_paint_leaves<4> : (g.B == 8 ? k_decode_paint_leaves<8> : k_decode_paint_leaves<16>);
+    hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}

@@ -201,6 +201,43 @@ FIC_API int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int3
  * iterations_out [planes], may be NULL.  Every range block must have been encoded. */
 FIC_API int fic_ctx_decode_host(fic_ctx* ctx, uint8_t* gray_out, float* avg_error_out, int* iterations_out);
 
+/* ---- quadtree (variable block size) grey codec -------------------------------------------------- */
+/* An extension like n_iso = 8: the reference encodes with one block size (FC:14).  Levels B_max in {8, 16}, B_min in {4, 8},
+ * B_min < B_max; w and h multiples of B_max.  Every level B = B_max, B_max/2, ..., B_min is encoded exactly as
+ * fic_encode_gray_u8(gray, w, h, B, wK_B, n_iso) encodes it, with wK_B = Dw_B (full search; square images) when wK = 0, else
+ * wK_B = wK (which must be a valid window at every level).  The collage error of a range block is
+ * SSE = sum (orig - value)^2 of its QUANTISED row, value = clamp((int) fl(fl(((float) qa / 100f) * d) + (float) qb)) with d the
+ * winner's domain pixel (isometry applied) in the 2:1-scaled original: what the decoder paints.  Top-down from B_max a
+ * block is split into four iff B > B_min and (double) SSE > (double) threshold * B * B (threshold: mean squared error per
+ * pixel; +inf never splits, a negative value always splits down to B_min; NaN is refused).
+ *   leaves   int32 [capacity][7] {x, y, B, idx_local, qa, qb, iso}: top-level blocks in scanline order, inside a block depth
+ *            first TL, TR, BL, BR; iso = 0 when n_iso = 1.  *n_leaves = the count (also set on FIC_E_CAPACITY).
+ * The first version encodes every level in full: the cost is the sum of the fixed-B encodes. */
+FIC_API int fic_encode_gray_quadtree_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                        int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+FIC_API int fic_encode_gray_quadtree_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                          float threshold, int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+/* Quadtree stream, host only: big-endian int32 header {2, w, h, B_max, B_min, wK, n_iso, n_leaves}, then per leaf
+ * {B, idx_local, qa, qb} (+ iso when n_iso = 8); positions follow from the order.  The leaves must tile the image in the order
+ * above.  Returns the bytes written or a negative code.  Tag 2 is NEW: the reference's FractalCompression.decode reads any
+ * non-zero first int as isRGB (FC:547-553) and would misread this stream as a colour .run; fic_decode_gray_run and
+ * fic_decode_rgb_run do not accept it either. */
+FIC_API int64_t fic_write_run_quadtree(const int32_t* leaves, int n_leaves, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                       uint8_t* out, int64_t capacity);
+/* Decoder of a quadtree stream: the loop of decodeGreyScale (FC:356-421) -- grey 128 start, at most 50 iterations, each one
+ * the 2:1 scale of the current image and every leaf painted from its own level's domain block, the squared changes summed
+ * in Java's float order over the leaves in stream order (pixel rows within a leaf), stop when avgError < 1.  avg_error_io as
+ * in fic_decode_gray_run.  The stream is checked before any device work: FIC_E_ARGUMENT for a tag other than 2, sizes that
+ * do not tile the image exactly, a B outside the levels, an idx_local outside the level's window, an isometry outside
+ * 0..n_iso-1, and a length other than the header's (truncated or oversized).  With threshold = +inf the stream decodes bit
+ * for bit like the fixed-B_max .run (pixels, avgError, iterations). */
+FIC_API int fic_decode_quadtree_run(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity, int* w,
+                                    int* h, float* avg_error_io, int* iterations);
+/* Test hook: the per-level collage SSE arrays of the quadtree encode, levels B_max .. B_min concatenated, [N_r(B)] each in
+ * scanline order. */
+FIC_API int fic_debug_quadtree_sse(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,
+                                   uint32_t* sse, int64_t capacity);
+
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
  *                     group-Fourier form, for 8 isometries at B = 8; k_sweep_fast otherwise)
