@@ -120,6 +120,10 @@ def lib():
         "fic_write_run_quadtree": (C.c_int64, [i32p] + [C.c_int] * 7 + [u8p, C.c_int64]),
         "fic_decode_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
         "fic_debug_quadtree_sse": (C.c_int, [u8p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
+        "fic_encode_rgb_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_write_run_rgb_quadtree": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
+        "fic_decode_rgb_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_debug_rgb_quadtree_sse": (C.c_int, [i32p] + [C.c_int] * 6 + [C.POINTER(C.c_uint32), C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -435,4 +439,69 @@ def decode_quadtree_run(run, device=0, avg_error_in=0.0):
     it, wo, ho = C.c_int(), C.c_int(), C.c_int()
     check(lib().fic_decode_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_uint8), cap, C.byref(wo),
                                         C.byref(ho), C.byref(avg), C.byref(it)))
+    return out[:cap].reshape(h, w), np.float32(avg.value), it.value
+
+
+QT_RGB_LEAF_FIELDS = ("x", "y", "B", "idx_local", "q1", "q2", "q3", "q4")
+
+
+def _argb_image(argb, w, h):
+    a = np.ascontiguousarray(argb, np.int32).reshape(-1)
+    if a.size != w * h:
+        raise FicError(-3, "argb has the wrong number of pixels")
+    return a
+
+
+def encode_rgb_quadtree(argb, w, h, B_max, B_min, wK=0, threshold=float("inf"), device=0):
+    """Joint-RGB quadtree encode of the int32 ARGB pixels `argb` ([h*w] or [h, w]; fic_encode_rgb_quadtree_argb).  wK = 0:
+    full search at every level.  Returns the leaf table int32 [n_leaves, 8] with the columns QT_RGB_LEAF_FIELDS (q1..q4: the
+    level's encode_rgb qrows row), in stream order."""
+    a = _argb_image(argb, w, h)
+    cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
+    out = np.zeros((max(cap, 1), 8), np.int32)
+    n = C.c_int()
+    check(lib().fic_encode_rgb_quadtree_argb(ptr(a, C.c_int32), w, h, B_max, B_min, wK, float(threshold), device,
+                                             ptr(out, C.c_int32), out.shape[0], C.byref(n)))
+    return out[:n.value].copy()
+
+
+def debug_rgb_quadtree_sse(argb, w, h, B_max, B_min, wK=0, device=0):
+    """Per-level collage SSE of the colour quadtree encode: {B: uint32 [Rh, Rw]} for B = B_max .. B_min
+    (fic_debug_rgb_quadtree_sse)."""
+    a = _argb_image(argb, w, h)
+    levels = _qt_levels(B_max, B_min)
+    sizes = [(h // B) * (w // B) for B in levels]
+    out = np.zeros(max(sum(sizes), 1), np.uint32)
+    check(lib().fic_debug_rgb_quadtree_sse(ptr(a, C.c_int32), w, h, B_max, B_min, wK, device, ptr(out, C.c_uint32), out.size))
+    r, o = {}, 0
+    for B, n in zip(levels, sizes):
+        r[B] = out[o:o + n].reshape(h // B, w // B)
+        o += n
+    return r
+
+
+def write_run_rgb_quadtree(leaves, w, h, B_max, B_min, wK):
+    """Colour quadtree stream (tag 3): header {3, w, h, 0, B_max, B_min, wK, n_leaves}, then {B, idx_local, q1, q2, q3, q4} per
+    leaf, big-endian int32 (fic_write_run_rgb_quadtree).  `leaves`: int32 [n, 8] as encode_rgb_quadtree returns it."""
+    q = np.ascontiguousarray(leaves, np.int32).reshape(-1, 8)
+    out = np.zeros(32 + 24 * q.shape[0], np.uint8)
+    n = lib().fic_write_run_rgb_quadtree(ptr(q, C.c_int32), q.shape[0], w, h, B_max, B_min, wK, ptr(out, C.c_uint8), out.size)
+    check(int(n))
+    return out.tobytes()
+
+
+def decode_rgb_quadtree_run(run, device=0, avg_error_in=0.0):
+    """Decoder of a colour quadtree stream on the GPU (fic_decode_rgb_quadtree_run).  Returns (argb int32 [H, W], avgError
+    float32 after the call, iterations)."""
+    buf = np.frombuffer(bytes(run), np.uint8)
+    if buf.size < 32:
+        raise FicError(-3, "colour quadtree stream shorter than its header")
+    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
+    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
+    cap = max(w, 0) * max(h, 0)
+    out = np.zeros(max(cap, 1), np.int32)
+    avg = C.c_float(avg_error_in)
+    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
+    check(lib().fic_decode_rgb_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_int32), cap, C.byref(wo),
+                                            C.byref(ho), C.byref(avg), C.byref(it)))
     return out[:cap].reshape(h, w), np.float32(avg.value), it.value

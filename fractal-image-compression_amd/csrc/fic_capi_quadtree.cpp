@@ -1,6 +1,7 @@
-// fic_capi_quadtree.cpp -- C ABI, quadtree (variable block size) grey codec: encode every level with the one-shot machinery,
-// collage SSE + split + compaction on the device (fic_quadtree.hip), the tag-2 stream writer / reader, and the decoder of
-// leaves of mixed size.  Host-side orchestration only.  Semantics: DESIGN.md section 4.13.
+// fic_capi_quadtree.cpp -- C ABI, quadtree (variable block size) codec, grey and joint RGB: encode every level with the
+// one-shot machinery, collage SSE + split + compaction on the device (fic_quadtree.hip), the tag-2 (grey) and tag-3 (colour)
+// stream writers / readers, and the decoders of leaves of mixed size.  Host-side orchestration only.  Semantics: DESIGN.md
+// sections 4.13 (grey) and 4.14 (colour).
 #include "fic_internal.h"
 
 using namespace ficd;
@@ -8,7 +9,9 @@ using namespace ficd;
 namespace {
 
 constexpr int kQtMaxLevels = 3;   // 16 -> 8 -> 4
-constexpr int kQtHeaderInts = 8;  // {2, w, h, B_max, B_min, wK, n_iso, n_leaves}
+constexpr int kQtHeaderInts = 8;  // {2, w, h, B_max, B_min, wK, n_iso, n_leaves}; colour: {3, w, h, 0, B_max, B_min, wK, n_leaves}
+constexpr int kQtRgbLeafInts = 8; // colour leaf table row {x, y, B, idx_local, q1, q2, q3, q4}
+constexpr int kQtRgbRunInts = 6;  // colour stream row {B, idx_local, q1, q2, q3, q4}
 
 // The levels B_max, B_max / 2, ..., B_min and their geometries (wK = 0: full search at every level, wK_B = Dw_B).
 struct QtLevels {
@@ -179,6 +182,83 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     return rc;
 }
 
+// The colour twin of qt_encode behind fic_encode_rgb_quadtree_argb and its SSE hook: every level through the one-shot RGB
+// contexts (fic_encode_rgb_argb's cache), then the per-level SSE over the three channels, the split and the compaction.
+int qt_encode_rgb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold, int device, int32_t* leaves,
+                  int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity)
+{
+    if (!argb) return fail(FIC_E_ARGUMENT, "colour quadtree encode: null image");
+    if (threshold != threshold) return fail(FIC_E_ARGUMENT, "colour quadtree encode: threshold is NaN");
+    QtLevels L;
+    int rc = qt_levels(w, h, B_max, B_min, wK, 1, &L);
+    if (rc) return rc;
+    size_t sse_total = 0;
+    for (int l = 0; l < L.nl; l++) sse_total += (size_t)L.g[l].Nr;
+    if (sse_out && sse_capacity < (int64_t)sse_total)
+        return fail(FIC_E_CAPACITY, "colour quadtree SSE: need %zu values, have %lld", sse_total, (long long)sse_capacity);
+    rc = check_device(device);
+    if (rc) return rc;
+
+    fic_rgb_ctx* c[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    char* scratch = nullptr;
+    for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
+        const FicGeom& g = L.g[l];
+        c[l] = rgb_cache_take(device, w, h, g.B, g.wK);
+        if (!c[l]) c[l] = fic_rgb_ctx_create(device, w, h, g.B, g.wK, 1);
+        if (!c[l]) { rc = g_err_code ? g_err_code : FIC_E_HIP; break; }
+        rc = fic_rgb_ctx_set_argb_host(c[l], argb);
+        if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c[l], 0, nullptr);   // exactly the one-shot RGB encode of this level
+    }
+    const FicGeom& top = L.g[0];
+    const size_t max_leaves = (size_t)L.g[L.nl - 1].Nr;
+    size_t o_sse[kQtMaxLevels], off = 0;
+    for (int l = 0; l < L.nl; l++) { o_sse[l] = off; off += align256((size_t)L.g[l].Nr * 4); }
+    const size_t o_cnt = off, o_offs = o_cnt + align256((size_t)top.Nr * 4), o_leaves = o_offs + align256(((size_t)top.Nr + 1) * 4),
+                 total = o_leaves + align256(max_leaves * kQtRgbLeafInts * 4);
+    if (rc == FIC_OK) rc = dev_alloc(&scratch, total);
+    const uint32_t* sse[kQtMaxLevels];
+    const int32_t* qrows[kQtMaxLevels];
+    const int32_t* no_iso[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    int Rw[kQtMaxLevels];
+    for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
+        const int32_t *d_argb, *d_scaled;   // the context's input and its scaleImageRGB copy, made by the encode
+        rgb_ctx_views(c[l], &d_argb, &d_scaled, &qrows[l]);
+        sse[l] = (const uint32_t*)(scratch + o_sse[l]);
+        Rw[l] = L.g[l].Rw;
+        if (fic_launch_leaf_sse_rgb(d_argb, d_scaled, qrows[l], (uint32_t*)(scratch + o_sse[l]), L.g[l], nullptr))
+            rc = fail(FIC_E_HIP, "k_leaf_sse_rgb launch failed");
+    }
+    int* d_offs = (int*)(scratch + o_offs);
+    if (rc == FIC_OK && fic_launch_qt_compact(sse, qrows, no_iso, Rw, L.nl, top.B, top.Rw, top.Nr, threshold, (int*)(scratch + o_cnt),
+                                              d_offs, (int32_t*)(scratch + o_leaves), nullptr, 5))
+        rc = fail(FIC_E_HIP, "colour quadtree compaction launch failed");
+    int n = 0;
+    if (rc == FIC_OK) {
+        hipError_t e = hipMemcpy(&n, d_offs + top.Nr, sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "colour quadtree encode: %s", hipGetErrorString(e));
+    }
+    if (rc == FIC_OK && n_leaves) *n_leaves = n;
+    if (rc == FIC_OK && leaves) {
+        if (capacity < n) rc = fail(FIC_E_CAPACITY, "colour quadtree encode: %d leaves, room for %lld", n, (long long)capacity);
+        else {
+            hipError_t e = hipMemcpy(leaves, scratch + o_leaves, (size_t)n * kQtRgbLeafInts * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "colour quadtree encode: %s", hipGetErrorString(e));
+        }
+    }
+    for (int l = 0, o = 0; rc == FIC_OK && sse_out && l < L.nl; o += L.g[l].Nr, l++) {
+        hipError_t e = hipMemcpy(sse_out + o, scratch + o_sse[l], (size_t)L.g[l].Nr * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "colour quadtree SSE: %s", hipGetErrorString(e));
+    }
+    ErrKeep keep;
+    if (scratch) (void)hipFree(scratch);
+    for (int l = 0; l < L.nl; l++) {
+        if (!c[l]) continue;
+        if (rc == FIC_OK) rgb_cache_give(c[l]);
+        else fic_rgb_ctx_destroy(c[l]);
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -300,6 +380,127 @@ int fic_decode_quadtree_run(const uint8_t* run, int64_t len, int device, uint8_t
     if (rc == FIC_OK) {
         hipError_t e = hipMemcpy(gray_out, d_image, npix, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_decode_quadtree_run: %s", hipGetErrorString(e));
+    }
+    if (rc == FIC_OK && avg_error_io) *avg_error_io = avg;
+    arena_give(ar);
+    return rc;
+}
+
+int fic_encode_rgb_quadtree_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold, int device,
+                                 int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_argb: null argument");
+    return qt_encode_rgb(argb, w, h, B_max, B_min, wK, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_debug_rgb_quadtree_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int device, uint32_t* sse,
+                               int64_t capacity)
+{
+    if (!argb || !sse) return fail(FIC_E_ARGUMENT, "fic_debug_rgb_quadtree_sse: null argument");
+    return qt_encode_rgb(argb, w, h, B_max, B_min, wK, __builtin_inff(), device, nullptr, 0, nullptr, sse, capacity);
+}
+
+int64_t fic_write_run_rgb_quadtree(const int32_t* leaves, int n_leaves, int w, int h, int B_max, int B_min, int wK, uint8_t* out,
+                                   int64_t capacity)
+{
+    if (!leaves || !out || n_leaves < 0) return fail(FIC_E_ARGUMENT, "fic_write_run_rgb_quadtree: bad argument");
+    QtLevels L;
+    int rc = qt_levels(w, h, B_max, B_min, wK, 1, &L);
+    if (rc) return rc;
+    const int32_t* lv = leaves;
+    const bool tiles = qt_tile(L, n_leaves, [&](int i) { return lv[kQtRgbLeafInts * (size_t)i + 2]; }, [&](int i, int x, int y, int) {
+        return lv[kQtRgbLeafInts * (size_t)i + 0] == x && lv[kQtRgbLeafInts * (size_t)i + 1] == y;
+    });
+    if (!tiles) return fail(FIC_E_ARGUMENT, "fic_write_run_rgb_quadtree: the leaves do not tile the %dx%d image in quadtree order", w, h);
+    const int64_t need = 4 * (kQtHeaderInts + kQtRgbRunInts * (int64_t)n_leaves);
+    if (capacity < need)
+        return fail(FIC_E_CAPACITY, "fic_write_run_rgb_quadtree: need %lld bytes, have %lld", (long long)need, (long long)capacity);
+    const int32_t hdr[kQtHeaderInts] = {3, w, h, 0, B_max, B_min, wK, n_leaves};   // 0 where the fixed-B .run holds B (FC:234-238)
+    for (int i = 0; i < kQtHeaderInts; i++) put_be32(out + 4 * i, hdr[i]);
+    uint8_t* p = out + 4 * kQtHeaderInts;
+    for (int i = 0; i < n_leaves; i++)    // {B, idx_local, q1, q2, q3, q4}: positions follow from the order
+        for (int k = 2; k < kQtRgbLeafInts; k++, p += 4) put_be32(p, leaves[kQtRgbLeafInts * (size_t)i + k]);
+    return need;
+}
+
+int fic_decode_rgb_quadtree_run(const uint8_t* run, int64_t len, int device, int32_t* argb_out, int64_t capacity_pixels, int* w_out,
+                                int* h_out, float* avg_error_io, int* iterations)
+{
+    if (!run || len < 4 * kQtHeaderInts)
+        return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: stream shorter than the 32-byte header");
+    int32_t hd[kQtHeaderInts];
+    for (int i = 0; i < kQtHeaderInts; i++) hd[i] = get_be32(run + 4 * i);
+    if (hd[0] != 3 || hd[3] != 0)
+        return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: header starts {%d, .., .., %d}, a colour quadtree stream has {3, w, h, 0}",
+                    hd[0], hd[3]);
+    const int w = hd[1], h = hd[2], B_max = hd[4], B_min = hd[5], wK = hd[6], n = hd[7];
+    QtLevels L;
+    if (qt_levels(w, h, B_max, B_min, wK, 1, &L))
+        return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: %s", g_err.c_str());
+    if (n < 1 || n > L.g[L.nl - 1].Nr) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: %d leaves", n);
+    const int64_t need = 4 * (kQtHeaderInts + kQtRgbRunInts * (int64_t)n);
+    if (len != need)
+        return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: %lld bytes, %d leaves need exactly %lld", (long long)len, n,
+                    (long long)need);
+    const uint8_t* rows = run + 4 * kQtHeaderInts;
+    constexpr size_t row_bytes = 4 * kQtRgbRunInts;
+    std::vector<FicQtLeafRgb> lv[kQtMaxLevels];
+    int sqoff = 0;
+    const bool ok = qt_tile(L, n, [&](int i) { return get_be32(rows + row_bytes * (size_t)i); }, [&](int i, int x, int y, int l) {
+        const FicGeom& g = L.g[l];
+        const uint8_t* r = rows + row_bytes * (size_t)i;
+        const int idx = get_be32(r + 4);
+        if (idx < 0 || idx >= g.wK * g.wK) return false;
+        const int gi = host_window_to_global(g, (y / g.B) * g.Rw + x / g.B, idx);
+        if (gi < 0 || gi >= g.Nd) return false;
+        lv[l].push_back(FicQtLeafRgb{x, y, gi, sqoff, get_be32(r + 8), get_be32(r + 12), get_be32(r + 16), get_be32(r + 20)});
+        sqoff += g.n;
+        return true;
+    });
+    if (!ok)
+        return fail(FIC_E_ARGUMENT, "fic_decode_rgb_quadtree_run: the leaf sizes do not tile the %dx%d image with levels %d..%d, or a "
+                                    "leaf's domain index is out of range", w, h, B_max, B_min);
+    if (w_out) *w_out = w;
+    if (h_out) *h_out = h;
+    const size_t npix = (size_t)w * h;
+    if (!argb_out || capacity_pixels < (int64_t)npix)
+        return fail(FIC_E_CAPACITY, "fic_decode_rgb_quadtree_run: output needs %zu pixels", npix);
+    int rc = check_device(device);
+    if (rc) return rc;
+    const FicGeom& g0 = L.g[0];
+    size_t o_lv[kQtMaxLevels];
+    const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g0.Ws * g0.Hs * 4);
+    size_t off = o_image + align256(npix * 4);
+    for (int l = 0; l < L.nl; l++) { o_lv[l] = off; off += align256((lv[l].size() + 1) * sizeof(FicQtLeafRgb)); }
+    const size_t o_state = off, o_sq = o_state + align256(sizeof(FicDecodeState)), total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
+    Arena ar;
+    rc = arena_take(device, total, &ar);
+    if (rc) return rc;
+    for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
+        if (lv[l].empty()) continue;
+        hipError_t e = hipMemcpy(ar.base + o_lv[l], lv[l].data(), lv[l].size() * sizeof(FicQtLeafRgb), hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_decode_rgb_quadtree_run: %s", hipGetErrorString(e));
+    }
+    int32_t* d_scaled = (int32_t*)(ar.base + o_scaled);
+    int32_t* d_image = (int32_t*)(ar.base + o_image);
+    FicDecodeState* d_state = (FicDecodeState*)(ar.base + o_state);
+    uint32_t* d_sq = (uint32_t*)(ar.base + o_sq);
+    float avg = avg_error_io ? *avg_error_io : 0.0f;
+    // one iteration: scaleImageRGB of the current image (FC:459), paint the leaves level by level from that copy, loop control.
+    // decode_loop fills the image with grey bytes; the colour start is generateGrayImage's 0xff808080 (FC:1142-1148).
+    if (rc == FIC_OK)
+        rc = decode_loop(1, npix, (uint8_t*)d_image, d_state, &avg, &avg, iterations, nullptr, nullptr, [&](int counter) {
+            if (counter == 0 && hipMemsetD32Async((hipDeviceptr_t)d_image, (int)0xff808080u, npix, nullptr) != hipSuccess) return -1;
+            if (fic_launch_scale_rgb(d_image, d_scaled, g0, nullptr)) return -1;
+            for (int l = 0; l < L.nl; l++)
+                if (fic_launch_decode_paint_leaves_rgb(d_scaled, d_image, (const FicQtLeafRgb*)(ar.base + o_lv[l]), (int)lv[l].size(),
+                                                       d_state, d_sq, counter, L.g[l], nullptr))
+                    return -1;
+            return fic_launch_decode_step(d_state, d_sq, counter, (int)npix, 1, nullptr);
+        });
+    if (rc == FIC_OK) {
+        hipError_t e = hipMemcpy(argb_out, d_image, npix * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_decode_rgb_quadtree_run: %s", hipGetErrorString(e));
     }
     if (rc == FIC_OK && avg_error_io) *avg_error_io = avg;
     arena_give(ar);

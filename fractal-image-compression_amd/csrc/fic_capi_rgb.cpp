@@ -353,8 +353,9 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
     return FIC_OK;
 }
 
-namespace {
-fic_rgb_ctx* rgb_cache_take(int device, int w, int h, int B, int wK)
+}  // extern "C"
+
+fic_rgb_ctx* ficd::rgb_cache_take(int device, int w, int h, int B, int wK)
 {
     std::lock_guard<std::mutex> lk(g_rgb_mu);
     for (size_t i = g_rgb_cache.size(); i-- > 0;) {
@@ -367,7 +368,7 @@ fic_rgb_ctx* rgb_cache_take(int device, int w, int h, int B, int wK)
     }
     return nullptr;
 }
-void rgb_cache_give(fic_rgb_ctx* c)
+void ficd::rgb_cache_give(fic_rgb_ctx* c)
 {
     fic_rgb_ctx* evict = nullptr;
     {
@@ -380,7 +381,15 @@ void rgb_cache_give(fic_rgb_ctx* c)
     }
     if (evict) fic_rgb_ctx_destroy(evict);
 }
-}  // namespace
+
+void ficd::rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5)
+{
+    if (argb) *argb = c->argb;
+    if (scaled) *scaled = c->scaled;
+    if (qrows5) *qrows5 = c->qrows;
+}
+
+extern "C" {
 
 int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK, int device, int32_t* idx_local, float* a,
                         float* bR, float* bG, float* bB, int32_t* qrows5, int32_t* collage_argb)

@@ -129,6 +129,27 @@ __device__ __forceinline__ void iso_dot(const uint8_t* __restrict__ blk, int W, 
     }
 }
 
+// decodeRGB's paint of one pixel from a quantised row {idx, q1, q2, q3, q4} (FC:446-450, 482-488): a = (float) q1 / 1000000f,
+// bR = (float) q2 / 100000f, bG = (float) q3 / 100000f, bB = (float) q4 (an integer: the reference's own quirk), and per channel
+// value_c = clamp((int) fl(fl(a * d_c) + b_c)) of the packed ARGB domain pixel d.  Shared by k_decode_paint_rgb and the colour
+// quadtree (collage SSE and leaf paint), so the encoder's error and the decoder's paint cannot drift apart.
+struct FicRgbCoef {
+    float a, bR, bG, bB;
+};
+__device__ __forceinline__ FicRgbCoef rgb_row_coef(int q1, int q2, int q3, int q4)
+{
+    return FicRgbCoef{__fdiv_rn((float)q1, 1000000.0f), __fdiv_rn((float)q2, 100000.0f), __fdiv_rn((float)q3, 100000.0f), (float)q4};
+}
+__device__ __forceinline__ void rgb_paint_px(const FicRgbCoef& c, int32_t d, int& vR, int& vG, int& vB)
+{
+    vR = java_f2i(__fadd_rn(__fmul_rn(c.a, (float)((d >> 16) & 0xff)), c.bR));
+    vG = java_f2i(__fadd_rn(__fmul_rn(c.a, (float)((d >> 8) & 0xff)), c.bG));
+    vB = java_f2i(__fadd_rn(__fmul_rn(c.a, (float)(d & 0xff)), c.bB));
+    vR = vR < 0 ? 0 : (vR > 255 ? 255 : vR);
+    vG = vG < 0 ? 0 : (vG > 255 ? 255 : vG);
+    vB = vB < 0 ? 0 : (vB > 255 ? 255 : vB);
+}
+
 // getDomainBlockIndex FC:516-545
 __device__ __forceinline__ int domain_block_index(int xr, int yr, int Rw, int Rh, int Dw)
 {

@@ -170,6 +170,7 @@ int fic_launch_sweep_q(const FicBuffers& b, const void* poolQ, const void* dflat
                        const FicOutputs* fin_out = nullptr, unsigned int* fin_count = nullptr, int r_begin = 0, int r_count = 0);
 int fic_launch_decode_iteration_rgb(int32_t* scaled, int32_t* image, const int32_t* qrows5, FicDecodeState* state,
                                     uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
+int fic_launch_scale_rgb(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s);   // one image
 
 // decoder (FC:356-421)
 // maps: fic_float_sum_map_words(count) u32 of scratch; out2[0] = the sum, out2[1] = segments that took the sequential-order path
@@ -191,10 +192,24 @@ struct FicQtLeaf {
 int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_t* qrows, const int32_t* iso, uint32_t* sse,
                         const FicGeom& g, hipStream_t s);
 // split + compaction over nl levels (B_max >> l): counts int [Ntop], offs int [Ntop + 1] (offs[Ntop] = leaves), leaves int32
-// [leaves][7] {x, y, B, idx_local, qa, qb, iso} (NULL: count only); room for the largest possible count is the caller's
+// (NULL: count only); room for the largest possible count is the caller's.  qw = ints per quantised row:
+//   3 (grey qrows, iso NULL or [N_r])  -> rows [leaves][7] {x, y, B, idx_local, qa, qb, iso}
+//   5 (colour qrows5, iso ignored)     -> rows [leaves][8] {x, y, B, idx_local, q1, q2, q3, q4}
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s);
+                          hipStream_t s, int qw = 3);
 // one paint of the n leaves of side g.B (one plane; g = that level's geometry)
 int fic_launch_decode_paint_leaves(const uint8_t* scaled, uint8_t* image, const FicQtLeaf* lv, int n, FicDecodeState* state,
                                    uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
+
+// colour quadtree (fic_quadtree.hip).  A leaf of the decoder's per-level lists, as FicQtLeaf with the colour row q1..q4.
+struct FicQtLeafRgb {
+    int32_t x, y, gi, sqoff, q1, q2, q3, q4;
+};
+// sse u32 [g.Nr]: collage SSE (three channels) of every range block of one level from its rows qrows5 [N_r][5]; argb the
+// original [H][W], scaled its scaleImageRGB [Hs][Ws]
+int fic_launch_leaf_sse_rgb(const int32_t* argb, const int32_t* scaled, const int32_t* qrows5, uint32_t* sse, const FicGeom& g,
+                            hipStream_t s);
+// one decodeRGB paint of the n leaves of side g.B (g = that level's geometry)
+int fic_launch_decode_paint_leaves_rgb(const int32_t* scaled, int32_t* image, const FicQtLeafRgb* lv, int n, FicDecodeState* state,
+                                       uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);

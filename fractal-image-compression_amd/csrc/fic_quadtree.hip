@@ -1,12 +1,15 @@
-// fic_quadtree.hip -- quadtree (variable block size) grey codec on the device: collage error per range block, the split
-// decision + leaf compaction, and the decoder's paint of leaves of mixed size.  An extension like n_iso = 8: the
-// reference encodes with one block size (FC:14).  gfx950 (MI355X / CDNA4) only, wave64; -ffp-contract=off like every
-// other translation unit (the paint arithmetic is k_decode_paint's, one rounding per operation).  DESIGN.md section 4.13.
+// fic_quadtree.hip -- quadtree (variable block size) codec on the device, grey and joint RGB: collage error per range
+// block, the split decision + leaf compaction, and the decoder's paint of leaves of mixed size.  An extension like
+// n_iso = 8: the reference encodes with one block size (FC:14).  gfx950 (MI355X / CDNA4) only, wave64; -ffp-contract=off
+// like every other translation unit (the paint arithmetic is k_decode_paint's / k_decode_paint_rgb's, one rounding per
+// operation).  DESIGN.md sections 4.13 (grey) and 4.14 (colour).
 //
 //   k_leaf_sse<B>            SSE of the quantised row of every range block of one level against the original image
+//   k_leaf_sse_rgb<B>        the same for joint-RGB rows, summed over the three channels
 //   k_qt_count / k_qt_scan / k_qt_scatter
 //                            top-down split of every top-level (B_max) block, leaf count, exclusive scan, ordered scatter
 //   k_decode_paint_leaves<B> one decoder paint of the leaves of one level (three launches per iteration, one per level)
+//   k_decode_paint_leaves_rgb<B>  the same for decodeRGB
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -77,11 +80,12 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const uint8_t* __restrict__ gr
 // (double) sse_l > (double) threshold * B * B.  Leaves are visited depth first, children TL, TR, BL, BR, top-level blocks in
 // scanline order.  One thread per top-level block walks its subtree (at most 1 + 4 + 16 nodes) with a small explicit stack:
 // k_qt_count counts the leaves, k_qt_scan (one workgroup) turns the counts into offsets, k_qt_scatter walks again and writes
-// the rows {x, y, B, idx_local, qa, qb, iso} at its offset.
+// the rows at its offset: {x, y, B} and the level's quantised row, {idx_local, qa, qb, iso} (grey) or {idx_local, q1, q2, q3,
+// q4} (colour).
 // ---------------------------------------------------------------------------------------------
 struct FicQtLevels {
     const uint32_t* sse[3];
-    const int32_t* qrows[3];
+    const int32_t* qrows[3];     // QW ints per range block (k_qt_scatter)
     const int32_t* iso[3];       // NULL: n_iso = 1 (iso 0)
     int Rw[3];
     int nl;                      // levels
@@ -159,22 +163,24 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
     if (t == FIC_QT_SCAN_THREADS - 1) offs[n] = part[t];
 }
 
+// QW ints per quantised row, RW ints per leaf row: <3, 7> grey (the iso column follows the row), <5, 8> colour (no isometries)
+template <int QW, int RW>
 __global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __restrict__ offs, int32_t* __restrict__ leaves)
 {
+    static_assert(RW == 3 + QW || RW == 4 + QW, "leaf row = {x, y, B} + quantised row [+ iso]");
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= L.Ntop) return;
     int o = offs[t];
     qt_walk(L, t, [&](int x, int y, int l) {
         const int B = L.B_max >> l;
         const int j = (y / B) * L.Rw[l] + x / B;
-        int32_t* r = leaves + 7 * (size_t)o;
+        int32_t* r = leaves + RW * (size_t)o;
         r[0] = x;
         r[1] = y;
         r[2] = B;
-        r[3] = L.qrows[l][3 * j + 0];
-        r[4] = L.qrows[l][3 * j + 1];
-        r[5] = L.qrows[l][3 * j + 2];
-        r[6] = L.iso[l] ? L.iso[l][j] : 0;
+#pragma unroll
+        for (int k = 0; k < QW; k++) r[3 + k] = L.qrows[l][QW * j + k];
+        if constexpr (RW == 4 + QW) r[3 + QW] = L.iso[l] ? L.iso[l][j] : 0;
         o++;
     });
 }
@@ -228,6 +234,93 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const uint8_t* __re
 }
 
 // ---------------------------------------------------------------------------------------------
+// Joint RGB.  The paint arithmetic of k_decode_paint_rgb (rgb_row_coef / rgb_paint_px, fic_devfn.h) on the
+// packed ARGB pixels; d is the domain pixel in the scaleImageRGB copy (FC:901-962), origin (c * B/4, r * B/4).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rgb_sq(int32_t cur, int vR, int vG, int vB)
+{
+    const int dR = ((cur >> 16) & 0xff) - vR, dG = ((cur >> 8) & 0xff) - vG, dB = (cur & 0xff) - vB;
+    return (uint32_t)(dR * dR + dG * dG + dB * dB);
+}
+
+// k_leaf_sse_rgb<B>: sse[j] = sum over the block's pixels and the channels R, G, B of (orig - value)^2, exact (at most
+// 256 * 3 * 255^2 < 2^32).  Work split and atomics as k_leaf_sse.
+template <int B>
+__global__ __launch_bounds__(256) void k_leaf_sse_rgb(const int32_t* __restrict__ argb, const int32_t* __restrict__ scaled,
+                                                      const int32_t* __restrict__ qrows5, uint32_t* __restrict__ sse, FicGeom g)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= g.Nr * B) return;
+    const int bx = t % g.Rw, row = t / g.Rw;
+    const int ry = row % B, by = row / B;
+    const int j = by * g.Rw + bx;
+    const int32_t* q = qrows5 + 5 * (size_t)j;
+    const int wloc = q[0];
+    const bool ok = wloc >= 0 && wloc < g.wK * g.wK;
+    const int gi = ok ? window_to_global(g, j, wloc) : -1;
+    if (gi < 0 || gi >= g.Nd) { atomicOr(&sse[j], 0xFFFFFFFFu); return; }   // never for an encoder's own rows: always split
+    const FicRgbCoef cf = rgb_row_coef(q[1], q[2], q[3], q[4]);
+    const int c = gi % g.Dw, r = gi / g.Dw;
+    const int32_t* drow = scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
+    const int32_t* prow = argb + (size_t)row * g.W + bx * B;
+    uint32_t s = 0;
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        int vR, vG, vB;
+        rgb_paint_px(cf, drow[x], vR, vG, vB);
+        s += rgb_sq(prow[x], vR, vG, vB);
+    }
+    if (s) atomicAdd(&sse[j], s);
+}
+
+// k_decode_paint_leaves_rgb<B>: one decodeRGB paint (FC:458-499) of the n leaves of side B in `lv`, entries as in
+// k_decode_paint_leaves.  One thread per pixel row of a leaf; sqbuf gets dR^2 + dG^2 + dB^2 per pixel (FC:493) at the leaf's
+// offset, the exact integer sum goes to state->ssd[counter].
+template <int B>
+__global__ __launch_bounds__(256) void k_decode_paint_leaves_rgb(const int32_t* __restrict__ scaled, int32_t* __restrict__ image,
+                                                                 const FicQtLeafRgb* __restrict__ lv, int n,
+                                                                 FicDecodeState* __restrict__ state, uint32_t* __restrict__ sqbuf,
+                                                                 int counter, FicGeom g)
+{
+    FicDecodeState* st = state;
+    if (st->done) return;                                  // uniform
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long sq = 0;
+    if (t < n * B) {
+        const FicQtLeafRgb e = lv[t / B];
+        const int ry = t % B;
+        int32_t* prow = image + (size_t)(e.y + ry) * g.W + e.x;
+        uint32_t* srow = sqbuf + (size_t)e.sqoff + (size_t)ry * B;
+        const int c = e.gi % g.Dw, r = e.gi / g.Dw;
+        const int32_t* drow = scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
+        const FicRgbCoef cf = rgb_row_coef(e.q1, e.q2, e.q3, e.q4);
+        int32_t cur[B], dom[B];
+        uint32_t sqv[B];
+        __builtin_memcpy(cur, prow, 4 * B);
+        __builtin_memcpy(dom, drow, 4 * B);
+#pragma unroll
+        for (int x = 0; x < B; x++) {
+            int vR, vG, vB;
+            rgb_paint_px(cf, dom[x], vR, vG, vB);
+            sqv[x] = rgb_sq(cur[x], vR, vG, vB);
+            sq += sqv[x];
+            cur[x] = (int32_t)(0xff000000u | ((uint32_t)vR << 16) | ((uint32_t)vG << 8) | (uint32_t)vB);
+        }
+        __builtin_memcpy(prow, cur, 4 * B);
+        __builtin_memcpy(srow, sqv, 4 * B);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    __shared__ unsigned long long s_part[4];
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+        if (tot) atomicAdd(&st->ssd[counter], tot);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
 int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_t* qrows, const int32_t* iso, uint32_t* sse,
@@ -242,8 +335,9 @@ int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_
 
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s)
+                          hipStream_t s, int qw)
 {
+    if (qw != 3 && qw != 5) return (int)hipErrorInvalidValue;
     FicQtLevels L{};
     for (int l = 0; l < nl; l++) {
         L.sse[l] = sse[l];
@@ -262,7 +356,8 @@ int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrow
     hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, Ntop);
     FIC_LAUNCH_CHECK();
     if (leaves) {
-        hipLaunchKernelGGL(k_qt_scatter, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
+        auto k = qw == 3 ? k_qt_scatter<3, 7> : k_qt_scatter<5, 8>;
+        hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
         FIC_LAUNCH_CHECK();
     }
     return 0;
@@ -273,6 +368,26 @@ int fic_launch_decode_paint_leaves(const uint8_t* scaled, uint8_t* image, const 
 {
     if (n <= 0) return 0;
     auto k = g.B == 4 ? k_decode_paint_leaves<4> : (g.B == 8 ? k_decode_paint_leaves<8> : k_decode_paint_leaves<16>);
+    hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_leaf_sse_rgb(const int32_t* argb, const int32_t* scaled, const int32_t* qrows5, uint32_t* sse, const FicGeom& g,
+                            hipStream_t s)
+{
+    if (hipMemsetAsync(sse, 0, (size_t)g.Nr * sizeof(uint32_t), s) != hipSuccess) return -1;
+    auto k = g.B == 4 ? k_leaf_sse_rgb<4> : (g.B == 8 ? k_leaf_sse_rgb<8> : k_leaf_sse_rgb<16>);
+    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, argb, scaled, qrows5, sse, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_decode_paint_leaves_rgb(const int32_t* scaled, int32_t* image, const FicQtLeafRgb* lv, int n, FicDecodeState* state,
+                                       uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
+{
+    if (n <= 0) return 0;
+    auto k = g.B == 4 ? k_decode_paint_leaves_rgb<4> : (g.B == 8 ? k_decode_paint_leaves_rgb<8> : k_decode_paint_leaves_rgb<16>);
     hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
     FIC_LAUNCH_CHECK();
     return 0;

@@ -293,10 +293,7 @@ __global__ __launch_bounds__(256) void k_decode_paint_rgb(const int32_t* __restr
         int j = (y / g.B) * g.Rw + (x / g.B);
         int rx = x % g.B, ry = y % g.B;
         int wloc = qrows5[5 * j + 0];
-        float a = __fdiv_rn((float)qrows5[5 * j + 1], 1000000.0f);
-        float bR = __fdiv_rn((float)qrows5[5 * j + 2], 100000.0f);
-        float bG = __fdiv_rn((float)qrows5[5 * j + 3], 100000.0f);
-        float bB = (float)qrows5[5 * j + 4];
+        const FicRgbCoef cf = rgb_row_coef(qrows5[5 * j + 1], qrows5[5 * j + 2], qrows5[5 * j + 3], qrows5[5 * j + 4]);
         bool ok = wloc >= 0 && wloc < g.wK * g.wK;
         int gi = ok ? window_to_global(g, j, wloc) : 0;
         if (!ok || gi < 0 || gi >= g.Nd) {
@@ -304,12 +301,8 @@ __global__ __launch_bounds__(256) void k_decode_paint_rgb(const int32_t* __restr
         } else {
             int c = gi % g.Dw, r = gi / g.Dw;
             int32_t d = scaled[(size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand + rx];
-            int vR = java_f2i(__fadd_rn(__fmul_rn(a, (float)ch_r(d)), bR));
-            int vG = java_f2i(__fadd_rn(__fmul_rn(a, (float)ch_g(d)), bG));
-            int vB = java_f2i(__fadd_rn(__fmul_rn(a, (float)ch_b(d)), bB));
-            vR = vR < 0 ? 0 : (vR > 255 ? 255 : vR);
-            vG = vG < 0 ? 0 : (vG > 255 ? 255 : vG);
-            vB = vB < 0 ? 0 : (vB > 255 ? 255 : vB);
+            int vR, vG, vB;
+            rgb_paint_px(cf, d, vR, vG, vB);
             size_t p = (size_t)y * g.W + x;
             int32_t cur = image[p];
             int dR = ch_r(cur) - vR, dG = ch_g(cur) - vG, dB = ch_b(cur) - vB;
@@ -388,6 +381,14 @@ int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int3
                            collage, g);
         FIC_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+// scaleImageRGB (FC:901-962) of one image
+int fic_launch_scale_rgb(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scale_rgb, dim3((g.Ws + 255) / 256, g.Hs), dim3(256), 0, s, argb, scaled, g);
+    FIC_LAUNCH_CHECK();
     return 0;
 }
 

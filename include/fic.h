@@ -238,6 +238,42 @@ FIC_API int fic_decode_quadtree_run(const uint8_t* run, int64_t len, int device,
 FIC_API int fic_debug_quadtree_sse(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,
                                    uint32_t* sse, int64_t capacity);
 
+/* ---- quadtree (variable block size) joint-RGB codec ---------------------------------------------- */
+/* The colour twin of the grey quadtree codec above, built on the joint-RGB path (encodeRGB / decodeRGB, FC:171-219,
+ * 430-508).  Levels, geometry, wK and the split rule as for the grey codec; no isometries (the reference's colour path has
+ * none).  Every level B is encoded exactly as fic_encode_rgb_argb(argb, w, h, B, wK_B) encodes it (the same cached
+ * working sets).  The collage error of a range block is that of its QUANTISED row {idx, q1, q2, q3, q4}, what decodeRGB
+ * paints: a = (float) q1 / 1e6f, bR = (float) q2 / 1e5f, bG = (float) q3 / 1e5f, bB = (float) q4 (sic), per channel
+ * value_c = clamp((int) fl(fl(a * d_c) + b_c)) with d the winner's domain pixel in scaleImageRGB of the original, and
+ * SSE = sum over the pixels and R, G, B of (orig_c - value_c)^2.  Split iff B > B_min and (double) SSE > (double) threshold * B * B:
+ * threshold is in the unit of decodeRGB's avgError, the squared error per pixel summed over the three channels.
+ *   argb     int32 [h][w] packed ARGB (RasterImage.argb)
+ *   leaves   int32 [capacity][8] {x, y, B, idx_local, q1, q2, q3, q4} in the grey codec's order; q1..q4 are the level's
+ *            qrows5 row.  *n_leaves = the count (also set on FIC_E_CAPACITY). */
+FIC_API int fic_encode_rgb_quadtree_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold,
+                                         int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+/* Colour quadtree stream, host only: big-endian int32 header {3, w, h, 0, B_max, B_min, wK, n_leaves}, then per leaf
+ * {B, idx_local, q1, q2, q3, q4}.  The leaves must tile the image in quadtree order.  Returns the bytes written or a negative
+ * code.  The 0 sits where a fixed-B .run holds its block size (FC:234-238): Java's decodeRGB divides by it, fic_decode_rgb_run
+ * refuses it with FIC_E_GEOMETRY, fic_decode_gray_run refuses the non-zero tag with FIC_E_NOT_GREY and fic_decode_quadtree_run
+ * refuses any tag but 2, so no existing reader misreads the stream. */
+FIC_API int64_t fic_write_run_rgb_quadtree(const int32_t* leaves, int n_leaves, int w, int h, int B_max, int B_min, int wK,
+                                           uint8_t* out, int64_t capacity);
+/* Decoder of a colour quadtree stream: the loop of decodeRGB (FC:430-508) -- generateGrayImage start (0xff808080), at most 50
+ * iterations, each one scaleImageRGB of the current image and every leaf painted from its own level's domain block, the
+ * per-pixel dR^2 + dG^2 + dB^2 summed in Java's float order over the leaves in stream order (pixel rows within a leaf), stop
+ * when avgError < 1.  argb_out int32 [capacity_pixels >= w*h]; avg_error_io as in fic_decode_rgb_run.  The stream is checked
+ * before any device work: FIC_E_ARGUMENT for a tag other than 3 or a non-zero 4th int, bad levels or geometry, sizes that do
+ * not tile the image, an idx_local outside its level's window, n_leaves outside 1 .. the B_min block count, and a length
+ * other than the header's.  With threshold = +inf the stream decodes bit for bit like the fixed-B_max .run that
+ * fic_write_run_rgb writes from the same codebook (pixels, avgError, iterations). */
+FIC_API int fic_decode_rgb_quadtree_run(const uint8_t* run, int64_t len, int device, int32_t* argb_out, int64_t capacity_pixels,
+                                        int* w, int* h, float* avg_error_io, int* iterations);
+/* Test hook: the per-level collage SSE arrays of the colour quadtree encode, levels B_max .. B_min concatenated, [N_r(B)]
+ * each in scanline order. */
+FIC_API int fic_debug_rgb_quadtree_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int device, uint32_t* sse,
+                                       int64_t capacity);
+
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
  *                     group-Fourier form, for 8 isometries at B = 8; k_sweep_fast otherwise)
