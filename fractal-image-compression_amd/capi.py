@@ -115,6 +115,8 @@ def lib():
         "fic_ctx_debug_pool_host": (C.c_int, [vp, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p]),
         "fic_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "fic_rgb_ctx_last_kernel": (C.c_int, [vp, C.c_char_p, C.c_int]),
+        "fic_rgb_ctx_sweep_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
         "fic_encode_gray_quadtree_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_encode_gray_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_write_run_quadtree": (C.c_int64, [i32p] + [C.c_int] * 7 + [u8p, C.c_int64]),
@@ -319,6 +321,18 @@ class RgbEncoder:
 
     def last_sweep(self):
         return check(lib().fic_rgb_ctx_last_sweep(self._h))
+
+    def last_kernel(self):
+        """Name of the sweep kernel the last encode launched, as rocprofv3 prints it (without the argument list)."""
+        buf = C.create_string_buffer(96)
+        check(lib().fic_rgb_ctx_last_kernel(self._h, buf, 96))
+        return buf.value.decode()
+
+    def sweep_stats(self, reset=True):
+        """Counters of the matrix-core sweep (after set_option("sweep_stats", 1)), as Encoder.sweep_stats."""
+        v = (C.c_uint64 * 8)()
+        check(lib().fic_rgb_ctx_sweep_stats(self._h, v, 1 if reset else 0))
+        return dict(zip(["tiles", "flagged_tiles", "exact_pairs", "waves", "wave_cycles", "wave_ticks", "waves_sampled"], [int(x) for x in v]))
 
     Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "amax")
 

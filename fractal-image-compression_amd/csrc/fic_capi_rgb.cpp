@@ -43,7 +43,7 @@ void rgb_free_all(fic_rgb_ctx* c)
     (void)hipSetDevice(c->device);
     void* ptrs[] = {c->argb_own, c->scaled, c->pool_sum, c->pool_cf, c->pool_st, c->rng_t, c->rng_st, c->key, c->idx_local,
                     c->idx_global, c->qrows, c->collage, c->a, c->bR, c->bG, c->bB, c->dec_image, c->dec_scaled, c->dec_state, c->dec_sq,
-                    c->q.poolQ, c->q.dflat, c->q.rngQ, c->q.qst, c->q.rngE, c->q.theta_g, c->q.amax};
+                    c->q.poolQ, c->q.dflat, c->q.rngQ, c->q.qst, c->q.rngE, c->q.theta_g, c->q.amax, c->q.stats};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -99,6 +99,7 @@ int rgb_q_setup(fic_rgb_ctx* c)
     const FicGeom& g = c->g;
     FicRgbQ& q = c->q;
     if (q.poolQ) return FIC_OK;
+    unsigned long long* const stats = q.stats;           // option "sweep_stats": set before the first matrix-core encode too
     const int unroll = fic_q_unroll(g.B, 1), CT = fic_q_ct(g.B);
     const size_t NK = (size_t)g.n / 16;
     q.ndtiles = (g.Nd + 31) / 32;
@@ -119,6 +120,7 @@ int rgb_q_setup(fic_rgb_ctx* c)
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
         q = FicRgbQ();
+        q.stats = stats;
     }
     return rc;
 }
@@ -248,6 +250,19 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         c->g.q_eshift = value;
         return FIC_OK;
     }
+    if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
+        HIP_TRY(hipSetDevice(c->device));
+        if (value && !c->q.stats) {
+            HIP_TRY(hipMalloc((void**)&c->q.stats, 8 * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(c->q.stats, 0, 8 * sizeof(unsigned long long)));
+            HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
+        } else if (!value && c->q.stats) {
+            HIP_TRY(hipStreamSynchronize(c->last_stream));
+            (void)hipFree(c->q.stats);
+            c->q.stats = nullptr;
+        }
+        return FIC_OK;
+    }
     return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: unknown option '%s'", name);
 }
 
@@ -284,6 +299,39 @@ int fic_rgb_ctx_last_sweep(fic_rgb_ctx* c)
 {
     if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_last_sweep: null context");
     return c->last_sweep;
+}
+
+int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* c, uint64_t* out8, int reset)
+{
+    if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_stats: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->q.stats) return fail(FIC_E_STATE, "fic_rgb_ctx_sweep_stats: set the option \"sweep_stats\" first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out8, c->q.stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reset) {
+        HIP_TRY(hipMemset(c->q.stats, 0, 8 * sizeof(uint64_t)));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return FIC_OK;
+}
+
+int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
+{
+    if (!c || !out || capacity < 1) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_last_kernel: bad argument");
+    const FicGeom& g = c->g;
+    const int NK = g.n / 16;
+    char buf[96];
+    if (c->last_sweep == 2) {
+        const int kind = fic_q_multi_kind(c->q.nchunks, c->q.tiles_per_chunk);      // what fic_launch_rgbq instantiates
+        if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, 3>", NK);
+        else snprintf(buf, sizeof(buf), "k_sweep_q<%d, 3, %s>", NK, kind ? "true" : "false");
+    } else if (c->last_sweep == 1) {
+        if (g.full && g.B <= 8) snprintf(buf, sizeof(buf), "k_sweep_rgb_fast<%d>", g.n);
+        else snprintf(buf, sizeof(buf), "k_sweep_rgb");
+    } else snprintf(buf, sizeof(buf), "(none)");
+    snprintf(out, (size_t)capacity, "%s", buf);
+    return FIC_OK;
 }
 
 int fic_rgb_ctx_sync(fic_rgb_ctx* c)

@@ -115,12 +115,14 @@ struct FicRgbBuffers {
 struct FicRgbQ {
     void *poolQ = nullptr, *dflat = nullptr, *rngQ = nullptr, *qst = nullptr, *rngE = nullptr, *theta_g = nullptr, *amax = nullptr;
     int ndtiles = 0, ndtiles_alloc = 0, nct_alloc = 0, tiles_per_chunk = 0, nchunks = 0;
+    unsigned long long* stats = nullptr;     // "sweep_stats" = 1: device counters of k_sweep_q<NK, 3> (fic_rgb_ctx_sweep_stats)
 };
 int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int32_t* collage, const FicGeom& g,
                           hipStream_t s, const FicRgbQ* q = nullptr);
 int fic_launch_rgbq(const uint16_t* pool_sum, const FicRgbDomStat* pool_st, const int16_t* rng_t, const FicRgbRngStat* rng_st,
                     unsigned long long* key, void* poolQ, void* dflat, void* rngQ, void* qst, void* rngE, void* theta_g, void* amax,
-                    const FicGeom& g, int ndtiles, int ndtiles_alloc, int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s);
+                    const FicGeom& g, int ndtiles, int ndtiles_alloc, int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s,
+                    unsigned long long* stats = nullptr);
 
 // opt-in matrix-core sweeps ("sweep" = 3)
 int fic_mfma8_group(int B);          // range blocks per workgroup of the 8-isometry kernel

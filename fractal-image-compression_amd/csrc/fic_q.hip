@@ -1666,7 +1666,8 @@ __global__ __launch_bounds__(256) void k_range_qrgb(const int16_t* __restrict__ 
 // prep + sweep of one RGB image (planes = 1 geometry); q buffers as in QArgs, sized by the caller (fic_capi_rgb.cpp)
 int fic_launch_rgbq(const uint16_t* pool_sum, const FicRgbDomStat* pool_st, const int16_t* rng_t, const FicRgbRngStat* rng_st,
                     unsigned long long* key, void* poolQ, void* dflat, void* rngQ, void* qst, void* rngE, void* theta_g, void* amax,
-                    const FicGeom& g, int ndtiles, int ndtiles_alloc, int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s)
+                    const FicGeom& g, int ndtiles, int ndtiles_alloc, int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s,
+                    unsigned long long* stats)
 {
     if (hipMemsetAsync(amax, 0, sizeof(uint32_t), s) != hipSuccess) return (int)hipErrorUnknown;
     hipLaunchKernelGGL(k_pool_qrgb, dim3(ndtiles_alloc), dim3(256), 0, s, pool_sum, pool_st, (v4i*)poolQ, (uint32_t*)dflat,
@@ -1678,7 +1679,7 @@ int fic_launch_rgbq(const uint16_t* pool_sum, const FicRgbDomStat* pool_st, cons
                        (uint32_t*)theta_g, (v4i*)rngQ, (const uint32_t*)amax, g, nct_alloc);
     FIC_LAUNCH_CHECK();
     QArgs A;
-    A.stats = nullptr;
+    A.stats = stats;
     A.dbg_noflag = 0;
     A.fin_count = nullptr; memset(&A.out, 0, sizeof(A.out)); A.geom = g; A.gray = nullptr; A.pool_var = nullptr; A.r_begin = 0; A.r_end = 0;
     A.poolQ = (const v4i*)poolQ; A.dflat = (const uint32_t*)dflat; A.pool_pix = nullptr; A.pool_st = nullptr; A.pool_s64 = nullptr;

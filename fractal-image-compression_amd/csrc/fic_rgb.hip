@@ -345,7 +345,7 @@ int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int3
         for (size_t p = 0; p < P; p++)
             if (fic_launch_rgbq(b.pool_sum + p * g.Nd * g.n, b.pool_st + p * g.Nd, b.rng_t + p * g.Nr * g.n, b.rng_st + p * g.Nr,
                                 b.key + p * g.Nr, q->poolQ, q->dflat, q->rngQ, q->qst, q->rngE, q->theta_g, q->amax, g1, q->ndtiles,
-                                q->ndtiles_alloc, q->nct_alloc, q->tiles_per_chunk, q->nchunks, s))
+                                q->ndtiles_alloc, q->nct_alloc, q->tiles_per_chunk, q->nchunks, s, q->stats))
                 return (int)hipErrorUnknown;
     } else if (g.full && g.B <= 8 && b.pool_cf) {
         // full search: lane = range block, wave-uniform domain blocks, pool chunks across workgroups

@@ -168,6 +168,13 @@ FIC_API int fic_rgb_ctx_sync(fic_rgb_ctx* ctx);
  * "chunks": pool chunks of the matrix-core sweep (0 = automatic; results do not depend on it). */
 FIC_API int fic_rgb_ctx_set_option(fic_rgb_ctx* ctx, const char* name, int value);
 FIC_API int fic_rgb_ctx_last_sweep(fic_rgb_ctx* ctx);
+/* Test hooks of the matrix-core RGB sweep, with the contracts of fic_ctx_last_kernel and fic_ctx_sweep_stats: the name of the
+ * sweep kernel the last encode launched -- "k_sweep_q<4, 3, false>" (one pool chunk), "k_sweep_q<4, 3, true>" (several) or
+ * "k_sweep_qs<4, 3>" (several short ones) for "sweep" = 2, the VALU kernel's name for "sweep" = 1 -- and, after
+ * fic_rgb_ctx_set_option(ctx, "sweep_stats", 1), the same eight counters summed over the planes encoded since the last
+ * reset.  Neither changes what is computed. */
+FIC_API int fic_rgb_ctx_last_kernel(fic_rgb_ctx* ctx, char* out, int capacity);
+FIC_API int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* ctx, uint64_t* out8, int reset);
 FIC_API int fic_rgb_ctx_get_results_host(fic_rgb_ctx* ctx, int32_t* idx_local, float* a, float* bR, float* bG, float* bB,
                                          int32_t* qrows5, int32_t* collage_argb);
 FIC_API int fic_rgb_ctx_decode_host(fic_rgb_ctx* ctx, int32_t* argb_out, float* avg_error_out, int* iterations_out);

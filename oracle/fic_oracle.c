@@ -822,6 +822,58 @@ FO_API int fo_encode_rgb(const int32_t* argb, int w, int h, int B, int wK, float
     return 0;
 }
 
+/* Test hook: the colour pool as createCodebuchRGB builds it.  pix int[N_d][n][3], means int[N_d][3] (mittelWertR/G/B),
+ * vD int[N_d] = varianzDomain of FC:778-792 (the f32 sum of greyD_i, an integer below 2^24). */
+FO_API int fo_pool_rgb(const int32_t* argb, int w, int h, int B, int32_t* pix, int32_t* means, int32_t* vD)
+{
+    int rc = fo_geometry(w, h, B, 0, 0, 0, 0);
+    if (rc) return rc;
+    int n = B * B;
+    fo_codebook_rgb cb;
+    rc = fo_create_codebuch_rgb(argb, w, h, B, &cb);
+    if (rc) { fo_codebook_rgb_free(&cb); return rc; }
+    for (int g = 0; g < cb.count; g++) {
+        const int32_t* d = cb.argb + (size_t)g * n;
+        float domainR = (float)cb.mR[g], domainG = (float)cb.mG[g], domainB = (float)cb.mB[g];
+        float varianzDomain = 0;
+        for (int i = 0; i < n; i++) {
+            for (int c = 0; c < 3; c++) pix[((size_t)g * n + i) * 3 + c] = chan(d[i], c);
+            varianzDomain += ((float)red(d[i]) - domainR) + ((float)green(d[i]) - domainG) + ((float)blue(d[i]) - domainB);
+        }
+        means[3 * g] = cb.mR[g]; means[3 * g + 1] = cb.mG[g]; means[3 * g + 2] = cb.mB[g];
+        vD[g] = (int32_t)varianzDomain;
+    }
+    fo_codebook_rgb_free(&cb);
+    return 0;
+}
+
+/* Test hook: greyR int[N_r][n] and varianzRange int[N_r] of every range block (FC:766-790; w, h multiples of B). */
+FO_API int fo_range_rgb(const int32_t* argb, int w, int h, int B, int32_t* greyR, int32_t* vR)
+{
+    int rc = fo_geometry(w, h, B, 0, 0, 0, 0);
+    if (rc) return rc;
+    if (w % B || h % B) return -5;
+    int n = B * B, j = 0;
+    for (int y = 0; y < h; y += B)
+        for (int x = 0; x < w; x += B, j++) {
+            int sR = 0, sG = 0, sB = 0;
+            for (int i = 0; i < n; i++) {
+                int32_t v = argb[(x + i % B) + (y + i / B) * w];
+                sR += red(v); sG += green(v); sB += blue(v);
+            }
+            int rangeRM = sR / n, rangeGM = sG / n, rangeBM = sB / n;
+            float varianzRange = 0;
+            for (int i = 0; i < n; i++) {
+                int32_t v = argb[(x + i % B) + (y + i / B) * w];
+                float g = (float)((red(v) - rangeRM) + (green(v) - rangeGM) + (blue(v) - rangeBM));
+                greyR[(size_t)j * n + i] = (int32_t)g;
+                varianzRange += g;
+            }
+            vR[j] = (int32_t)varianzRange;
+        }
+    return 0;
+}
+
 /* getBestGeneratedCollageRGB FC:308-347; info float[N_r][5], its column 0 is mutated to the global index */
 FO_API int fo_collage_rgb(const int32_t* argb, int w, int h, int B, int wK, float* info, int32_t* out_argb)
 {

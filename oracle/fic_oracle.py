@@ -55,6 +55,8 @@ def lib():
         L.fo_is_greyscale.argtypes = [i32p, C.c_int, C.c_int]
         L.fo_encode_rgb.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p]
         L.fo_write_run_rgb.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p]
+        L.fo_pool_rgb.argtypes = [i32p, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p]
+        L.fo_range_rgb.argtypes = [i32p, C.c_int, C.c_int, C.c_int, i32p, i32p]
         L.fo_write_run_rgb.restype = C.c_int64
         _lib = L
     return _lib
@@ -185,6 +187,32 @@ def encode_rgb(argb, w, h, B, wK):
     if rc:
         raise ValueError(f"fo_encode_rgb rc={rc}")
     return info
+
+
+def pool_rgb(argb, w, h, B):
+    """The colour pool: pixels int32 [N_d, n, 3], channel means [N_d, 3], varianzDomain [N_d]."""
+    Rw, Rh, Dw, Dh = geometry(w, h, B)
+    nd, n = Dw * Dh, B * B
+    pix = np.zeros((nd, n, 3), np.int32)
+    means = np.zeros((nd, 3), np.int32)
+    vD = np.zeros(nd, np.int32)
+    argb = np.ascontiguousarray(argb, np.int32)
+    rc = lib().fo_pool_rgb(_p(argb, C.c_int32), w, h, B, _p(pix, C.c_int32), _p(means, C.c_int32), _p(vD, C.c_int32))
+    if rc:
+        raise ValueError(f"fo_pool_rgb rc={rc}")
+    return pix, means, vD
+
+
+def range_rgb(argb, w, h, B):
+    """greyR int32 [N_r, n] and varianzRange [N_r] of the range blocks."""
+    Rw, Rh, Dw, Dh = geometry(w, h, B)
+    greyR = np.zeros((Rw * Rh, B * B), np.int32)
+    vR = np.zeros(Rw * Rh, np.int32)
+    argb = np.ascontiguousarray(argb, np.int32)
+    rc = lib().fo_range_rgb(_p(argb, C.c_int32), w, h, B, _p(greyR, C.c_int32), _p(vR, C.c_int32))
+    if rc:
+        raise ValueError(f"fo_range_rgb rc={rc}")
+    return greyR, vR
 
 
 def decode_rgb(run, avg_error_in=0.0):

@@ -438,3 +438,112 @@ def rgb_kov_java(greyR, psum, msum):
     for i in range(gd.shape[1]):
         kov = (kov + np.outer(gd[:, i], gr[:, i]).astype(F32)).astype(F32)
     return kov
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# colour inputs that push pairs against the joint-RGB bound
+# ---------------------------------------------------------------------------------------------------------------------
+# B -> image side, share of the rows that hold domain probes, h1_c + h2_c of every probe pair per channel (= rho_c mod n)
+# (chosen among a few sums per block size for the roundings of greyD / vD: vD = 5 / 3 / 13)
+TIGHT_RGB_SHAPES = {4: (128, 0.5, (226, 226, 225)), 8: (256, 0.5, (257, 257, 257)), 16: (512, 0.75, (261, 260, 260))}
+
+
+# The smallest q_eshift (E_r times 2^-q_eshift) at which the model finds prune witnesses on the committed generator, seed 1
+# (tests/test_q_bound.py asserts it; tests/test_gpu_rgb_q_bound.py shrinks the device's E_r by it).  1 is undetectable.
+TIGHT_RGB_ESHIFT = {4: 2, 8: 2, 16: 2}
+
+
+def tight_rgb_image(B, seed=1, size=None, bg=40, band=0.12):
+    """A colour image whose range blocks sit against the joint-RGB prune bound, and the first probe range r0.
+
+    q = kovarianz / vD is not normalised by the domain block's norm, and E_r carries the pool-wide factor Amax = max ||greyD|| /
+    vD: the bound is tight only where the competing blocks have ||greyD|| / vD close to Amax, so the generator fixes vD and
+    the norm of EVERY non-flat block of the pool.
+      * Top rows, "domain probes": spike pairs (h1, h2 per channel) at x, x + 2 of one row of the SCALED image (uniform 2x2
+        cells), one pair per (pitch x B) cell, pitch = B + 2 rounded up to a multiple of abstand: a domain block holds a whole
+        pair, one spike of a cut pair, or nothing.  Per channel h1_c + h2_c is the same constant for all pairs, = rho_c mod
+        n: every block with a whole pair has vD = sum rho_c (5, 3, 13: greyD / vD rounds in f16), the same floor term, and
+        ||greyD|| within 1 % (H1 + H2 constant, H1 : H2 within 1 +- band) -- these blocks are Amax.  A block with one spike has
+        vD = sum (h_c mod n) >= 6 by construction (residues 0 and 1 are rejected) and at most half the squared norm; all other
+        blocks are flat (vD = 0).
+      * Bottom rows, "range probes": spikes a1, a2 = a1 - (0..2 per channel) at (1, 1) and (3, 1) of every range block -- odd
+        coordinates, which the reference's colour down-scaling never reads (its 4th tap repeats the lower-left pixel), so
+        the pool under the range probes is flat and cannot set Amax.
+    With H1 + H2 constant, q of the matching blocks is const + (A1 - A2) H1 / vD: all of them lie within a fraction of E_r of
+    each other, while the f16 roundings of (H1 - eps) / vD and (H2 - eps) / vD differ by a sizeable share of E_r.  The pair with
+    the largest H1 and the one with the smallest come last in the pool, so the exact winner of every probe range has the
+    other candidates in earlier domain tiles (rgb_prune_witnesses)."""
+    S, frac, csum = TIGHT_RGB_SHAPES[B]
+    S = S if size is None else size
+    n, ab = B * B, B // 4
+    pitch = -(-(B + 2) // ab) * ab
+    rng = np.random.default_rng(seed)
+    top = int(S * frac) // (2 * B) * (2 * B)
+    sc = np.full((top // 2, S // 2, 3), bg, np.int64)
+    cells = [(x, y) for y in range(1, top // 2 - 1, B) for x in range(1, S // 2 - 3, pitch)]
+    pairs = []
+    while len(pairs) < len(cells):
+        h1 = np.array([int(round(c / 2 * rng.uniform(1 - band, 1 + band))) for c in csum])
+        h2 = np.array(csum) - h1
+        if all(1 <= h <= 255 - bg and h % n >= 2 for h in list(h1) + list(h2)):
+            pairs.append((h1, h2))
+    # The pair with the largest H1 and the one with the smallest come last in the pool (the exact winners of the probe ranges
+    # with A1 > A2 and A1 < A2), each moved 1..7 further out to the step whose two f16 roundings fall lowest: the winner's
+    # test value then lies below its q, the near-equal candidates of the earlier tiles above theirs.
+    eps, vd = sum(c // n for c in csum), sum(c % n for c in csum)
+
+    def low(h1):
+        x = np.array([h1.sum() - eps, sum(csum) - h1.sum() - eps], np.int64)
+        return float(((x.astype(F32) / F32(vd)).astype(np.float16).astype(np.float64) - x / vd).sum())
+
+    def ok(h1):
+        return all(1 <= h <= 255 - bg and h % n >= 2 for h in list(h1) + list(np.array(csum) - h1))
+
+    H1 = [int(p[0].sum()) for p in pairs]
+    ends = []
+    for i, sgn in ((int(np.argmin(H1)), -1), (int(np.argmax(H1)), 1)):
+        cand = []
+        for k in range(1, 8):
+            for c in range(3):
+                h1 = pairs[i][0] + sgn * np.array([k // 3 + (1 if (j - c) % 3 < k % 3 else 0) for j in range(3)])
+                if ok(h1):
+                    cand.append((low(h1), k, c, h1))
+        h1 = min(cand, key=lambda t: t[:3])[3]
+        ends.append((h1, np.array(csum) - h1))
+    keep = [p for i, p in enumerate(pairs) if i not in (int(np.argmin(H1)), int(np.argmax(H1)))]
+    pairs = keep + ends
+    order = range(len(pairs))
+    for (x, y), i in zip(cells, order):
+        sc[y, x], sc[y, x + 2] = bg + pairs[i][0], bg + pairs[i][1]
+    g = np.full((S, S, 3), bg, np.int64)
+    g[:top] = np.repeat(np.repeat(sc, 2, 0), 2, 1)
+    for by in range(top // B, S // B):
+        for bx in range(S // B):
+            a1 = rng.integers(150, 211, 3)
+            d = rng.integers(0, 3, 3)
+            if d.sum() == 0:
+                d[int(rng.integers(0, 3))] = 1
+            sgn = 1 if rng.integers(0, 2) else -1
+            g[by * B + 1, bx * B + 1], g[by * B + 1, bx * B + 3] = bg + a1, bg + a1 - sgn * d
+    return np.clip(g, 0, 255).astype(np.uint8), (top // B) * (S // B)
+
+
+def rgb_sweep_tables(rgb, B, eshift=0):
+    """Everything the prune test of one colour image sees, from the model (the colour analogue of sweep_tables): operands,
+    test values |acc| (exact sums of the f16 products), the accumulation allowance, vR, and E_r with the square roots one ulp
+    low (the smallest E_r the device can store)."""
+    H, W = rgb.shape[:2]
+    G = Geom(W, H, B)
+    psum, msum, vD = rgb_pool(rgb, B)
+    gR, vR = rgb_range(rgb, B)
+    A, norm = rgb_domain_operands(psum, msum, vD, -1)
+    amax = norm.max()
+    E = rgb_error_bound(gR, amax, eshift, -1)
+    Bc = gR.astype(np.float16)
+    return {"G": G, "psum": psum, "msum": msum, "vD": vD, "gR": gR, "A": A, "norm": norm, "amax": amax,
+            "rs": {"rem": vR, "E": E}, "val": np.abs(acc_exact(A, Bc)), "allow": allowance(A, Bc, G.NK), "folded": False}
+
+
+def rgb_prune_witnesses(T, winners, s, r0=0):
+    """prune_witnesses for the tables of rgb_sweep_tables; `winners` are the oracle's (encode_rgb, full search)."""
+    return prune_witnesses(T, winners, np.zeros(len(winners), np.int64), s, r0)

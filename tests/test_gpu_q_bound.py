@@ -6,7 +6,8 @@
      the CPU checks of the bound and its lemmas (tests/test_q_bound.py) speak about the real operands.
   2. Option "q_eshift" (E_r times 2^-k): at k = 0 the stored E_r is the model's exactly; wider thresholds (k < 0, up to every
      pair flagged) give the same codebooks; a threshold 8 times too narrow (k = 3) is CAUGHT on the tight inputs
-     (qmodel.tight_image) for every grey mode and block size, against the VALU sweep -- which random images do not do."""
+     (qmodel.tight_image) for every grey mode and block size, against the VALU sweep -- which random images do not do.
+     (Joint RGB, k_sweep_q<NK, 3>: tests/test_gpu_rgb_q_bound.py.)"""
 import numpy as np
 import pytest
 
@@ -294,18 +295,18 @@ def test_too_narrow_threshold_is_caught(B, n_iso, capsys):
               f"(mismatches at E_r/4, /8, /16): {rnd}")
 
 
-def test_rgb_wider_threshold_gives_the_same_codebooks(capsys):
+def test_rgb_wider_threshold_gives_the_same_codebooks():
     """Joint RGB through the matrix-core sweep (k_sweep_q<NK, 3>): E_r (with its Amax factor) times 4 and 4096 gives the same
-    codebook as E_r.  Recorded, not asserted: how many entries E_r / 8 and E_r / 16 change on this natural image."""
+    codebook as E_r on a natural image.  That a narrower E_r is caught is asserted on the tight colour inputs
+    (tests/test_gpu_rgb_q_bound.py); a natural image does not sit against the bound."""
     rgb = np.load(f"{GOLDEN}/lena_colored_256.npy")
     from oracle import fic_oracle as fo
     argb = fo.rgb_to_argb(rgb)
     h, w = rgb.shape[:2]
-    out = {}
     for B in (8, 16):
         Dw = fic_amd.geometry(w, h, B)[2]
         res = {}
-        for k in (0, -2, -12, 3, 4):
+        for k in (0, -2, -12):
             with fic_amd.capi.RgbEncoder(w, h, B, Dw) as enc:
                 enc.set_option("sweep", 2)
                 enc.set_option("q_eshift", k)
@@ -319,9 +320,6 @@ def test_rgb_wider_threshold_gives_the_same_codebooks(capsys):
             for key in ("a", "bR", "bG", "bB"):
                 x, y = res[k][key], res[0][key]
                 assert ((x.view(np.uint32) == y.view(np.uint32)) | (np.isnan(x) & np.isnan(y))).all(), (B, k, key)
-        out[B] = {k: int((res[k]["idx_local"] != res[0]["idx_local"]).sum()) for k in (3, 4)}
-    with capsys.disabled():
-        print(f"\n[q_eshift] joint RGB lena 256: changed winners at E_r/8, E_r/16 by B: {out}")
 
 
 @pytest.mark.parametrize("B", [4, 8, 16])

@@ -7,7 +7,8 @@ model's operands ARE the device's, bit for bit, so these are statements about th
   * the lemmas the derivation rests on: the chunk-start rule, the theta invariant (folded maximum included), operands never
     subnormal, FIC_Q_TAU_ALL above every test value;
   * the tight inputs (qmodel.tight_image) really are tight: many range blocks have a pair X in an earlier domain tile whose
-    test value exceeds the exact winner's by more than 2 s E_r -- what the GPU tests need to catch a bound shrunk by s."""
+    test value exceeds the exact winner's by more than 2 s E_r -- what the GPU tests need to catch a bound shrunk by s;
+  * the same for joint RGB (k_sweep_q<NK, 3>, E_r scaled by the pool-wide Amax) on qmodel.tight_rgb_image."""
 import numpy as np
 import pytest
 
@@ -204,7 +205,8 @@ def test_rgb_bound_with_amax(B):
     the pool) -- against the exact integer kovarianz and against the reference's f32 sequential one (the value it compares),
     on random colour, low-contrast colour (vD small: large operands near Amax) and grey-as-colour images.  The square roots
     are taken one ulp low (the device's are within one ulp).  These inputs reach ~0.1-0.2 of E_r: Amax is a pool-wide
-    factor, so RGB has no tight inputs here and no test that a shrunk RGB bound is caught."""
+    factor and their winning candidates lie far below it.  The inputs that sit against the colour bound are
+    qmodel.tight_rgb_image (the tests below; tests/test_gpu_rgb_q_bound.py shows that a shrunk RGB bound is caught on them)."""
     rng = np.random.default_rng(3 + B)
     imgs = {"random": rng.integers(0, 256, (64, 64, 3)), "lowamp": 120 + rng.integers(-3, 4, (64, 64, 3)),
             "grey": np.repeat(rng.integers(0, 256, (64, 64, 1)), 3, 2)}
@@ -224,3 +226,85 @@ def test_rgb_bound_with_amax(B):
             worst = max(worst, ((np.abs(acc[live] - qq) + allow[live]) / E[None, :]).max())
     assert worst <= 1.0, worst
     assert worst >= 0.02, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# joint RGB on the tight colour inputs (qmodel.tight_rgb_image)
+# ---------------------------------------------------------------------------------------------------------------------
+_RGB_TIGHT = {}
+
+
+def _rgb_tight(B):
+    if B not in _RGB_TIGHT:
+        rgb, r0 = M.tight_rgb_image(B)
+        _RGB_TIGHT[B] = (rgb, r0, M.rgb_sweep_tables(rgb, B))
+    return _RGB_TIGHT[B]
+
+
+# Floors of max (|acc - q| + allowance) / E_r on the tight colour inputs, seed 1: measured 0.429 / 0.353 / 0.538 (the same
+# against the exact kovarianz and against the f32 sequential one: two spikes per block keep every partial sum below 2^24),
+# set at about 60 %.  (2^-11 * 1.07 / 7.0e-4 = 0.75 is the most any input can reach.)
+RGB_TIGHT_FLOOR = {4: 0.25, 8: 0.21, 16: 0.32}
+
+
+@pytest.mark.parametrize("B", [4, 8, 16])
+def test_rgb_bound_holds_and_is_approached_on_the_tight_inputs(B):
+    """|acc - kovarianz / vD| + allowance <= E_r over every non-flat domain block and every range block of the tight colour
+    image, against the exact integer kovarianz and against the reference's f32 sequential one; the worst pair comes within
+    a stated share of E_r (random colour images: 0.1-0.2); and the construction holds what it promises: Amax is the norm of
+    the blocks with a whole probe pair, which all have the same small vD and norms within 2 % of each other."""
+    rgb, r0, T = _rgb_tight(B)
+    vD, norm = T["vD"], T["norm"]
+    live = vD != 0
+    n = B * B
+    vd_pair = sum(c % n for c in M.TIGHT_RGB_SHAPES[B][2])
+    pair = vD == vd_pair
+    assert pair.sum() >= 100 and vD[live].min() == vd_pair
+    assert norm[pair].max() == T["amax"] and norm[pair].min() >= 0.98 * float(T["amax"])
+    assert not (live & ~pair).any() or norm[live & ~pair].max() < 0.6 * float(T["amax"])
+    E = T["rs"]["E"].astype(np.float64)
+    acc = M.acc_exact(T["A"], T["gR"].astype(np.float16))
+    q = ((T["psum"] - T["msum"][:, None]) @ T["gR"].T)[live] / vD[live, None].astype(np.float64)
+    qJ = M.rgb_kov_java(T["gR"], T["psum"][live], T["msum"][live]).astype(np.float64) / vD[live, None]
+    for name, qq in (("exact", q), ("java", qJ)):
+        worst = ((np.abs(acc[live] - qq) + T["allow"][live]) / E[None, :]).max()
+        print(f"[rgb tight] B={B} {name}: worst {worst:.4f}")
+        assert worst <= 1.0, (name, worst)
+        assert worst >= RGB_TIGHT_FLOOR[B], f"tight colour inputs reach only {worst:.3f} of E_r ({name})"
+
+
+def test_rgb_model_pool_is_the_oracle_pool(oracle):
+    """rgb_pool / rgb_range are the oracle's colour pool and range statistics on the tight colour images: pool pixels, the
+    channel means and vD (sum of greyD as the reference accumulates it), greyR and vR."""
+    for B in (4, 8, 16):
+        rgb, r0, T = _rgb_tight(B)
+        S = rgb.shape[0]
+        pix, means, vD = oracle.pool_rgb(oracle.rgb_to_argb(rgb), S, S, B)
+        assert (pix.sum(2) == T["psum"]).all(), B
+        assert (means.sum(1) == T["msum"]).all(), B
+        assert (vD == T["vD"]).all(), B
+        gR, vR = oracle.range_rgb(oracle.rgb_to_argb(rgb), S, S, B)
+        assert (gR == T["gR"]).all() and (vR == T["rs"]["rem"]).all(), B
+
+
+# Floors of the witness counts on the committed generator (qmodel.tight_rgb_image, seed 1), probe ranges only: none at s = 1
+# and 1/2 (the bound is sound); measured at s = 1/4: 511 of 512 / 512 of 512 / 246 of 256 range blocks -- every block size
+# reaches the largest detectable shrink, q_eshift = 2 -- and at s = 1/8: 511 / 512 / 256.  Floors at about 60 %.
+RGB_WITNESS_FLOOR = {4: (300, 300), 8: (300, 300), 16: (150, 150)}
+
+
+@pytest.mark.parametrize("B", [4, 8, 16])
+def test_rgb_tight_inputs_have_prune_witnesses(oracle, B):
+    """Probe ranges of the tight colour image where a pair X of an earlier domain tile reaches, with E_r shrunk to s E_r, a
+    theta above the test value of the exact winner W (the oracle's encodeRGB, full search; MFMA allowances included): a
+    one-chunk k_sweep_q<NK, 3> whose E_r is s times too small skips W."""
+    rgb, r0, T = _rgb_tight(B)
+    S = rgb.shape[0]
+    ref = oracle.encode_rgb(oracle.rgb_to_argb(rgb), S, S, B, T["G"].Dw)
+    win = ref[:, 0].astype(np.int64)
+    counts = {s: int(M.rgb_prune_witnesses(T, win, s, r0)[0].sum()) for s in (1.0, 0.5, 0.25, 0.125, 0.0625)}
+    print(f"[rgb witnesses] B={B}: {counts}")
+    f4, f8 = RGB_WITNESS_FLOOR[B]
+    assert counts[1.0] == 0 and counts[0.5] == 0, counts
+    assert counts[0.25] >= f4 and counts[0.125] >= f8, counts
+    assert counts[2.0 ** -M.TIGHT_RGB_ESHIFT[B]] >= 1 and all(counts[2.0 ** -k] == 0 for k in range(M.TIGHT_RGB_ESHIFT[B]))
