@@ -21,6 +21,14 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
+int check_device(int device)
+{
+    int ndev = fic_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d (this library has no CPU path)", device);
+    HIP_TRY(hipSetDevice(device));
+    return FIC_OK;
+}
+
 static int ilog2(int v)
 {
     int l = 0;
@@ -481,14 +489,10 @@ int64_t fic_write_run_gray(const int32_t* qrows, int n_ranges, int w, int h, int
     if (!qrows || !out || n_ranges < 0) return fail(FIC_E_ARGUMENT, "fic_write_run_gray: bad argument");
     int64_t need = 20 + 12 * (int64_t)n_ranges;
     if (capacity < need) return fail(FIC_E_CAPACITY, "fic_write_run_gray: need %lld bytes, have %lld", (long long)need, (long long)capacity);
-    auto put = [](uint8_t* p, int32_t v) {
-        uint32_t u = (uint32_t)v;
-        p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u;
-    };
     const int32_t hdr[5] = {0, w, h, B, wK};          // FC:234-238
-    for (int i = 0; i < 5; i++) put(out + 4 * i, hdr[i]);
+    for (int i = 0; i < 5; i++) put_be32(out + 4 * i, hdr[i]);
     uint8_t* p = out + 20;
-    for (int64_t i = 0; i < 3 * (int64_t)n_ranges; i++, p += 4) put(p, qrows[i]);   // FC:241-245
+    for (int64_t i = 0; i < 3 * (int64_t)n_ranges; i++, p += 4) put_be32(p, qrows[i]);   // FC:241-245
     return need;
 }
 
@@ -884,12 +888,10 @@ int fic_sweep_ranges_per_pool_read(int kind, int B, int n_iso)
 int fic_debug_sqrt_f64(int device, uint32_t first, uint32_t count, double* out)
 {
     if (!out || count == 0) return fail(FIC_E_ARGUMENT, "fic_debug_sqrt_f64: bad argument");
-    int ndev = fic_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
+    int rc = check_device(device);
+    if (rc) return rc;
     double* d = nullptr;
     HIP_TRY(hipMalloc((void**)&d, (size_t)count * sizeof(double)));
-    int rc = FIC_OK;
     if (fic_launch_sqrt_probe(d, first, count, nullptr)) rc = fail(FIC_E_HIP, "k_sqrt_probe launch failed");
     if (rc == FIC_OK) {
         hipError_t e = hipMemcpy(out, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost);

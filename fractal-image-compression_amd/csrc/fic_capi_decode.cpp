@@ -60,10 +60,10 @@ static thread_local int g_last_sum_fallbacks = 0;
 // Runs the reconstruction loop on the device.  The first 8 iterations are enqueued in one go, later ones in pairs, and the
 // per-plane loop state is read back after each group (a converging decode takes 6-9 iterations): one host sync per
 // group, none per iteration; iterations enqueued behind the last one exit at once.  `iteration(counter)` enqueues one
-// iteration (scale, paint, loop control) on s; d_image [planes][npix] starts grey 128.
+// iteration (scale, paint, loop control) on s; d_image [planes][npix] pixels of kind.px_bytes is filled with kind.px_start here.
 //   d_state [planes]: scratch of the caller
-int ficd::decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState* d_state, const float* avg_in, float* avg_out,
-                      int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration)
+int ficd::decode_loop(const DecodeKind& kind, int planes, size_t npix, void* d_image, FicDecodeState* d_state, const float* avg_in,
+                      float* avg_out, int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration)
 {
     const size_t P = (size_t)planes;
     std::vector<FicDecodeState> st(P);
@@ -71,18 +71,20 @@ int ficd::decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState*
     for (size_t p = 0; p < P; p++) st[p].avg = avg_in ? avg_in[p] : 0.0f;   // static avgError is never reset (FC:20)
     int rc = FIC_OK;
     hipError_t e = hipMemcpyAsync(d_state, st.data(), P * sizeof(FicDecodeState), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_image, 128, P * npix, s);             // generateGrayImage FC:1142-1148
-    if (e != hipSuccess) rc = fail(FIC_E_HIP, "decode init: %s", hipGetErrorString(e));
+    if (e == hipSuccess)                                                            // generateGrayImage FC:1142-1148
+        e = kind.px_bytes == 1 ? hipMemsetAsync(d_image, (int)kind.px_start, P * npix, s)
+                               : hipMemsetD32Async((hipDeviceptr_t)d_image, (int)kind.px_start, P * npix, s);
+    if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s init: %s", kind.name, hipGetErrorString(e));
     for (int counter = 0; rc == FIC_OK && counter < 50; counter++) {
         if (iteration(counter)) {
-            rc = fail(FIC_E_HIP, "decode iteration launch failed");
+            rc = fail(FIC_E_HIP, "%s iteration launch failed", kind.name);
             break;
         }
         // a converging decode takes 6-9 iterations: look at the loop state after 8, then after every second iteration
         if (counter == 7 || (counter > 7 && (counter & 1)) || counter == 49) {
             e = hipMemcpyAsync(st.data(), d_state, P * sizeof(FicDecodeState), hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { rc = fail(FIC_E_HIP, "decode readback: %s", hipGetErrorString(e)); break; }
+            if (e != hipSuccess) { rc = fail(FIC_E_HIP, "%s readback: %s", kind.name, hipGetErrorString(e)); break; }
             bool all = true;
             for (size_t p = 0; p < P; p++) all = all && st[p].done;
             if (all) break;
@@ -90,9 +92,11 @@ int ficd::decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState*
     }
     if (rc != FIC_OK) return rc;
     for (size_t p = 0; p < P; p++) {
-        if (st[p].bad_index)
-            return fail(FIC_E_ARGUMENT, "decode: a codebook row of plane %zu points outside the domain pool "
-                                        "(ArrayIndexOutOfBounds at FC:394 in the reference)", p);
+        if (st[p].bad_index) {
+            const std::string of_plane = P > 1 ? " of plane " + std::to_string(p) : "";
+            return fail(FIC_E_ARGUMENT, "%s: a codebook row%s points outside the domain pool (ArrayIndexOutOfBounds at %s in the "
+                                        "reference)", kind.name, of_plane.c_str(), kind.paint_line);
+        }
         if (avg_out) avg_out[p] = st[p].avg_out;
         if (iters_out) iters_out[p] = st[p].iters;
         if (seq_out) seq_out[p] = st[p].seq_sums;
@@ -107,7 +111,7 @@ static int run_decode_loop(const FicGeom& g, uint8_t* d_scaled, uint8_t* d_image
                            const int32_t* d_iso, FicDecodeState* d_state, uint32_t* d_sqbuf, const float* avg_in,
                            float* avg_out, int* iters_out, int* seq_out, hipStream_t s)
 {
-    return decode_loop(g.planes, (size_t)g.W * g.H, d_image, d_state, avg_in, avg_out, iters_out, seq_out, s, [&](int counter) {
+    return decode_loop(kDecodeGrey, g.planes, (size_t)g.W * g.H, d_image, d_state, avg_in, avg_out, iters_out, seq_out, s, [&](int counter) {
         return fic_launch_decode_iteration(d_scaled, d_image, d_qrows, d_iso, d_state, d_sqbuf, counter, g, s);
     });
 }
@@ -131,19 +135,13 @@ int fic_ctx_decode_host(fic_ctx* c, uint8_t* gray_out, float* avg_error_out, int
     return FIC_OK;
 }
 
-static int32_t run_be32(const uint8_t* run, int64_t off)
-{
-    return (int32_t)(((uint32_t)run[off] << 24) | ((uint32_t)run[off + 1] << 16) | ((uint32_t)run[off + 2] << 8) |
-                     (uint32_t)run[off + 3]);
-}
-
 static int decode_gray_run_impl(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
                                 int* h_out, float* avg_error_io, int* iterations, int* seq_sums)
 {
     if (!run || len < 20) return fail(FIC_E_ARGUMENT, "fic_decode_gray_run: stream shorter than the 20-byte header");
-    if (run_be32(run, 0) != 0)
-        return fail(FIC_E_NOT_GREY, "fic_decode_gray_run: isRGB = %d (FC:548-552 dispatches to decodeRGB)", run_be32(run, 0));
-    const int w = run_be32(run, 4), h = run_be32(run, 8), B = run_be32(run, 12), wK = run_be32(run, 16);
+    if (get_be32(run) != 0)
+        return fail(FIC_E_NOT_GREY, "fic_decode_gray_run: isRGB = %d (FC:548-552 dispatches to decodeRGB)", get_be32(run));
+    const int w = get_be32(run + 4), h = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
     FicGeom g;
     int rc = make_geometry(w, h, B, wK, 1, 1, &g);
     if (rc) return rc;
@@ -153,11 +151,10 @@ static int decode_gray_run_impl(const uint8_t* run, int64_t len, int device, uin
         return fail(FIC_E_ARGUMENT, "fic_decode_gray_run: %lld bytes, need %lld (EOFException in the reference)",
                     (long long)len, (long long)(20 + 12 * (int64_t)g.Nr));
     if (!gray_out || capacity < (int64_t)w * h) return fail(FIC_E_CAPACITY, "fic_decode_gray_run: output needs %d bytes", w * h);
-    int ndev = fic_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d (this library has no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
+    rc = check_device(device);
+    if (rc) return rc;
     std::vector<int32_t> q((size_t)g.Nr * 3);
-    for (size_t i = 0; i < q.size(); i++) q[i] = run_be32(run, 20 + 4 * (int64_t)i);          // FC:372-374
+    for (size_t i = 0; i < q.size(); i++) q[i] = get_be32(run + 20 + 4 * i);          // FC:372-374
     const size_t npix = (size_t)w * h;
     const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g.Ws * g.Hs), o_q = o_image + align256(npix),
                  o_state = o_q + align256(q.size() * 4), o_sq = o_state + align256(sizeof(FicDecodeState)),
@@ -190,9 +187,8 @@ int fic_decode_gray_run(const uint8_t* run, int64_t len, int device, uint8_t* gr
 int fic_debug_float_sum(int device, float carry, const uint32_t* vals, int count, float* out)
 {
     if (!vals || !out || count < 0) return fail(FIC_E_ARGUMENT, "fic_debug_float_sum: bad argument");
-    int ndev = fic_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
+    int rc = check_device(device);
+    if (rc) return rc;
     uint32_t* d = nullptr;
     float* r = nullptr;
     uint32_t* maps = nullptr;
@@ -200,7 +196,7 @@ int fic_debug_float_sum(int device, float carry, const uint32_t* vals, int count
     hipError_t e = hipMalloc((void**)&r, 8);
     if (e == hipSuccess) e = hipMalloc((void**)&maps, (fic_float_sum_map_words((size_t)count) + 4) * 4);
     if (e == hipSuccess) e = hipMemcpy(d, vals, (size_t)count * 4, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? FIC_OK : fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
     if (rc == FIC_OK && fic_launch_float_sum_probe(carry, d, count, maps, r, nullptr)) rc = fail(FIC_E_HIP, "k_float_sum_probe launch failed");
     if (rc == FIC_OK) {
         float two[2] = {0.0f, 0.0f};
@@ -230,8 +226,8 @@ int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* arg
                        int* w_out, int* h_out, float* avg_error_io, int* iterations)
 {
     if (!run || len < 20) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: stream shorter than the 20-byte header");
-    if (run_be32(run, 0) == 0) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: isRGB = 0 (FC:548-550 dispatches to decodeGreyScale)");
-    const int w = run_be32(run, 4), h = run_be32(run, 8), B = run_be32(run, 12), wK = run_be32(run, 16);
+    if (get_be32(run) == 0) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: isRGB = 0 (FC:548-550 dispatches to decodeGreyScale)");
+    const int w = get_be32(run + 4), h = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
     FicGeom g;
     int rc = make_geometry(w, h, B, wK, 1, 1, &g);
     if (rc) return rc;
@@ -241,13 +237,11 @@ int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* arg
         return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: %lld bytes, need %lld (EOFException in the reference)",
                     (long long)len, (long long)(20 + 20 * (int64_t)g.Nr));
     if (!argb_out || capacity_pixels < (int64_t)w * h) return fail(FIC_E_CAPACITY, "fic_decode_rgb_run: output needs %d ints", w * h);
-    int ndev = fic_device_count();
-    if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d (this library has no CPU path)", device);
-    HIP_TRY(hipSetDevice(device));
+    rc = check_device(device);
+    if (rc) return rc;
     std::vector<int32_t> q((size_t)g.Nr * 5);
-    for (size_t i = 0; i < q.size(); i++) q[i] = run_be32(run, 20 + 4 * (int64_t)i);          // FC:446-450
+    for (size_t i = 0; i < q.size(); i++) q[i] = get_be32(run + 20 + 4 * i);          // FC:446-450
     const size_t npix = (size_t)w * h;
-    std::vector<int32_t> init(npix, (int32_t)0xff808080u);                          // generateGrayImage FC:1142-1148
     const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g.Ws * g.Hs * 4), o_q = o_image + align256(npix * 4),
                  o_state = o_q + align256(q.size() * 4), o_sq = o_state + align256(sizeof(FicDecodeState)),
                  total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
@@ -259,34 +253,18 @@ int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* arg
     int32_t* d_q = (int32_t*)(ar.base + o_q);
     FicDecodeState* d_state = (FicDecodeState*)(ar.base + o_state);
     uint32_t* d_sq = (uint32_t*)(ar.base + o_sq);
-    FicDecodeState st;
-    memset(&st, 0, sizeof(st));
-    st.avg = avg_error_io ? *avg_error_io : 0.0f;
     hipError_t e = hipMemcpy(d_q, q.data(), q.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_image, init.data(), npix * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_state, &st, sizeof(st), hipMemcpyHostToDevice);
     if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_decode_rgb_run: %s", hipGetErrorString(e));
-    for (int counter = 0; rc == FIC_OK && counter < 50; counter++) {
-        if (fic_launch_decode_iteration_rgb(d_scaled, d_image, d_q, d_state, d_sq, counter, g, nullptr)) {
-            rc = fail(FIC_E_HIP, "decodeRGB iteration launch failed");
-            break;
-        }
-        if ((counter & 7) == 7 || counter == 49) {
-            e = hipMemcpy(&st, d_state, sizeof(st), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { rc = fail(FIC_E_HIP, "decodeRGB readback: %s", hipGetErrorString(e)); break; }
-            if (st.done) break;
-        }
-    }
-    if (rc == FIC_OK && st.bad_index)
-        rc = fail(FIC_E_ARGUMENT, "decodeRGB: a codebook row points outside the domain pool (ArrayIndexOutOfBounds at FC:477)");
+    float avg = avg_error_io ? *avg_error_io : 0.0f;
+    if (rc == FIC_OK)
+        rc = decode_loop(kDecodeRgb, 1, npix, d_image, d_state, &avg, &avg, iterations, nullptr, nullptr, [&](int counter) {
+            return fic_launch_decode_iteration_rgb(d_scaled, d_image, d_q, d_state, d_sq, counter, g, nullptr);
+        });
     if (rc == FIC_OK) {
         e = hipMemcpy(argb_out, d_image, npix * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_decode_rgb_run: %s", hipGetErrorString(e));
     }
-    if (rc == FIC_OK) {
-        if (avg_error_io) *avg_error_io = st.avg_out;
-        if (iterations) *iterations = st.iters;
-    }
+    if (rc == FIC_OK && avg_error_io) *avg_error_io = avg;
     arena_give(ar);
     return rc;
 }

@@ -377,26 +377,15 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
     if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, 1); if (rc) return rc; }
     if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(1, npix)); if (rc) return rc; }
     hipStream_t s = c->last_stream;
-    std::vector<int32_t> init(npix, (int32_t)0xff808080u);                          // generateGrayImage FC:1142-1148
     for (int p = 0; p < g.planes; p++) {
-        FicDecodeState st;
-        memset(&st, 0, sizeof(st));
-        HIP_TRY(hipMemcpyAsync(c->dec_image, init.data(), npix * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->dec_state, &st, sizeof(st), hipMemcpyHostToDevice, s));
-        for (int counter = 0; counter < 50; counter++) {
-            if (fic_launch_decode_iteration_rgb(c->dec_scaled, c->dec_image, c->qrows + (size_t)p * g.Nr * 5, c->dec_state, c->dec_sq,
-                                                counter, g1, s))
-                return fail(FIC_E_HIP, "decodeRGB iteration launch failed");
-            if ((counter & 7) == 7 || counter == 49) {
-                HIP_TRY(hipMemcpyAsync(&st, c->dec_state, sizeof(st), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                if (st.done) break;
-            }
-        }
-        if (st.bad_index) return fail(FIC_E_ARGUMENT, "decodeRGB: a codebook row of plane %d points outside the domain pool", p);
+        const int32_t* qrows = c->qrows + (size_t)p * g.Nr * 5;
+        int rc = decode_loop(kDecodeRgb, 1, npix, c->dec_image, c->dec_state, nullptr, avg_error_out ? avg_error_out + p : nullptr,
+                             iterations_out ? iterations_out + p : nullptr, nullptr, s, [&](int counter) {
+            return fic_launch_decode_iteration_rgb(c->dec_scaled, c->dec_image, qrows, c->dec_state, c->dec_sq, counter, g1, s);
+        });
+        if (rc == FIC_E_ARGUMENT) return fail(rc, "%s (plane %d of the context)", g_err.c_str(), p);
+        if (rc) return rc;
         HIP_TRY(hipMemcpy(argb_out + (size_t)p * npix, c->dec_image, npix * 4, hipMemcpyDeviceToHost));
-        if (avg_error_out) avg_error_out[p] = st.avg_out;
-        if (iterations_out) iterations_out[p] = st.iters;
     }
     return FIC_OK;
 }
@@ -461,14 +450,10 @@ int64_t fic_write_run_rgb(const int32_t* qrows5, int n_ranges, int w, int h, int
     if (!qrows5 || !out || n_ranges < 0) return fail(FIC_E_ARGUMENT, "fic_write_run_rgb: bad argument");
     int64_t need = 20 + 20 * (int64_t)n_ranges;
     if (capacity < need) return fail(FIC_E_CAPACITY, "fic_write_run_rgb: need %lld bytes, have %lld", (long long)need, (long long)capacity);
-    auto put = [](uint8_t* p, int32_t v) {
-        uint32_t u = (uint32_t)v;
-        p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u;
-    };
     const int32_t hdr[5] = {1, w, h, B, wK};          // FC:234-238, isRGB = 1
-    for (int i = 0; i < 5; i++) put(out + 4 * i, hdr[i]);
+    for (int i = 0; i < 5; i++) put_be32(out + 4 * i, hdr[i]);
     uint8_t* p = out + 20;
-    for (int64_t i = 0; i < 5 * (int64_t)n_ranges; i++, p += 4) put(p, qrows5[i]);   // FC:249-256
+    for (int64_t i = 0; i < 5 * (int64_t)n_ranges; i++, p += 4) put_be32(p, qrows5[i]);   // FC:249-256
     return need;
 }
 

@@ -46,6 +46,20 @@ int dev_alloc(T** p, size_t count)
 }
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Makes `device` current, or refuses it with FIC_E_NO_DEVICE (fic_capi.cpp)
+int check_device(int device);
+
+// DataOutputStream.writeInt / DataInputStream.readInt of the .run streams (FC:234-256, 372-374): big-endian int32
+inline void put_be32(uint8_t* p, int32_t v)
+{
+    uint32_t u = (uint32_t)v;
+    p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u;
+}
+inline int32_t get_be32(const uint8_t* p)
+{
+    return (int32_t)(((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3]);
+}
+
 // idle single-plane grey contexts of the one-shot / multi-device entries (fic_capi.cpp)
 fic_ctx* cache_take(int device, int w, int h, int B, int wK, int n_iso);
 void cache_give(fic_ctx* c);
@@ -66,10 +80,19 @@ struct Arena {
 };
 int arena_take(int device, size_t bytes, Arena* out);
 void arena_give(const Arena& a);
-// the decoder's loop control (decodeGreyScale FC:381-418, fic_capi_decode.cpp) around `iteration(counter)`, which enqueues one
-// iteration -- scale, paint, fic_launch_decode_step -- on s
-int decode_loop(int planes, size_t npix, uint8_t* d_image, FicDecodeState* d_state, const float* avg_in, float* avg_out,
-                int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration);
+// What the two decoders of the reference differ in around their loop: the pixel of generateGrayImage (FC:1142-1148) the image
+// starts from, and the names a row outside the pool is reported with.
+struct DecodeKind {
+    size_t px_bytes;         // 1: grey bytes, 4: packed ARGB
+    uint32_t px_start;
+    const char* name;
+    const char* paint_line;  // where the reference throws ArrayIndexOutOfBounds
+};
+constexpr DecodeKind kDecodeGrey{1, 128u, "decode", "FC:394"}, kDecodeRgb{4, 0xff808080u, "decodeRGB", "FC:477"};
+// the decoder's loop control (decodeGreyScale FC:381-418, decodeRGB FC:458-505; fic_capi_decode.cpp) around
+// `iteration(counter)`, which enqueues one iteration -- scale, paint, fic_launch_decode_step -- on s
+int decode_loop(const DecodeKind& kind, int planes, size_t npix, void* d_image, FicDecodeState* d_state, const float* avg_in,
+                float* avg_out, int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration);
 
 // what fic_release_cache() frees besides the grey contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp

@@ -1,5 +1,5 @@
 // fic_prep.hip -- pool build, range prep, finalise, collage.  The other translation units: fic_sweep.hip (sweeps),
-// fic_mfma.hip (opt-in matrix-core sweeps), fic_decode.hip, fic_rgb.hip.  Overview of ALL kernels follows.
+// fic_mfma.hip (opt-in matrix-core sweeps), fic_decode.hip, fic_rgb.hip, fic_quadtree.hip.  Overview of ALL kernels follows.
 // gfx950 (MI355X / CDNA4) kernels for the bvk_ss19 grey encode hot path.
 //
 // Written for wave64 / SIMD-32 CDNA4 only.  Compile with -ffp-contract=off: every
@@ -18,6 +18,8 @@
 //   k_collage        one-step collage image                       (getBestGeneratedCollage FC:269-300)
 // Decoder:  k_decode_paint / k_decode_paint_rgb / k_decode_step   (decodeGreyScale FC:356-421, decodeRGB FC:430-508)
 // Joint RGB: k_scale_rgb, k_pool_rgb, k_range_rgb, k_sweep_rgb, k_finalize_rgb, k_collage_rgb (encodeRGB FC:171-219 ...)
+// Quadtree (an extension), one set of kernels templated on the pixel format Fmt = QtGrey / QtRgb (fic_launch.h):
+//   k_leaf_sse<Fmt, B>, k_qt_count / k_qt_scan / k_qt_scatter<Fmt>, k_decode_paint_leaves<Fmt, B>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>

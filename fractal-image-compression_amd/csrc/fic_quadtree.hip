@@ -4,12 +4,16 @@
 // like every other translation unit (the paint arithmetic is k_decode_paint's / k_decode_paint_rgb's, one rounding per
 // operation).  DESIGN.md sections 4.13 (grey) and 4.14 (colour).
 //
-//   k_leaf_sse<B>            SSE of the quantised row of every range block of one level against the original image
-//   k_leaf_sse_rgb<B>        the same for joint-RGB rows, summed over the three channels
-//   k_qt_count / k_qt_scan / k_qt_scatter
+// The kernels that touch pixels are templated on the pixel format (QtGrey / QtRgb, fic_launch.h) and share their indexing,
+// their atomics and the reduction of the decoder's squares; only the per-pixel arithmetic of a block row is written per format
+// (qt_row_sse / qt_paint_row on bytes: qt_row_values; on packed ARGB: rgb_row_coef / rgb_paint_px, fic_devfn.h).
+//
+//   k_leaf_sse<Fmt, B>       SSE of the quantised row of every range block of one level against the original image (colour:
+//                            summed over the three channels)
+//   k_qt_count / k_qt_scan / k_qt_scatter<Fmt>
 //                            top-down split of every top-level (B_max) block, leaf count, exclusive scan, ordered scatter
-//   k_decode_paint_leaves<B> one decoder paint of the leaves of one level (three launches per iteration, one per level)
-//   k_decode_paint_leaves_rgb<B>  the same for decodeRGB
+//   k_decode_paint_leaves<Fmt, B>
+//                            one decoder paint of the leaves of one level (three launches per iteration, one per level)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -42,13 +46,62 @@ __device__ __forceinline__ void qt_row_values(const uint8_t* __restrict__ scaled
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_leaf_sse<B>: sse[j] = sum over the block's pixels of (orig - value)^2, exact.  One thread per pixel row of a range block,
-// ordered like k_decode_paint (block row, pixel row, block column); the B row sums of a block meet in sse[j] (zeroed by the
-// launcher) through integer atomics, so the result does not depend on their order.  At most 256 * 255^2 < 2^32 per block.
-// ---------------------------------------------------------------------------------------------
+// The sum over one pixel row `prow` of a range block of (orig - value)^2, grey: q = {qa, qb} of the block's row, k its isometry.
 template <int B>
-__global__ __launch_bounds__(256) void k_leaf_sse(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ scaled,
+__device__ __forceinline__ uint32_t qt_row_sse(const uint8_t* __restrict__ prow, const uint8_t* __restrict__ scaled, const FicGeom& g,
+                                               int gi, int k, int ry, const int32_t* __restrict__ q)
+{
+    int value[B];
+    qt_row_values<B>(scaled, g, gi, k, ry, __fdiv_rn((float)q[0], 100.0f), (float)q[1], value);
+    uint32_t s = 0;
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        const int d = (int)prow[x] - value[x];
+        s += (uint32_t)(d * d);
+    }
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Joint RGB (DESIGN.md 4.14).  The paint arithmetic of k_decode_paint_rgb (rgb_row_coef / rgb_paint_px, fic_devfn.h) on the
+// packed ARGB pixels; d is the domain pixel in the scaleImageRGB copy (FC:901-962), origin (c * B/4, r * B/4).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rgb_sq(int32_t cur, int vR, int vG, int vB)
+{
+    const int dR = ((cur >> 16) & 0xff) - vR, dG = ((cur >> 8) & 0xff) - vG, dB = (cur & 0xff) - vB;
+    return (uint32_t)(dR * dR + dG * dG + dB * dB);
+}
+__device__ __forceinline__ const int32_t* rgb_domain_row(const int32_t* __restrict__ scaled, const FicGeom& g, int gi, int ry)
+{
+    const int c = gi % g.Dw, r = gi / g.Dw;
+    return scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
+}
+
+// The same over the channels R, G, B: q = {q1, q2, q3, q4} (no isometries).
+template <int B>
+__device__ __forceinline__ uint32_t qt_row_sse(const int32_t* __restrict__ prow, const int32_t* __restrict__ scaled, const FicGeom& g,
+                                               int gi, int, int ry, const int32_t* __restrict__ q)
+{
+    const FicRgbCoef cf = rgb_row_coef(q[0], q[1], q[2], q[3]);
+    const int32_t* drow = rgb_domain_row(scaled, g, gi, ry);
+    uint32_t s = 0;
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        int vR, vG, vB;
+        rgb_paint_px(cf, drow[x], vR, vG, vB);
+        s += rgb_sq(prow[x], vR, vG, vB);
+    }
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_leaf_sse<Fmt, B>: sse[j] = sum over the block's pixels (and channels) of (orig - value)^2, exact.  One thread per pixel row
+// of a range block, ordered like k_decode_paint (block row, pixel row, block column); the B row sums of a block meet in sse[j]
+// (zeroed by the launcher) through integer atomics, so the result does not depend on their order.  At most
+// 256 * 3 * 255^2 < 2^32 per block.
+// ---------------------------------------------------------------------------------------------
+template <typename Fmt, int B>
+__global__ __launch_bounds__(256) void k_leaf_sse(const typename Fmt::Px* __restrict__ image, const typename Fmt::Px* __restrict__ scaled,
                                                   const int32_t* __restrict__ qrows, const int32_t* __restrict__ iso,
                                                   uint32_t* __restrict__ sse, FicGeom g)
 {
@@ -57,21 +110,14 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const uint8_t* __restrict__ gr
     const int bx = t % g.Rw, row = t / g.Rw;
     const int ry = row % B, by = row / B;
     const int j = by * g.Rw + bx;
-    const int wloc = qrows[3 * j + 0];
-    const float a = __fdiv_rn((float)qrows[3 * j + 1], 100.0f);
-    const float b = (float)qrows[3 * j + 2];
+    const int32_t* q = qrows + Fmt::QW * (size_t)j;
+    const int wloc = q[0];
     const bool ok = wloc >= 0 && wloc < g.wK * g.wK;
     const int gi = ok ? window_to_global(g, j, wloc) : -1;
     if (gi < 0 || gi >= g.Nd) { atomicOr(&sse[j], 0xFFFFFFFFu); return; }   // never for an encoder's own rows: always split
-    int value[B];
-    qt_row_values<B>(scaled, g, gi, iso ? iso[j] : 0, ry, a, b, value);
-    const uint8_t* prow = gray + (size_t)row * g.W + bx * B;
-    uint32_t s = 0;
-#pragma unroll
-    for (int x = 0; x < B; x++) {
-        const int d = (int)prow[x] - value[x];
-        s += (uint32_t)(d * d);
-    }
+    int k = 0;
+    if constexpr (Fmt::kIso) k = iso ? iso[j] : 0;
+    const uint32_t s = qt_row_sse<B>(image + (size_t)row * g.W + bx * B, scaled, g, gi, k, ry, q + 1);
     if (s) atomicAdd(&sse[j], s);
 }
 
@@ -85,7 +131,7 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const uint8_t* __restrict__ gr
 // ---------------------------------------------------------------------------------------------
 struct FicQtLevels {
     const uint32_t* sse[3];
-    const int32_t* qrows[3];     // QW ints per range block (k_qt_scatter)
+    const int32_t* qrows[3];     // Fmt::QW ints per range block (k_qt_scatter)
     const int32_t* iso[3];       // NULL: n_iso = 1 (iso 0)
     int Rw[3];
     int nl;                      // levels
@@ -163,36 +209,100 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
     if (t == FIC_QT_SCAN_THREADS - 1) offs[n] = part[t];
 }
 
-// QW ints per quantised row, RW ints per leaf row: <3, 7> grey (the iso column follows the row), <5, 8> colour (no isometries)
-template <int QW, int RW>
+// Leaf rows of Fmt::QW + 3 ints, grey one more: the iso column follows the quantised row
+template <typename Fmt>
 __global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __restrict__ offs, int32_t* __restrict__ leaves)
 {
-    static_assert(RW == 3 + QW || RW == 4 + QW, "leaf row = {x, y, B} + quantised row [+ iso]");
+    constexpr int QW = Fmt::QW;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= L.Ntop) return;
     int o = offs[t];
     qt_walk(L, t, [&](int x, int y, int l) {
         const int B = L.B_max >> l;
         const int j = (y / B) * L.Rw[l] + x / B;
-        int32_t* r = leaves + RW * (size_t)o;
+        int32_t* r = leaves + Fmt::kLeafInts * (size_t)o;
         r[0] = x;
         r[1] = y;
         r[2] = B;
 #pragma unroll
         for (int k = 0; k < QW; k++) r[3 + k] = L.qrows[l][QW * j + k];
-        if constexpr (RW == 4 + QW) r[3 + QW] = L.iso[l] ? L.iso[l][j] : 0;
+        if constexpr (Fmt::kIso) r[3 + QW] = L.iso[l] ? L.iso[l][j] : 0;
         o++;
     });
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_decode_paint_leaves<B>: one decoder paint (FC:385-407) of the n leaves of side B in `lv`.  Each entry carries the leaf's
-// position, its global domain block (window_to_global of its level, resolved by the reader), its offset in `sqbuf` (the
-// prefix sum of B^2 over the leaves before it, so the squares lie in leaf order, pixel rows within a leaf) and its row.  One
-// thread per pixel row of a leaf; the exact integer sum of the squares goes to state->ssd[counter] like k_decode_paint's.
+// One pixel row of one decoder paint of leaf e, grey (FC:385-407): paints prow, stores the squared changes to srow, returns
+// their sum.
 // ---------------------------------------------------------------------------------------------
 template <int B>
-__global__ __launch_bounds__(256) void k_decode_paint_leaves(const uint8_t* __restrict__ scaled, uint8_t* __restrict__ image,
+__device__ __forceinline__ uint32_t qt_paint_row(uint8_t* __restrict__ prow, uint32_t* __restrict__ srow, const uint8_t* __restrict__ scaled,
+                                                 const FicGeom& g, const FicQtLeaf& e, int ry)
+{
+    uint32_t old[B / 4], neu[B / 4], sqv[B], sq = 0;
+    __builtin_memcpy(old, prow, B);
+    int value[B];
+    qt_row_values<B>(scaled, g, e.gi, e.q[2], ry, __fdiv_rn((float)e.q[0], 100.0f), (float)e.q[1], value);
+#pragma unroll
+    for (int q = 0; q < B / 4; q++) neu[q] = 0u;
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        const int dd = (int)((old[x >> 2] >> (8 * (x & 3))) & 0xffu) - value[x];
+        neu[x >> 2] |= (uint32_t)value[x] << (8 * (x & 3));
+        sqv[x] = (uint32_t)(dd * dd);
+        sq += sqv[x];
+    }
+    __builtin_memcpy(prow, neu, B);
+#pragma unroll
+    for (int q = 0; q < B / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
+    return sq;
+}
+
+// The same for decodeRGB (FC:458-499): the squares are dR^2 + dG^2 + dB^2 per pixel (FC:493).
+template <int B>
+__device__ __forceinline__ uint32_t qt_paint_row(int32_t* __restrict__ prow, uint32_t* __restrict__ srow, const int32_t* __restrict__ scaled,
+                                                 const FicGeom& g, const FicQtLeaf& e, int ry)
+{
+    const FicRgbCoef cf = rgb_row_coef(e.q[0], e.q[1], e.q[2], e.q[3]);
+    int32_t cur[B], dom[B];
+    uint32_t sqv[B], sq = 0;
+    __builtin_memcpy(cur, prow, 4 * B);
+    __builtin_memcpy(dom, rgb_domain_row(scaled, g, e.gi, ry), 4 * B);
+#pragma unroll
+    for (int x = 0; x < B; x++) {
+        int vR, vG, vB;
+        rgb_paint_px(cf, dom[x], vR, vG, vB);
+        sqv[x] = rgb_sq(cur[x], vR, vG, vB);
+        sq += sqv[x];
+        cur[x] = (int32_t)(0xff000000u | ((uint32_t)vR << 16) | ((uint32_t)vG << 8) | (uint32_t)vB);
+    }
+    __builtin_memcpy(prow, cur, 4 * B);
+    __builtin_memcpy(srow, sqv, 4 * B);
+    return sq;
+}
+
+// Adds the workgroup's (256 threads) sum of sq to *ssd: wave reduction, then one atomic per workgroup.
+__device__ __forceinline__ void qt_ssd_add(unsigned long long sq, unsigned long long* ssd)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    __shared__ unsigned long long s_part[4];
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+        if (tot) atomicAdd(ssd, tot);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_decode_paint_leaves<Fmt, B>: one decoder paint of the n leaves of side B in `lv`.  Each entry carries the leaf's position,
+// its global domain block (window_to_global of its level, resolved by the reader), its offset in `sqbuf` (the prefix sum of
+// B^2 over the leaves before it, so the squares lie in leaf order, pixel rows within a leaf) and its row.  One thread per pixel
+// row of a leaf; the exact integer sum of the squares goes to state->ssd[counter] like k_decode_paint's.
+// ---------------------------------------------------------------------------------------------
+template <typename Fmt, int B>
+__global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt::Px* __restrict__ scaled, typename Fmt::Px* __restrict__ image,
                                                              const FicQtLeaf* __restrict__ lv, int n, FicDecodeState* __restrict__ state,
                                                              uint32_t* __restrict__ sqbuf, int counter, FicGeom g)
 {
@@ -203,141 +313,30 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const uint8_t* __re
     if (t < n * B) {
         const FicQtLeaf e = lv[t / B];
         const int ry = t % B;
-        uint8_t* prow = image + (size_t)(e.y + ry) * g.W + e.x;
-        uint32_t* srow = sqbuf + (size_t)e.sqoff + (size_t)ry * B;
-        uint32_t old[B / 4], neu[B / 4], sqv[B];
-        __builtin_memcpy(old, prow, B);
-        int value[B];
-        qt_row_values<B>(scaled, g, e.gi, e.iso, ry, __fdiv_rn((float)e.qa, 100.0f), (float)e.qb, value);
-#pragma unroll
-        for (int q = 0; q < B / 4; q++) neu[q] = 0u;
-#pragma unroll
-        for (int x = 0; x < B; x++) {
-            const int dd = (int)((old[x >> 2] >> (8 * (x & 3))) & 0xffu) - value[x];
-            neu[x >> 2] |= (uint32_t)value[x] << (8 * (x & 3));
-            sqv[x] = (uint32_t)(dd * dd);
-            sq += sqv[x];
-        }
-        __builtin_memcpy(prow, neu, B);
-#pragma unroll
-        for (int q = 0; q < B / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
+        sq = qt_paint_row<B>(image + (size_t)(e.y + ry) * g.W + e.x, sqbuf + (size_t)e.sqoff + (size_t)ry * B, scaled, g, e, ry);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
-    __shared__ unsigned long long s_part[4];
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        if (tot) atomicAdd(&st->ssd[counter], tot);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Joint RGB (DESIGN.md 4.14).  The paint arithmetic of k_decode_paint_rgb (rgb_row_coef / rgb_paint_px, fic_devfn.h) on the
-// packed ARGB pixels; d is the domain pixel in the scaleImageRGB copy (FC:901-962), origin (c * B/4, r * B/4).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rgb_sq(int32_t cur, int vR, int vG, int vB)
-{
-    const int dR = ((cur >> 16) & 0xff) - vR, dG = ((cur >> 8) & 0xff) - vG, dB = (cur & 0xff) - vB;
-    return (uint32_t)(dR * dR + dG * dG + dB * dB);
-}
-
-// k_leaf_sse_rgb<B>: sse[j] = sum over the block's pixels and the channels R, G, B of (orig - value)^2, exact (at most
-// 256 * 3 * 255^2 < 2^32).  Work split and atomics as k_leaf_sse.
-template <int B>
-__global__ __launch_bounds__(256) void k_leaf_sse_rgb(const int32_t* __restrict__ argb, const int32_t* __restrict__ scaled,
-                                                      const int32_t* __restrict__ qrows5, uint32_t* __restrict__ sse, FicGeom g)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= g.Nr * B) return;
-    const int bx = t % g.Rw, row = t / g.Rw;
-    const int ry = row % B, by = row / B;
-    const int j = by * g.Rw + bx;
-    const int32_t* q = qrows5 + 5 * (size_t)j;
-    const int wloc = q[0];
-    const bool ok = wloc >= 0 && wloc < g.wK * g.wK;
-    const int gi = ok ? window_to_global(g, j, wloc) : -1;
-    if (gi < 0 || gi >= g.Nd) { atomicOr(&sse[j], 0xFFFFFFFFu); return; }   // never for an encoder's own rows: always split
-    const FicRgbCoef cf = rgb_row_coef(q[1], q[2], q[3], q[4]);
-    const int c = gi % g.Dw, r = gi / g.Dw;
-    const int32_t* drow = scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
-    const int32_t* prow = argb + (size_t)row * g.W + bx * B;
-    uint32_t s = 0;
-#pragma unroll
-    for (int x = 0; x < B; x++) {
-        int vR, vG, vB;
-        rgb_paint_px(cf, drow[x], vR, vG, vB);
-        s += rgb_sq(prow[x], vR, vG, vB);
-    }
-    if (s) atomicAdd(&sse[j], s);
-}
-
-// k_decode_paint_leaves_rgb<B>: one decodeRGB paint (FC:458-499) of the n leaves of side B in `lv`, entries as in
-// k_decode_paint_leaves.  One thread per pixel row of a leaf; sqbuf gets dR^2 + dG^2 + dB^2 per pixel (FC:493) at the leaf's
-// offset, the exact integer sum goes to state->ssd[counter].
-template <int B>
-__global__ __launch_bounds__(256) void k_decode_paint_leaves_rgb(const int32_t* __restrict__ scaled, int32_t* __restrict__ image,
-                                                                 const FicQtLeafRgb* __restrict__ lv, int n,
-                                                                 FicDecodeState* __restrict__ state, uint32_t* __restrict__ sqbuf,
-                                                                 int counter, FicGeom g)
-{
-    FicDecodeState* st = state;
-    if (st->done) return;                                  // uniform
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    unsigned long long sq = 0;
-    if (t < n * B) {
-        const FicQtLeafRgb e = lv[t / B];
-        const int ry = t % B;
-        int32_t* prow = image + (size_t)(e.y + ry) * g.W + e.x;
-        uint32_t* srow = sqbuf + (size_t)e.sqoff + (size_t)ry * B;
-        const int c = e.gi % g.Dw, r = e.gi / g.Dw;
-        const int32_t* drow = scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
-        const FicRgbCoef cf = rgb_row_coef(e.q1, e.q2, e.q3, e.q4);
-        int32_t cur[B], dom[B];
-        uint32_t sqv[B];
-        __builtin_memcpy(cur, prow, 4 * B);
-        __builtin_memcpy(dom, drow, 4 * B);
-#pragma unroll
-        for (int x = 0; x < B; x++) {
-            int vR, vG, vB;
-            rgb_paint_px(cf, dom[x], vR, vG, vB);
-            sqv[x] = rgb_sq(cur[x], vR, vG, vB);
-            sq += sqv[x];
-            cur[x] = (int32_t)(0xff000000u | ((uint32_t)vR << 16) | ((uint32_t)vG << 8) | (uint32_t)vB);
-        }
-        __builtin_memcpy(prow, cur, 4 * B);
-        __builtin_memcpy(srow, sqv, 4 * B);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
-    __shared__ unsigned long long s_part[4];
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        if (tot) atomicAdd(&st->ssd[counter], tot);
-    }
+    qt_ssd_add(sq, &st->ssd[counter]);
 }
 
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
-int fic_launch_leaf_sse(const uint8_t* gray, const uint8_t* scaled, const int32_t* qrows, const int32_t* iso, uint32_t* sse,
-                        const FicGeom& g, hipStream_t s)
+template <typename Fmt>
+int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* scaled, const int32_t* qrows, const int32_t* iso,
+                        uint32_t* sse, const FicGeom& g, hipStream_t s)
 {
     if (hipMemsetAsync(sse, 0, (size_t)g.Nr * sizeof(uint32_t), s) != hipSuccess) return -1;
-    auto k = g.B == 4 ? k_leaf_sse<4> : (g.B == 8 ? k_leaf_sse<8> : k_leaf_sse<16>);
-    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, gray, scaled, qrows, iso, sse, g);
+    auto k = g.B == 4 ? k_leaf_sse<Fmt, 4> : (g.B == 8 ? k_leaf_sse<Fmt, 8> : k_leaf_sse<Fmt, 16>);
+    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, image, scaled, qrows, iso, sse, g);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
+template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s, int qw)
+                          hipStream_t s)
 {
-    if (qw != 3 && qw != 5) return (int)hipErrorInvalidValue;
     FicQtLevels L{};
     for (int l = 0; l < nl; l++) {
         L.sse[l] = sse[l];
@@ -356,39 +355,29 @@ int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrow
     hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, Ntop);
     FIC_LAUNCH_CHECK();
     if (leaves) {
-        auto k = qw == 3 ? k_qt_scatter<3, 7> : k_qt_scatter<5, 8>;
-        hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
+        hipLaunchKernelGGL(k_qt_scatter<Fmt>, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
         FIC_LAUNCH_CHECK();
     }
     return 0;
 }
 
-int fic_launch_decode_paint_leaves(const uint8_t* scaled, uint8_t* image, const FicQtLeaf* lv, int n, FicDecodeState* state,
-                                   uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
+template <typename Fmt>
+int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const FicQtLeaf* lv, int n,
+                                   FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
 {
     if (n <= 0) return 0;
-    auto k = g.B == 4 ? k_decode_paint_leaves<4> : (g.B == 8 ? k_decode_paint_leaves<8> : k_decode_paint_leaves<16>);
+    auto k = g.B == 4 ? k_decode_paint_leaves<Fmt, 4> : (g.B == 8 ? k_decode_paint_leaves<Fmt, 8> : k_decode_paint_leaves<Fmt, 16>);
     hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-int fic_launch_leaf_sse_rgb(const int32_t* argb, const int32_t* scaled, const int32_t* qrows5, uint32_t* sse, const FicGeom& g,
-                            hipStream_t s)
-{
-    if (hipMemsetAsync(sse, 0, (size_t)g.Nr * sizeof(uint32_t), s) != hipSuccess) return -1;
-    auto k = g.B == 4 ? k_leaf_sse_rgb<4> : (g.B == 8 ? k_leaf_sse_rgb<8> : k_leaf_sse_rgb<16>);
-    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, argb, scaled, qrows5, sse, g);
-    FIC_LAUNCH_CHECK();
-    return 0;
-}
-
-int fic_launch_decode_paint_leaves_rgb(const int32_t* scaled, int32_t* image, const FicQtLeafRgb* lv, int n, FicDecodeState* state,
-                                       uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
-{
-    if (n <= 0) return 0;
-    auto k = g.B == 4 ? k_decode_paint_leaves_rgb<4> : (g.B == 8 ? k_decode_paint_leaves_rgb<8> : k_decode_paint_leaves_rgb<16>);
-    hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
-    FIC_LAUNCH_CHECK();
-    return 0;
-}
+#define FIC_QT_INSTANTIATE(Fmt)                                                                                                       \
+    template int fic_launch_leaf_sse<Fmt>(const Fmt::Px*, const Fmt::Px*, const int32_t*, const int32_t*, uint32_t*, const FicGeom&,  \
+                                          hipStream_t);                                                                               \
+    template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \
+                                            int, int, int, float, int*, int*, int32_t*, hipStream_t);                                 \
+    template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const FicQtLeaf*, int, FicDecodeState*, uint32_t*,     \
+                                                     int, const FicGeom&, hipStream_t);
+FIC_QT_INSTANTIATE(QtGrey)
+FIC_QT_INSTANTIATE(QtRgb)
