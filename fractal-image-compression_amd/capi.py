@@ -126,6 +126,11 @@ def lib():
         "fic_write_run_rgb_quadtree": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
         "fic_decode_rgb_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
         "fic_debug_rgb_quadtree_sse": (C.c_int, [i32p] + [C.c_int] * 6 + [C.POINTER(C.c_uint32), C.c_int64]),
+        "fic_decode_gray_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_decode_rgb_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_decode_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_decode_rgb_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_ctx_decode_zoom_host": (C.c_int, [vp, C.c_int, u8p, f32p, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -166,9 +171,33 @@ def geometry(w, h, B):
     return tuple(x.value for x in v)
 
 
-def decode_gray_run(run, device=0, avg_error_in=0.0):
+def _decode_run_zoom(fn, run, header_bytes, what, dtype, device, avg_error_in, zoom):
+    """One stream decoder of the C ABI at `zoom`: (pixels [zoom*h * zoom*w] of dtype, avgError float32, iterations, zoom*w,
+    zoom*h).  The output is sized from the header; the library checks everything else."""
+    buf = np.frombuffer(bytes(run), np.uint8)
+    if buf.size < header_bytes:
+        raise FicError(-3, f"{what} shorter than its header")
+    z = int(zoom)
+    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
+    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
+    cap = max(w, 0) * max(h, 0) * (z * z if z in (1, 2, 4) else 1)
+    if cap >= 2 ** 31:                  # the library refuses the size (FIC_E_GEOMETRY) before it looks at the buffer
+        cap = 0
+    out = np.zeros(max(cap, 1), dtype)
+    avg = C.c_float(avg_error_in)
+    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
+    check(fn(ptr(buf, C.c_uint8), buf.size, z, device, ptr(out, C.c_uint8 if dtype == np.uint8 else C.c_int32), cap, C.byref(wo),
+             C.byref(ho), C.byref(avg), C.byref(it)))
+    return out[:cap], np.float32(avg.value), it.value, wo.value, ho.value
+
+
+def decode_gray_run(run, device=0, avg_error_in=0.0, zoom=1):
     """FractalCompression.decode on a grey .run stream (FC:547-553, 356-421), on the GPU.
-    Returns (gray uint8 [H,W], avgError float32 after the call, iterations)."""
+    Returns (gray uint8 [H,W], avgError float32 after the call, iterations).  zoom = 2 / 4: the same loop on the geometry
+    (zoom*w, zoom*h, zoom*B, wK), [zoom*H, zoom*W] out (fic_decode_gray_run_zoom)."""
+    if zoom != 1:
+        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_gray_run_zoom, run, 20, "run stream", np.uint8, device, avg_error_in, zoom)
+        return out.reshape(h, w), avg, it
     buf = np.frombuffer(bytes(run), np.uint8)
     if buf.size < 20:
         raise FicError(-3, "run stream shorter than its header")
@@ -225,9 +254,12 @@ def release_cache():
     lib().fic_release_cache()
 
 
-def decode_rgb_run(run, device=0, avg_error_in=0.0):
-    """decodeRGB (FC:430-508) on the GPU.  Returns (argb int32 [H*W], avgError float32, iterations, w, h)."""
+def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):
+    """decodeRGB (FC:430-508) on the GPU.  Returns (argb int32 [H*W], avgError float32, iterations, w, h); zoom = 2 / 4: at the
+    zoomed size (fic_decode_rgb_run_zoom)."""
     L = lib()
+    if zoom != 1:
+        return _decode_run_zoom(L.fic_decode_rgb_run_zoom, run, 20, "run stream", np.int32, device, avg_error_in, zoom)
     L.fic_decode_rgb_run.restype = C.c_int
     L.fic_decode_rgb_run.argtypes = [C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int64,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]
@@ -439,9 +471,13 @@ def write_run_quadtree(leaves, w, h, B_max, B_min, wK, n_iso):
     return out.tobytes()
 
 
-def decode_quadtree_run(run, device=0, avg_error_in=0.0):
+def decode_quadtree_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a quadtree stream on the GPU (fic_decode_quadtree_run).  Returns (gray uint8 [H,W], avgError float32 after the
-    call, iterations)."""
+    call, iterations).  zoom = 2 / 4: every leaf {x, y, B} painted as {zoom*x, zoom*y, zoom*B} (fic_decode_quadtree_run_zoom)."""
+    if zoom != 1:
+        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_quadtree_run_zoom, run, 32, "quadtree stream", np.uint8, device,
+                                              avg_error_in, zoom)
+        return out.reshape(h, w), avg, it
     buf = np.frombuffer(bytes(run), np.uint8)
     if buf.size < 32:
         raise FicError(-3, "quadtree stream shorter than its header")
@@ -504,9 +540,13 @@ def write_run_rgb_quadtree(leaves, w, h, B_max, B_min, wK):
     return out.tobytes()
 
 
-def decode_rgb_quadtree_run(run, device=0, avg_error_in=0.0):
+def decode_rgb_quadtree_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a colour quadtree stream on the GPU (fic_decode_rgb_quadtree_run).  Returns (argb int32 [H, W], avgError
-    float32 after the call, iterations)."""
+    float32 after the call, iterations).  zoom = 2 / 4: at the zoomed size (fic_decode_rgb_quadtree_run_zoom)."""
+    if zoom != 1:
+        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_rgb_quadtree_run_zoom, run, 32, "colour quadtree stream", np.int32,
+                                              device, avg_error_in, zoom)
+        return out.reshape(h, w), avg, it
     buf = np.frombuffer(bytes(run), np.uint8)
     if buf.size < 32:
         raise FicError(-3, "colour quadtree stream shorter than its header")

@@ -36,10 +36,10 @@ static int ilog2(int v)
     return l;
 }
 
-// Geometry as the reference derives it (FC:111-116, FC:1019-1022) + what it needs to not throw.
-int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* out)
+// Geometry as the reference derives it (FC:111-116, FC:1019-1022) + what it needs to not throw.  B_top: the largest side taken.
+static int geometry_for(int w, int h, int B, int wK, int n_iso, int planes, int B_top, FicGeom* out)
 {
-    if (B != 4 && B != 8 && B != 16)
+    if (B != 4 && B != 8 && B != 16 && !(B_top >= B && (B == 32 || B == 64)))
         return fail(FIC_E_GEOMETRY, "blockgroesse B=%d unsupported (GUI values 4, 8, 16; B=2 divides by zero at FC:1022)", B);
     if (w <= 0 || h <= 0 || (w % 2) || (h % 2))
         return fail(FIC_E_GEOMETRY, "image %dx%d: width and height must be positive and even (scaleImage FC:970-1007 overruns otherwise)", w, h);
@@ -73,6 +73,18 @@ int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* o
     g.full = (wK == g.Dw && wK == g.Dh) ? 1 : 0;
     *out = g;
     return FIC_OK;
+}
+
+int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* out) { return geometry_for(w, h, B, wK, n_iso, planes, 16, out); }
+
+// The geometry (zoom * w, zoom * h, zoom * B, wK) a stream of the valid geometry (w, h, B, wK) decodes on at zoom 1, 2 or 4:
+// the same block counts, so every row keeps its meaning.  The sides 32 and 64 exist for the decoders only.
+int make_decode_geometry(int w, int h, int B, int wK, int n_iso, int planes, int zoom, FicGeom* out)
+{
+    if (zoom != 1 && zoom != 2 && zoom != 4) return fail(FIC_E_ARGUMENT, "zoom=%d: only 1, 2 or 4", zoom);
+    if ((long long)w * zoom >= 0x7FFFFFFFll || (long long)h * zoom >= 0x7FFFFFFFll)
+        return fail(FIC_E_GEOMETRY, "image %dx%d at zoom %d too large for 32-bit candidate indices", w, h, zoom);
+    return geometry_for(w * zoom, h * zoom, B * zoom, wK, n_iso, planes, 64, out);
 }
 
 }  // namespace ficd

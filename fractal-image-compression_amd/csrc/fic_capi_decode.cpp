@@ -116,11 +116,38 @@ static int run_decode_loop(const FicGeom& g, uint8_t* d_scaled, uint8_t* d_image
     });
 }
 
-int fic_ctx_decode_host(fic_ctx* c, uint8_t* gray_out, float* avg_error_out, int* iterations_out)
+int fic_ctx_decode_zoom_host(fic_ctx* c, int zoom, uint8_t* gray_out, float* avg_error_out, int* iterations_out)
 {
     if (!c || !gray_out) return fail(FIC_E_ARGUMENT, "fic_ctx_decode_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->encoded_any) return fail(FIC_E_STATE, "fic_ctx_decode_host: nothing encoded yet");
+    const int32_t* d_iso = c->g.n_iso > 1 ? c->o.iso : nullptr;
+    if (zoom != 1) {
+        // the context's own scratch holds the encoded size: a zoomed decode takes an arena of the zoomed size instead
+        FicGeom g;
+        int rc = make_decode_geometry(c->g.W, c->g.H, c->g.B, c->g.wK, c->g.n_iso, c->g.planes, zoom, &g);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t P = (size_t)g.planes, npix = P * g.W * g.H;
+        const size_t o_scaled = 0, o_image = o_scaled + align256(P * g.Ws * g.Hs), o_state = o_image + align256(npix),
+                     o_sq = o_state + align256(P * sizeof(FicDecodeState)),
+                     total = o_sq + align256(fic_decode_sq_words(P, (size_t)g.W * g.H) * 4);
+        Arena ar;
+        rc = arena_take(c->device, total, &ar);
+        if (rc) return rc;
+        hipError_t e = hipStreamSynchronize(c->last_stream);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_ctx_decode_zoom_host: %s", hipGetErrorString(e));
+        if (rc == FIC_OK)
+            rc = run_decode_loop(g, (uint8_t*)(ar.base + o_scaled), (uint8_t*)(ar.base + o_image), c->o.qrows, d_iso,
+                                 (FicDecodeState*)(ar.base + o_state), (uint32_t*)(ar.base + o_sq), nullptr, avg_error_out, iterations_out,
+                                 nullptr, c->last_stream);
+        if (rc == FIC_OK) {
+            e = hipMemcpy(gray_out, ar.base + o_image, npix, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_ctx_decode_zoom_host: %s", hipGetErrorString(e));
+        }
+        arena_give(ar);
+        return rc;
+    }
     HIP_TRY(hipSetDevice(c->device));
     const FicGeom& g = c->g;
     size_t npix = (size_t)g.planes * g.W * g.H;
@@ -128,23 +155,31 @@ int fic_ctx_decode_host(fic_ctx* c, uint8_t* gray_out, float* avg_error_out, int
     if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, (size_t)g.planes); if (rc) return rc; }
     if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words((size_t)g.planes, (size_t)g.W * g.H)); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(c->last_stream));
-    int rc = run_decode_loop(g, c->b.scaled, c->decoded, c->o.qrows, g.n_iso > 1 ? c->o.iso : nullptr, c->dec_state, c->dec_sq,
+    int rc = run_decode_loop(g, c->b.scaled, c->decoded, c->o.qrows, d_iso, c->dec_state, c->dec_sq,
                              nullptr, avg_error_out, iterations_out, nullptr, c->last_stream);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(gray_out, c->decoded, npix, hipMemcpyDeviceToHost));
     return FIC_OK;
 }
 
-static int decode_gray_run_impl(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
+int fic_ctx_decode_host(fic_ctx* c, uint8_t* gray_out, float* avg_error_out, int* iterations_out)
+{
+    return fic_ctx_decode_zoom_host(c, 1, gray_out, avg_error_out, iterations_out);
+}
+
+// The header's geometry (w, h, B, wK) must be one the encoders take; the decode runs on it times `zoom` (make_decode_geometry).
+static int decode_gray_run_impl(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
                                 int* h_out, float* avg_error_io, int* iterations, int* seq_sums)
 {
     if (!run || len < 20) return fail(FIC_E_ARGUMENT, "fic_decode_gray_run: stream shorter than the 20-byte header");
     if (get_be32(run) != 0)
         return fail(FIC_E_NOT_GREY, "fic_decode_gray_run: isRGB = %d (FC:548-552 dispatches to decodeRGB)", get_be32(run));
-    const int w = get_be32(run + 4), h = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
+    const int w0 = get_be32(run + 4), h0 = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
     FicGeom g;
-    int rc = make_geometry(w, h, B, wK, 1, 1, &g);
+    int rc = make_geometry(w0, h0, B, wK, 1, 1, &g);
+    if (rc == FIC_OK) rc = make_decode_geometry(w0, h0, B, wK, 1, 1, zoom, &g);
     if (rc) return rc;
+    const int w = g.W, h = g.H;
     if (w_out) *w_out = w;
     if (h_out) *h_out = h;
     if (len < 20 + 12 * (int64_t)g.Nr)
@@ -177,10 +212,16 @@ static int decode_gray_run_impl(const uint8_t* run, int64_t len, int device, uin
     return rc;
 }
 
+int fic_decode_gray_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
+                             int* h_out, float* avg_error_io, int* iterations)
+{
+    return decode_gray_run_impl(run, len, zoom, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations, nullptr);
+}
+
 int fic_decode_gray_run(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
                         int* h_out, float* avg_error_io, int* iterations)
 {
-    return decode_gray_run_impl(run, len, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations, nullptr);
+    return fic_decode_gray_run_zoom(run, len, 1, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations);
 }
 
 // Test hook: the decoder's reproduction of Java's `avgError += (float) v[i]` loop (FC:407) on arbitrary values.
@@ -218,19 +259,21 @@ int fic_debug_float_sum_fallbacks(void) { return g_last_sum_fallbacks; }
 int fic_debug_decode_gray_run(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity,
                               float* avg_error_io, int* iterations, int* seq_sums)
 {
-    return decode_gray_run_impl(run, len, device, gray_out, capacity, nullptr, nullptr, avg_error_io, iterations, seq_sums);
+    return decode_gray_run_impl(run, len, 1, device, gray_out, capacity, nullptr, nullptr, avg_error_io, iterations, seq_sums);
 }
 
 // ---- decodeRGB (FC:430-508) -----------------------------------------------------------------------
-int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* argb_out, int64_t capacity_pixels,
-                       int* w_out, int* h_out, float* avg_error_io, int* iterations)
+int fic_decode_rgb_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out, int64_t capacity_pixels,
+                            int* w_out, int* h_out, float* avg_error_io, int* iterations)
 {
     if (!run || len < 20) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: stream shorter than the 20-byte header");
     if (get_be32(run) == 0) return fail(FIC_E_ARGUMENT, "fic_decode_rgb_run: isRGB = 0 (FC:548-550 dispatches to decodeGreyScale)");
-    const int w = get_be32(run + 4), h = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
+    const int w0 = get_be32(run + 4), h0 = get_be32(run + 8), B = get_be32(run + 12), wK = get_be32(run + 16);
     FicGeom g;
-    int rc = make_geometry(w, h, B, wK, 1, 1, &g);
+    int rc = make_geometry(w0, h0, B, wK, 1, 1, &g);
+    if (rc == FIC_OK) rc = make_decode_geometry(w0, h0, B, wK, 1, 1, zoom, &g);
     if (rc) return rc;
+    const int w = g.W, h = g.H;
     if (w_out) *w_out = w;
     if (h_out) *h_out = h;
     if (len < 20 + 20 * (int64_t)g.Nr)
@@ -267,6 +310,12 @@ int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* arg
     if (rc == FIC_OK && avg_error_io) *avg_error_io = avg;
     arena_give(ar);
     return rc;
+}
+
+int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* argb_out, int64_t capacity_pixels,
+                       int* w_out, int* h_out, float* avg_error_io, int* iterations)
+{
+    return fic_decode_rgb_run_zoom(run, len, 1, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
 }
 
 }  // extern "C"

@@ -270,9 +270,10 @@ int64_t qt_write_run(const int32_t* leaves, int n_leaves, int w, int h, int B_ma
 }
 
 // The stream reader and decoder: the leaves of every level resolved once on the host, then the decoder's loop with one paint
-// per level and iteration.
+// per level and iteration.  zoom: every leaf {x, y, B} is painted as {zoom x, zoom y, zoom B} on the level's geometry times
+// zoom (make_decode_geometry; the same block counts, so idx_local keeps its meaning), in the same stream order.
 template <typename Fmt>
-int qt_decode_run(const uint8_t* run, int64_t len, int device, typename Fmt::Px* out, int64_t capacity_pixels, int* w_out, int* h_out,
+int qt_decode_run(const uint8_t* run, int64_t len, int zoom, int device, typename Fmt::Px* out, int64_t capacity_pixels, int* w_out, int* h_out,
                   float* avg_error_io, int* iterations)
 {
     using Px = typename Fmt::Px;
@@ -282,10 +283,16 @@ int qt_decode_run(const uint8_t* run, int64_t len, int device, typename Fmt::Px*
     QtHeader H;
     int rc = Fmt::unpack(hd, &H);
     if (rc) return rc;
-    const int w = H.w, h = H.h, n = H.n;
-    QtLevels L;
-    rc = qt_levels(w, h, H.B_max, H.B_min, H.wK, H.n_iso, &L);
+    const int n = H.n;
+    QtLevels L, Z;                                     // the stream's levels and the same at `zoom`, where the paint runs
+    rc = qt_levels(H.w, H.h, H.B_max, H.B_min, H.wK, H.n_iso, &L);
     if (rc) return Fmt::levels_refused(rc);
+    Z.nl = L.nl;
+    for (int l = 0; l < L.nl; l++) {
+        rc = make_decode_geometry(H.w, H.h, L.g[l].B, L.g[l].wK, H.n_iso, 1, zoom, &Z.g[l]);
+        if (rc) return rc;
+    }
+    const int w = Z.g[0].W, h = Z.g[0].H;
     if (n < 1 || n > L.g[L.nl - 1].Nr) return fail(FIC_E_ARGUMENT, "%s: %d leaves", Fmt::kReader, n);
     const int per = Fmt::run_ints(H.n_iso);
     const int64_t need = 4 * (kQtHeaderInts + per * (int64_t)n);
@@ -298,25 +305,25 @@ int qt_decode_run(const uint8_t* run, int64_t len, int device, typename Fmt::Px*
         const FicGeom& g = L.g[l];
         const uint8_t* r = rows + 4 * per * (size_t)i;
         const int idx = get_be32(r + 4);
-        FicQtLeaf e{x, y, 0, sqoff, {0, 0, 0, 0}};
+        FicQtLeaf e{zoom * x, zoom * y, 0, sqoff, {0, 0, 0, 0}};
         for (int k = 2; k < per; k++) e.q[k - 2] = get_be32(r + 4 * k);
         if (idx < 0 || idx >= g.wK * g.wK || (Fmt::kIso && (e.q[2] < 0 || e.q[2] >= H.n_iso))) return false;
         e.gi = host_window_to_global(g, (y / g.B) * g.Rw + x / g.B, idx);
         if (e.gi < 0 || e.gi >= g.Nd) return false;
         lv[l].push_back(e);
-        sqoff += g.n;
+        sqoff += Z.g[l].n;
         return true;
     });
     if (!ok)
         return fail(FIC_E_ARGUMENT, "%s: the leaf sizes do not tile the %dx%d image with levels %d..%d, or a leaf's domain index%s is "
-                                    "out of range", Fmt::kReader, w, h, H.B_max, H.B_min, Fmt::kIso ? " / isometry" : "");
+                                    "out of range", Fmt::kReader, H.w, H.h, H.B_max, H.B_min, Fmt::kIso ? " / isometry" : "");
     if (w_out) *w_out = w;
     if (h_out) *h_out = h;
     const size_t npix = (size_t)w * h;
     if (!out || capacity_pixels < (int64_t)npix) return fail(FIC_E_CAPACITY, "%s: output needs %zu pixels", Fmt::kReader, npix);
     rc = check_device(device);
     if (rc) return rc;
-    const FicGeom& g0 = L.g[0];
+    const FicGeom& g0 = Z.g[0];
     size_t o_lv[kQtMaxLevels];
     const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g0.Ws * g0.Hs * sizeof(Px));
     size_t off = o_image + align256(npix * sizeof(Px));
@@ -341,7 +348,7 @@ int qt_decode_run(const uint8_t* run, int64_t len, int device, typename Fmt::Px*
             if (Fmt::scale(d_image, d_scaled, g0)) return -1;
             for (int l = 0; l < L.nl; l++)
                 if (fic_launch_decode_paint_leaves<typename Fmt::Dev>(d_scaled, d_image, (const FicQtLeaf*)(ar.base + o_lv[l]),
-                                                                      (int)lv[l].size(), d_state, d_sq, counter, L.g[l], nullptr))
+                                                                      (int)lv[l].size(), d_state, d_sq, counter, Z.g[l], nullptr))
                     return -1;
             return fic_launch_decode_step(d_state, d_sq, counter, (int)npix, 1, nullptr);
         });
@@ -385,10 +392,16 @@ int64_t fic_write_run_quadtree(const int32_t* leaves, int n_leaves, int w, int h
     return qt_write_run<QtGreyHost>(leaves, n_leaves, w, h, B_max, B_min, wK, n_iso, out, capacity);
 }
 
+int fic_decode_quadtree_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
+                                 int* h_out, float* avg_error_io, int* iterations)
+{
+    return qt_decode_run<QtGreyHost>(run, len, zoom, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations);
+}
+
 int fic_decode_quadtree_run(const uint8_t* run, int64_t len, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
                             int* h_out, float* avg_error_io, int* iterations)
 {
-    return qt_decode_run<QtGreyHost>(run, len, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations);
+    return fic_decode_quadtree_run_zoom(run, len, 1, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations);
 }
 
 int fic_encode_rgb_quadtree_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold, int device,
@@ -411,10 +424,16 @@ int64_t fic_write_run_rgb_quadtree(const int32_t* leaves, int n_leaves, int w, i
     return qt_write_run<QtRgbHost>(leaves, n_leaves, w, h, B_max, B_min, wK, 1, out, capacity);
 }
 
+int fic_decode_rgb_quadtree_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out, int64_t capacity_pixels,
+                                     int* w_out, int* h_out, float* avg_error_io, int* iterations)
+{
+    return qt_decode_run<QtRgbHost>(run, len, zoom, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
+}
+
 int fic_decode_rgb_quadtree_run(const uint8_t* run, int64_t len, int device, int32_t* argb_out, int64_t capacity_pixels, int* w_out,
                                 int* h_out, float* avg_error_io, int* iterations)
 {
-    return qt_decode_run<QtRgbHost>(run, len, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
+    return fic_decode_rgb_quadtree_run_zoom(run, len, 1, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
 }
 
 }  // extern "C"

@@ -24,22 +24,26 @@
 //            (kept in `sqbuf` in Java's visiting order) exactly as FC:407 does, one float add per pixel in that order
 //            (java_float_sum: a parallel scan over parity-dependent rounding maps, same bits as the sequential loop).
 // ---------------------------------------------------------------------------------------------
-// One thread = one pixel ROW of one range block (B pixels): the codebook row, its fit and its domain block are looked up once
-// per B pixels, the image row is one B-byte load + store, the squares one contiguous run of `sqbuf`.  Threads are ordered
-// (block row, pixel row, block column): neighbours in a wave touch neighbouring bytes of the same image row.
+// One thread = one SEGMENT of a pixel row of one range block: S = min(B, 16) pixels, B / S segments per row (one up to
+// B = 16; 2 and 4 at the decode-only sides 32 and 64 of a zoomed decode, DESIGN.md 4.15, where a whole row would not fit a
+// thread's registers).  The codebook row, its fit and its domain block are looked up once per S pixels, the image segment is
+// one S-byte load + store, the squares one contiguous run of `sqbuf`.  Threads are ordered (block row, pixel row, block
+// column, segment): neighbours in a wave touch neighbouring bytes of the same image row.
 template <int B>
 __global__ __launch_bounds__(256) void k_decode_paint(const uint8_t* __restrict__ scaled, uint8_t* __restrict__ image,
                                                       const int32_t* __restrict__ qrows, const int32_t* __restrict__ iso,
                                                       FicDecodeState* __restrict__ state, uint32_t* __restrict__ sqbuf,
                                                       int counter, FicGeom g)
 {
+    constexpr int S = B < 16 ? B : 16, NS = B / S;
     const int plane = blockIdx.y;
     FicDecodeState* st = state + plane;
     if (st->done) return;                                  // uniform per plane
-    const int t = blockIdx.x * 256 + threadIdx.x;          // (by * B + ry) * Rw + bx
+    const int t = blockIdx.x * 256 + threadIdx.x;          // ((by * B + ry) * Rw + bx) * NS + seg
     unsigned long long sq = 0;
-    if (t < g.Nr * B) {
-        const int bx = t % g.Rw, row = t / g.Rw;           // row = by * B + ry = the image row
+    if (t < g.Nr * B * NS) {
+        const int x0 = (t % NS) * S, u = t / NS;           // x0: the segment's first pixel in the block row
+        const int bx = u % g.Rw, row = u / g.Rw;           // row = by * B + ry = the image row
         const int ry = row % B, by = row / B;
         const int j = by * g.Rw + bx;
         const size_t o = (size_t)plane * g.Nr + j;
@@ -48,32 +52,32 @@ __global__ __launch_bounds__(256) void k_decode_paint(const uint8_t* __restrict_
         const float b = (float)qrows[3 * o + 2];
         const bool ok = wloc >= 0 && wloc < g.wK * g.wK;
         const int gi = ok ? window_to_global(g, j, wloc) : 0;
-        uint8_t* prow = image + (size_t)plane * g.W * g.H + (size_t)row * g.W + bx * B;
-        uint32_t* srow = sqbuf + (size_t)plane * g.W * g.H + ((size_t)j * B + ry) * B;   // Java's visiting order (FC:385-389)
-        uint32_t old[B / 4], neu[B / 4], sqv[B];
-        __builtin_memcpy(old, prow, B);
+        uint8_t* prow = image + (size_t)plane * g.W * g.H + (size_t)row * g.W + bx * B + x0;
+        uint32_t* srow = sqbuf + (size_t)plane * g.W * g.H + ((size_t)j * B + ry) * B + x0;   // Java's visiting order (FC:385-389)
+        uint32_t old[S / 4], neu[S / 4], sqv[S];
+        __builtin_memcpy(old, prow, S);
         if (!ok || gi < 0 || gi >= g.Nd) {
             st->bad_index = 1;                             // Java: ArrayIndexOutOfBoundsException at FC:394
 #pragma unroll
-            for (int x = 0; x < B; x++) sqv[x] = 0u;
+            for (int x = 0; x < S; x++) sqv[x] = 0u;
         } else {
             const int c = gi % g.Dw, r = gi / g.Dw;
             const uint8_t* dom = scaled + (size_t)plane * g.Ws * g.Hs + (size_t)(r * g.abstand) * g.Ws + c * g.abstand;
-            uint8_t dpx[B];
+            uint8_t dpx[S];
             const int k = iso ? iso[o] : 0;
             if (k == 0) {
-                __builtin_memcpy(dpx, dom + (size_t)ry * g.Ws, B);       // the block's row ry: B consecutive scaled pixels
+                __builtin_memcpy(dpx, dom + (size_t)ry * g.Ws + x0, S);  // the block's row ry: S consecutive scaled pixels
             } else {
                 int ax, bx_, cx, ay, by_, cy;
                 iso_affine(k, B - 1, ax, bx_, cx, ay, by_, cy);          // source (sx, sy) = (ax x + bx y + cx, ay x + by y + cy)
-                const int s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry, sx = ay * g.Ws + ax;
+                const int sx = ay * g.Ws + ax, s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry + sx * x0;
 #pragma unroll
-                for (int x = 0; x < B; x++) dpx[x] = dom[s0 + sx * x];
+                for (int x = 0; x < S; x++) dpx[x] = dom[s0 + sx * x];
             }
 #pragma unroll
-            for (int q = 0; q < B / 4; q++) neu[q] = 0u;
+            for (int q = 0; q < S / 4; q++) neu[q] = 0u;
 #pragma unroll
-            for (int x = 0; x < B; x++) {
+            for (int x = 0; x < S; x++) {
                 int value = java_f2i(__fadd_rn(__fmul_rn(a, (float)dpx[x]), b));
                 value = value < 0 ? 0 : (value > 255 ? 255 : value);
                 const int dd = (int)((old[x >> 2] >> (8 * (x & 3))) & 0xffu) - value;
@@ -81,10 +85,10 @@ __global__ __launch_bounds__(256) void k_decode_paint(const uint8_t* __restrict_
                 sqv[x] = (uint32_t)(dd * dd);
                 sq += sqv[x];
             }
-            __builtin_memcpy(prow, neu, B);
+            __builtin_memcpy(prow, neu, S);
         }
 #pragma unroll
-        for (int q = 0; q < B / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
+        for (int q = 0; q < S / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
@@ -576,8 +580,10 @@ int fic_launch_decode_iteration(uint8_t* scaled, uint8_t* image, const int32_t* 
                                 FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
 {
     if (fic_launch_scale(image, scaled, g, s)) return -1;      // FC:382 -> createCodebuch -> scaleImage
-    auto paint = g.B == 4 ? k_decode_paint<4> : (g.B == 8 ? k_decode_paint<8> : k_decode_paint<16>);
-    hipLaunchKernelGGL(paint, dim3((g.Nr * g.B + 255) / 256, g.planes), dim3(256), 0, s, scaled, image, qrows, iso,
+    auto paint = g.B == 4 ? k_decode_paint<4> : (g.B == 8 ? k_decode_paint<8> : (g.B == 16 ? k_decode_paint<16> :
+                 (g.B == 32 ? k_decode_paint<32> : k_decode_paint<64>)));      // 32, 64: zoomed decodes only
+    const int threads = g.W / (g.B < 16 ? g.B : 16) * g.H;                    // one per row segment of min(B, 16) pixels
+    hipLaunchKernelGGL(paint, dim3((threads + 255) / 256, g.planes), dim3(256), 0, s, scaled, image, qrows, iso,
                        state, sqbuf, counter, g);
     FIC_LAUNCH_CHECK();
     return fic_launch_decode_step(state, sqbuf, counter, g.W * g.H, g.planes, s);

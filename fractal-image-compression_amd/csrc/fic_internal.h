@@ -37,6 +37,9 @@ struct ErrKeep {
 
 // Geometry as the reference derives it (FC:111-116, FC:1019-1022) + what it needs to not throw; out == nullptr: validate only
 int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* out);
+// Decoders only: the geometry (zoom w, zoom h, zoom B, wK) of a decode at zoom 1, 2 or 4 of a stream whose own geometry
+// (w, h, B, wK) make_geometry accepts; block sides up to 64.  FIC_E_ARGUMENT for another zoom.
+int make_decode_geometry(int w, int h, int B, int wK, int n_iso, int planes, int zoom, FicGeom* out);
 
 template <typename T>
 int dev_alloc(T** p, size_t count)

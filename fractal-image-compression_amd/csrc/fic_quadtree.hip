@@ -23,24 +23,25 @@
 // The quantised row's value at every pixel of a range block row, as k_decode_paint computes it (FC:394-402):
 //   a = (float) qa / 100f, b = (float) qb, value = clamp((int) fl(fl(a * d) + b)),
 // d the winner's domain pixel (isometry applied) in the 2:1-scaled image `scaled`.
-template <int B>
-__device__ __forceinline__ void qt_row_values(const uint8_t* __restrict__ scaled, const FicGeom& g, int gi, int k, int ry, float a,
-                                              float b, int (&value)[B])
+// A row is evaluated in segments of S pixels from x0 on (S = B, x0 = 0 up to B = 16: the whole row).
+template <int B, int S>
+__device__ __forceinline__ void qt_row_values(const uint8_t* __restrict__ scaled, const FicGeom& g, int gi, int k, int ry, int x0,
+                                              float a, float b, int (&value)[S])
 {
     const int c = gi % g.Dw, r = gi / g.Dw;
     const uint8_t* dom = scaled + (size_t)(r * g.abstand) * g.Ws + c * g.abstand;
-    uint8_t dpx[B];
+    uint8_t dpx[S];
     if (k == 0) {
-        __builtin_memcpy(dpx, dom + (size_t)ry * g.Ws, B);
+        __builtin_memcpy(dpx, dom + (size_t)ry * g.Ws + x0, S);
     } else {
         int ax, bx_, cx, ay, by_, cy;
         iso_affine(k, B - 1, ax, bx_, cx, ay, by_, cy);
-        const int s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry, sx = ay * g.Ws + ax;
+        const int sx = ay * g.Ws + ax, s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry + sx * x0;
 #pragma unroll
-        for (int x = 0; x < B; x++) dpx[x] = dom[s0 + sx * x];
+        for (int x = 0; x < S; x++) dpx[x] = dom[s0 + sx * x];
     }
 #pragma unroll
-    for (int x = 0; x < B; x++) {
+    for (int x = 0; x < S; x++) {
         int v = java_f2i(__fadd_rn(__fmul_rn(a, (float)dpx[x]), b));
         value[x] = v < 0 ? 0 : (v > 255 ? 255 : v);
     }
@@ -52,7 +53,7 @@ __device__ __forceinline__ uint32_t qt_row_sse(const uint8_t* __restrict__ prow,
                                                int gi, int k, int ry, const int32_t* __restrict__ q)
 {
     int value[B];
-    qt_row_values<B>(scaled, g, gi, k, ry, __fdiv_rn((float)q[0], 100.0f), (float)q[1], value);
+    qt_row_values<B, B>(scaled, g, gi, k, ry, 0, __fdiv_rn((float)q[0], 100.0f), (float)q[1], value);
     uint32_t s = 0;
 #pragma unroll
     for (int x = 0; x < B; x++) {
@@ -232,52 +233,52 @@ __global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// One pixel row of one decoder paint of leaf e, grey (FC:385-407): paints prow, stores the squared changes to srow, returns
-// their sum.
+// One segment -- S pixels from x0 on; the whole row up to B = 16 -- of pixel row ry of one decoder paint of leaf e, grey
+// (FC:385-407): paints prow, stores the squared changes to srow (both at the segment), returns their sum.
 // ---------------------------------------------------------------------------------------------
-template <int B>
+template <int B, int S>
 __device__ __forceinline__ uint32_t qt_paint_row(uint8_t* __restrict__ prow, uint32_t* __restrict__ srow, const uint8_t* __restrict__ scaled,
-                                                 const FicGeom& g, const FicQtLeaf& e, int ry)
+                                                 const FicGeom& g, const FicQtLeaf& e, int ry, int x0)
 {
-    uint32_t old[B / 4], neu[B / 4], sqv[B], sq = 0;
-    __builtin_memcpy(old, prow, B);
-    int value[B];
-    qt_row_values<B>(scaled, g, e.gi, e.q[2], ry, __fdiv_rn((float)e.q[0], 100.0f), (float)e.q[1], value);
+    uint32_t old[S / 4], neu[S / 4], sqv[S], sq = 0;
+    __builtin_memcpy(old, prow, S);
+    int value[S];
+    qt_row_values<B, S>(scaled, g, e.gi, e.q[2], ry, x0, __fdiv_rn((float)e.q[0], 100.0f), (float)e.q[1], value);
 #pragma unroll
-    for (int q = 0; q < B / 4; q++) neu[q] = 0u;
+    for (int q = 0; q < S / 4; q++) neu[q] = 0u;
 #pragma unroll
-    for (int x = 0; x < B; x++) {
+    for (int x = 0; x < S; x++) {
         const int dd = (int)((old[x >> 2] >> (8 * (x & 3))) & 0xffu) - value[x];
         neu[x >> 2] |= (uint32_t)value[x] << (8 * (x & 3));
         sqv[x] = (uint32_t)(dd * dd);
         sq += sqv[x];
     }
-    __builtin_memcpy(prow, neu, B);
+    __builtin_memcpy(prow, neu, S);
 #pragma unroll
-    for (int q = 0; q < B / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
+    for (int q = 0; q < S / 4; q++) *(uint4*)(srow + 4 * q) = make_uint4(sqv[4 * q], sqv[4 * q + 1], sqv[4 * q + 2], sqv[4 * q + 3]);
     return sq;
 }
 
 // The same for decodeRGB (FC:458-499): the squares are dR^2 + dG^2 + dB^2 per pixel (FC:493).
-template <int B>
+template <int B, int S>
 __device__ __forceinline__ uint32_t qt_paint_row(int32_t* __restrict__ prow, uint32_t* __restrict__ srow, const int32_t* __restrict__ scaled,
-                                                 const FicGeom& g, const FicQtLeaf& e, int ry)
+                                                 const FicGeom& g, const FicQtLeaf& e, int ry, int x0)
 {
     const FicRgbCoef cf = rgb_row_coef(e.q[0], e.q[1], e.q[2], e.q[3]);
-    int32_t cur[B], dom[B];
-    uint32_t sqv[B], sq = 0;
-    __builtin_memcpy(cur, prow, 4 * B);
-    __builtin_memcpy(dom, rgb_domain_row(scaled, g, e.gi, ry), 4 * B);
+    int32_t cur[S], dom[S];
+    uint32_t sqv[S], sq = 0;
+    __builtin_memcpy(cur, prow, 4 * S);
+    __builtin_memcpy(dom, rgb_domain_row(scaled, g, e.gi, ry) + x0, 4 * S);
 #pragma unroll
-    for (int x = 0; x < B; x++) {
+    for (int x = 0; x < S; x++) {
         int vR, vG, vB;
         rgb_paint_px(cf, dom[x], vR, vG, vB);
         sqv[x] = rgb_sq(cur[x], vR, vG, vB);
         sq += sqv[x];
         cur[x] = (int32_t)(0xff000000u | ((uint32_t)vR << 16) | ((uint32_t)vG << 8) | (uint32_t)vB);
     }
-    __builtin_memcpy(prow, cur, 4 * B);
-    __builtin_memcpy(srow, sqv, 4 * B);
+    __builtin_memcpy(prow, cur, 4 * S);
+    __builtin_memcpy(srow, sqv, 4 * S);
     return sq;
 }
 
@@ -299,8 +300,13 @@ __device__ __forceinline__ void qt_ssd_add(unsigned long long sq, unsigned long 
 // k_decode_paint_leaves<Fmt, B>: one decoder paint of the n leaves of side B in `lv`.  Each entry carries the leaf's position,
 // its global domain block (window_to_global of its level, resolved by the reader), its offset in `sqbuf` (the prefix sum of
 // B^2 over the leaves before it, so the squares lie in leaf order, pixel rows within a leaf) and its row.  One thread per pixel
-// row of a leaf; the exact integer sum of the squares goes to state->ssd[counter] like k_decode_paint's.
+// row of a leaf up to B = 16; at the decode-only sides 32 and 64 (zoomed decodes) per row SEGMENT of 16 grey or
+// 4 packed ARGB pixels (16 bytes of the image per thread either way, a whole row would not fit a thread's registers), ordered
+// (leaf, pixel row, segment): neighbours in a wave touch neighbouring bytes of the same image row.  The exact integer sum of
+// the squares goes to state->ssd[counter] like k_decode_paint's.
 // ---------------------------------------------------------------------------------------------
+template <typename Fmt, int B>
+constexpr int qt_paint_seg() { return B <= 16 ? B : (sizeof(typename Fmt::Px) == 1 ? 16 : 4); }
 template <typename Fmt, int B>
 __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt::Px* __restrict__ scaled, typename Fmt::Px* __restrict__ image,
                                                              const FicQtLeaf* __restrict__ lv, int n, FicDecodeState* __restrict__ state,
@@ -310,10 +316,13 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt:
     if (st->done) return;                                  // uniform
     const int t = blockIdx.x * 256 + threadIdx.x;
     unsigned long long sq = 0;
-    if (t < n * B) {
-        const FicQtLeaf e = lv[t / B];
-        const int ry = t % B;
-        sq = qt_paint_row<B>(image + (size_t)(e.y + ry) * g.W + e.x, sqbuf + (size_t)e.sqoff + (size_t)ry * B, scaled, g, e, ry);
+    constexpr int S = qt_paint_seg<Fmt, B>(), NS = B / S;
+    if (t < n * B * NS) {
+        const int x0 = (t % NS) * S, u = t / NS;
+        const FicQtLeaf e = lv[u / B];
+        const int ry = u % B;
+        sq = qt_paint_row<B, S>(image + (size_t)(e.y + ry) * g.W + e.x + x0, sqbuf + (size_t)e.sqoff + (size_t)ry * B + x0, scaled, g, e,
+                                ry, x0);
     }
     qt_ssd_add(sq, &st->ssd[counter]);
 }
@@ -366,8 +375,10 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
                                    FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
 {
     if (n <= 0) return 0;
-    auto k = g.B == 4 ? k_decode_paint_leaves<Fmt, 4> : (g.B == 8 ? k_decode_paint_leaves<Fmt, 8> : k_decode_paint_leaves<Fmt, 16>);
-    hipLaunchKernelGGL(k, dim3((n * g.B + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
+    auto k = g.B == 4 ? k_decode_paint_leaves<Fmt, 4> : (g.B == 8 ? k_decode_paint_leaves<Fmt, 8> : (g.B == 16 ? k_decode_paint_leaves<Fmt, 16> :
+             (g.B == 32 ? k_decode_paint_leaves<Fmt, 32> : k_decode_paint_leaves<Fmt, 64>)));      // 32, 64: zoomed decodes only
+    const int segs = g.B <= 16 ? 1 : g.B / (sizeof(typename Fmt::Px) == 1 ? 16 : 4);               // qt_paint_seg
+    hipLaunchKernelGGL(k, dim3((n * g.B * segs + 255) / 256), dim3(256), 0, s, scaled, image, lv, n, state, sqbuf, counter, g);
     FIC_LAUNCH_CHECK();
     return 0;
 }

@@ -190,13 +190,21 @@ class Encoder:
         capi.check(capi.lib().fic_ctx_collage_host(self._h, capi.ptr(out, C.c_int32)))
         return out
 
-    def decode(self):
+    def decode(self, zoom=1):
         """Reference decoder loop (FC:356-421) on the device from the last encode's quantised rows
-        (+ isometries).  Returns (gray uint8 [planes,H,W], avgError float32 [planes], iterations int32 [planes])."""
+        (+ isometries).  Returns (gray uint8 [planes,H,W], avgError float32 [planes], iterations int32 [planes]).
+        zoom = 2 / 4: the same loop on the geometry (zoom*W, zoom*H, zoom*B, wK), [planes, zoom*H, zoom*W] out
+        (fic_ctx_decode_zoom_host)."""
         P = self.planes
-        out = np.zeros((P, self.height, self.width), np.uint8)
         avg = np.zeros(P, np.float32)
         it = np.zeros(P, np.int32)
+        if zoom != 1:
+            z = int(zoom) if zoom in (1, 2, 4) else 1     # the library refuses any other zoom before it writes
+            out = np.zeros((P, z * self.height, z * self.width), np.uint8)
+            capi.check(capi.lib().fic_ctx_decode_zoom_host(self._h, int(zoom), capi.ptr(out, C.c_uint8), capi.ptr(avg, C.c_float),
+                                                           capi.ptr(it, C.c_int)))
+            return out, avg, it
+        out = np.zeros((P, self.height, self.width), np.uint8)
         capi.check(capi.lib().fic_ctx_decode_host(self._h, capi.ptr(out, C.c_uint8), capi.ptr(avg, C.c_float),
                                                   capi.ptr(it, C.c_int)))
         return out, avg, it

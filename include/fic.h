@@ -208,6 +208,31 @@ FIC_API int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int3
  * iterations_out [planes], may be NULL.  Every range block must have been encoded. */
 FIC_API int fic_ctx_decode_host(fic_ctx* ctx, uint8_t* gray_out, float* avg_error_out, int* iterations_out);
 
+/* ---- decoding at 2x or 4x zoom ------------------------------------------------------------------ */
+/* A codebook row says "paint this range block from that domain block with contrast a and brightness b"; nothing in it
+ * depends on the pixel size.  The geometry is scale-free (Rw = w / B, Dw = 2 Rw - 3, domain stride B / 4), so the stream of
+ * a w x h, block-B image is also a stream of a zoom*w x zoom*h image with block zoom*B.  Each entry below is its unzoomed
+ * twin with `int zoom` in {1, 2, 4} (FIC_E_ARGUMENT otherwise) and runs exactly the twin's loop on the geometry
+ * (zoom*w, zoom*h, zoom*B, wK): the same start image, the rows unchanged, scaleImage / scaleImageRGB of the current zoomed
+ * image (the `x + 1 >= height` quirk evaluated at the zoomed size), domain origin (c * zoom*B / 4, r * zoom*B / 4), the same
+ * per-pixel arithmetic, isometries of side zoom*B, avgError summed in Java's float order over the zoomed pixels (range block by
+ * range block, pixel rows within a block) and divided by (float) (zoom*w * zoom*h), at most 50 iterations, stop at < 1.  A
+ * quadtree leaf {x, y, B} becomes {zoom*x, zoom*y, zoom*B} in its stream order with its own level's window.  zoom = 1 is the
+ * twin bit for bit.  The stream itself must be one the twin accepts (its own B in {4, 8, 16}: the sides 32 and 64 exist for
+ * zoomed decodes only); *w / *h return the zoomed size and the output needs zoom^2 * w * h pixels (FIC_E_CAPACITY);
+ * FIC_E_GEOMETRY when the zoomed image exceeds the 32-bit limits of the geometry.  All checks happen before any device work. */
+FIC_API int fic_decode_gray_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity,
+                                     int* w, int* h, float* avg_error_io, int* iterations);
+FIC_API int fic_decode_rgb_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out,
+                                    int64_t capacity_pixels, int* w, int* h, float* avg_error_io, int* iterations);
+FIC_API int fic_decode_quadtree_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity,
+                                         int* w, int* h, float* avg_error_io, int* iterations);
+FIC_API int fic_decode_rgb_quadtree_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out,
+                                             int64_t capacity_pixels, int* w, int* h, float* avg_error_io, int* iterations);
+/* fic_ctx_decode_host at zoom: gray_out [planes][zoom*h][zoom*w].  The way to zoom a fixed-B n_iso = 8 codebook (the .run
+ * format has no isometry column), and batched planes. */
+FIC_API int fic_ctx_decode_zoom_host(fic_ctx* ctx, int zoom, uint8_t* gray_out, float* avg_error_out, int* iterations_out);
+
 /* ---- quadtree (variable block size) grey codec -------------------------------------------------- */
 /* An extension like n_iso = 8: the reference encodes with one block size (FC:14).  Levels B_max in {8, 16}, B_min in {4, 8},
  * B_min < B_max; w and h multiples of B_max.  Every level B = B_max, B_max/2, ..., B_min is encoded exactly as

@@ -93,22 +93,26 @@ public:
         return collage;
     }
 
-    // FractalCompression.java:547-553: reads the whole .run stream and dispatches on its first int.
-    static RasterImage decode(std::istream& in)
+    // FractalCompression.java:547-553: reads the whole .run stream and dispatches on its first int.  zoom = 2 / 4 (an
+    // extension): the same loop on the geometry (zoom w, zoom h, zoom B, wK), a zoom w x zoom h image out.
+    static RasterImage decode(std::istream& in, int zoom = 1)
     {
+        if (zoom != 1 && zoom != 2 && zoom != 4) throw std::runtime_error("decode: zoom must be 1, 2 or 4");
         std::vector<uint8_t> run((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
         if (run.size() < 20) throw std::runtime_error("decode: stream shorter than its header (EOFException)");
         const bool rgb = (run[0] | run[1] | run[2] | run[3]) != 0;
         int w = 0, h = 0;
         auto be = [&](size_t o) { return (int)((run[o] << 24) | (run[o + 1] << 16) | (run[o + 2] << 8) | run[o + 3]); };
-        RasterImage img(be(4) > 0 ? be(4) : 0, be(8) > 0 ? be(8) : 0);
+        const int64_t zw = (int64_t)(be(4) > 0 ? be(4) : 0) * zoom, zh = (int64_t)(be(8) > 0 ? be(8) : 0) * zoom;
+        if (zw * zh >= 0x7FFFFFFFll) throw std::runtime_error("decode: image too large");
+        RasterImage img((int)zw, (int)zh);
         if (rgb) {
-            check(fic_decode_rgb_run(run.data(), (int64_t)run.size(), device, img.argb.data(), (int64_t)img.argb.size(), &w, &h,
-                                     &avgError, nullptr));
+            check(fic_decode_rgb_run_zoom(run.data(), (int64_t)run.size(), zoom, device, img.argb.data(), (int64_t)img.argb.size(),
+                                          &w, &h, &avgError, nullptr));
         } else {
             std::vector<uint8_t> g(img.argb.size());
-            check(fic_decode_gray_run(run.data(), (int64_t)run.size(), device, g.data(), (int64_t)g.size(), &w, &h, &avgError,
-                                      nullptr));
+            check(fic_decode_gray_run_zoom(run.data(), (int64_t)run.size(), zoom, device, g.data(), (int64_t)g.size(), &w, &h,
+                                           &avgError, nullptr));
             for (size_t i = 0; i < g.size(); i++)
                 img.argb[i] = (int32_t)(0xff000000u | ((uint32_t)g[i] << 16) | ((uint32_t)g[i] << 8) | g[i]);
         }
