@@ -88,6 +88,9 @@ def lib():
         "fic_ctx_collage_host": (C.c_int, [vp, i32p]),
         "fic_encode_rgb_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p]),
         "fic_rgb_ctx_create": (vp, [C.c_int] * 6),
+        "fic_encode_rgb_iso_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p, i32p]),
+        "fic_rgb_ctx_create_iso": (vp, [C.c_int] * 7),
+        "fic_rgb_ctx_get_iso_host": (C.c_int, [vp, i32p]),
         "fic_rgb_ctx_destroy": (None, [vp]),
         "fic_rgb_ctx_set_argb_host": (C.c_int, [vp, i32p]),
         "fic_rgb_ctx_set_argb_device": (C.c_int, [vp, vp]),
@@ -277,34 +280,40 @@ def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):
     return out[:cap], np.float32(avg.value), it.value, w, h
 
 
-def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False):
+def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1):
     """encodeRGB (FC:171-219) on the GPU.  argb: int32 [h*w].  Returns a dict of [N_r] arrays
-    (idx_local, a, bR, bG, bB, qrows [N_r,5]) and, when asked, the collage (int32 [h*w])."""
+    (idx_local, a, bR, bG, bB, iso, qrows [N_r,5]) and, when asked, the collage (int32 [h*w]).  n_iso = 8: the search also
+    tries the 8 isometries of the domain block (fic_encode_rgb_iso_argb; `iso` is all 0 with n_iso = 1, the reference path)."""
     Rw, Rh, Dw, Dh = geometry(w, h, B)
     nr = Rw * Rh
     argb = np.ascontiguousarray(argb, np.int32).reshape(-1)
     if argb.size != w * h:
         raise FicError(-3, "argb has the wrong number of pixels")
     r = {"idx_local": np.zeros(nr, np.int32), "a": np.zeros(nr, np.float32), "bR": np.zeros(nr, np.float32),
-         "bG": np.zeros(nr, np.float32), "bB": np.zeros(nr, np.float32), "qrows": np.zeros((nr, 5), np.int32)}
+         "bG": np.zeros(nr, np.float32), "bB": np.zeros(nr, np.float32), "iso": np.zeros(nr, np.int32),
+         "qrows": np.zeros((nr, 5), np.int32)}
     col = np.zeros(w * h, np.int32) if want_collage else None
-    check(lib().fic_encode_rgb_argb(ptr(argb, C.c_int32), w, h, B, wK, device, ptr(r["idx_local"], C.c_int32),
-                                    ptr(r["a"], C.c_float), ptr(r["bR"], C.c_float), ptr(r["bG"], C.c_float),
-                                    ptr(r["bB"], C.c_float), ptr(r["qrows"], C.c_int32), ptr(col, C.c_int32)))
+    check(lib().fic_encode_rgb_iso_argb(ptr(argb, C.c_int32), w, h, B, wK, n_iso, device, ptr(r["idx_local"], C.c_int32),
+                                        ptr(r["a"], C.c_float), ptr(r["bR"], C.c_float), ptr(r["bG"], C.c_float),
+                                        ptr(r["bB"], C.c_float), ptr(r["iso"], C.c_int32), ptr(r["qrows"], C.c_int32),
+                                        ptr(col, C.c_int32)))
     if want_collage:
         r["collage"] = col
     return r
 
 
 class RgbEncoder:
-    """Handle API of the joint-RGB path (fic_rgb_ctx_*): `planes` colour images of one geometry, device resident."""
+    """Handle API of the joint-RGB path (fic_rgb_ctx_*): `planes` colour images of one geometry, device resident.
+    n_iso = 8: the search tries the 8 isometries of every domain block; results()["iso"] holds the winners and decode()
+    paints through them."""
 
-    def __init__(self, width, height, B, wK, planes=1, device=0):
+    def __init__(self, width, height, B, wK, planes=1, device=0, n_iso=1):
         L = lib()
         self.width, self.height, self.B, self.wK, self.planes, self.device = width, height, B, wK, planes, device
+        self.n_iso = n_iso
         Rw, Rh, Dw, Dh = geometry(width, height, B)
         self.n_ranges = Rw * Rh
-        self._h = L.fic_rgb_ctx_create(device, width, height, B, wK, planes)
+        self._h = L.fic_rgb_ctx_create_iso(device, width, height, B, wK, n_iso, planes)
         if not self._h:
             raise FicError(L.fic_last_error_code() or -3, last_error())
 
@@ -387,6 +396,9 @@ class RgbEncoder:
         check(lib().fic_rgb_ctx_get_results_host(self._h, ptr(r["idx_local"], C.c_int32), ptr(r["a"], C.c_float),
                                                  ptr(r["bR"], C.c_float), ptr(r["bG"], C.c_float), ptr(r["bB"], C.c_float),
                                                  ptr(r["qrows"], C.c_int32), ptr(col, C.c_int32)))
+        r["iso"] = np.zeros((P, N), np.int32)
+        if self.n_iso != 1:                                  # n_iso = 1: the identity everywhere, the calls of the reference path only
+            check(lib().fic_rgb_ctx_get_iso_host(self._h, ptr(r["iso"], C.c_int32)))
         if col is not None:
             r["collage"] = col
         return r

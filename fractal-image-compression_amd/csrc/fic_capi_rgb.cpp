@@ -24,6 +24,7 @@ struct fic_rgb_ctx {
     unsigned long long* key = nullptr;
     int32_t *idx_local = nullptr, *idx_global = nullptr, *qrows = nullptr, *collage = nullptr;
     float *a = nullptr, *bR = nullptr, *bG = nullptr, *bB = nullptr;
+    int32_t* iso = nullptr;          // winning isometries [planes][N_r] (n_iso = 8 contexts only; g.n_iso says which)
     int32_t* dec_image = nullptr;    // decoder: image, scaled image, state, per-pixel squared changes (one plane at a time)
     int32_t* dec_scaled = nullptr;
     FicDecodeState* dec_state = nullptr;
@@ -42,7 +43,7 @@ void rgb_free_all(fic_rgb_ctx* c)
 {
     (void)hipSetDevice(c->device);
     void* ptrs[] = {c->argb_own, c->scaled, c->pool_sum, c->pool_cf, c->pool_st, c->rng_t, c->rng_st, c->key, c->idx_local,
-                    c->idx_global, c->qrows, c->collage, c->a, c->bR, c->bG, c->bB, c->dec_image, c->dec_scaled, c->dec_state, c->dec_sq,
+                    c->idx_global, c->qrows, c->collage, c->a, c->bR, c->bG, c->bB, c->iso, c->dec_image, c->dec_scaled, c->dec_state, c->dec_sq,
                     c->q.poolQ, c->q.dflat, c->q.rngQ, c->q.qst, c->q.rngE, c->q.theta_g, c->q.amax, c->q.stats};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -67,6 +68,7 @@ void rgb_plane(const fic_rgb_ctx* c, int p, FicRgbBuffers* b, FicRgbOutputs* o)
     o->bG = c->bG + P * nr;
     o->bB = c->bB + P * nr;
     o->qrows = c->qrows + P * nr * 5;
+    o->iso = c->iso ? c->iso + P * nr : nullptr;
 }
 // pool chunks of the matrix-core full search: the policy of the grey q sweep (fic_capi.cpp, q_sweep), or the "chunks" option
 void rgb_q_chunks(fic_rgb_ctx* c)
@@ -74,7 +76,7 @@ void rgb_q_chunks(fic_rgb_ctx* c)
     const FicGeom& g = c->g;
     FicRgbQ& q = c->q;
     const int unroll = fic_q_unroll(g.B, 1), CT = fic_q_ct(g.B);
-    const int nct = (g.Nr + 31) / 32;
+    const int nct = (int)(((long long)g.Nr * g.n_iso + 31) / 32);       // n_iso = 8: 8 columns per range block
     long long nc = c->opt_chunks;
     if (nc <= 0) {
         const long long base_wg = (nct + CT - 1) / CT;
@@ -104,7 +106,7 @@ int rgb_q_setup(fic_rgb_ctx* c)
     const size_t NK = (size_t)g.n / 16;
     q.ndtiles = (g.Nd + 31) / 32;
     q.ndtiles_alloc = q.ndtiles + 2 * unroll;
-    const int nct = (g.Nr + 31) / 32;
+    const int nct = (int)(((long long)g.Nr * g.n_iso + 31) / 32);       // n_iso = 8: 8 columns per range block
     q.nct_alloc = ((nct + CT - 1) / CT * CT + CT + 1) & ~1;
     int rc = FIC_OK;
     auto A = [&](hipError_t e) { if (rc == FIC_OK && e != hipSuccess) rc = fail(FIC_E_HIP, "RGB matrix-core buffers: %s", hipGetErrorString(e)); };
@@ -131,8 +133,20 @@ std::vector<fic_rgb_ctx*> g_rgb_cache;
 
 fic_rgb_ctx* fic_rgb_ctx_create(int device, int w, int h, int B, int wK, int planes)
 {
+    return fic_rgb_ctx_create_iso(device, w, h, B, wK, 1, planes);
+}
+
+fic_rgb_ctx* fic_rgb_ctx_create_iso(int device, int w, int h, int B, int wK, int n_iso, int planes)
+{
+    if (n_iso != 1 && n_iso != 8) { fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso); return nullptr; }
     FicGeom g;
     if (make_geometry(w, h, B, wK, 1, planes, &g)) return nullptr;
+    // the search key's low word carries c * 8 + k
+    if (n_iso == 8 && (long long)g.wK * g.wK >= (1ll << 28)) {
+        fail(FIC_E_GEOMETRY, "window of %d x %d candidates too large for 8 isometries (c * 8 + k must fit 31 bits)", g.wK, g.wK);
+        return nullptr;
+    }
+    g.n_iso = n_iso;                 // the other fields are those of the 1-isometry geometry (the grey sweeps' tiling is not used here)
     int ndev = fic_device_count();
     if (ndev <= 0) { fail(FIC_E_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); return nullptr; }
     if (device < 0 || device >= ndev) { fail(FIC_E_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1); return nullptr; }
@@ -157,6 +171,7 @@ fic_rgb_ctx* fic_rgb_ctx_create(int device, int w, int h, int B, int wK, int pla
     A(dev_alloc(&c->bB, P * nr));
     A(dev_alloc(&c->qrows, P * nr * 5));
     A(dev_alloc(&c->collage, P * npix));
+    if (n_iso == 8) A(dev_alloc(&c->iso, P * nr));
     if (rc != FIC_OK) {
         rgb_free_all(c);
         delete c;
@@ -211,7 +226,8 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
     int want = c->opt_sweep;
     if (const char* env = getenv("FIC_RGB_SWEEP"))
         if (env[0] >= '1' && env[0] <= '2' && !env[1]) want = env[0] - '0';
-    const bool use_q = g.full && g.Nd < (1 << 24) && (want == 2 || (want == 0 && ((double)g.Nr * g.Nd >= 3e7 || g.B == 16)));
+    // 8 isometries: the same rule with 8 times the pairs (k_sweep_q<NK, 4>)
+    const bool use_q = g.full && g.Nd < (1 << 24) && (want == 2 || (want == 0 && ((double)g.n_iso * g.Nr * g.Nd >= 3e7 || g.B == 16)));
     if (use_q && rgb_q_setup(c)) return FIC_E_HIP;
     if (use_q) rgb_q_chunks(c);
     if (!use_q && g.full && g.B <= 8 && !c->pool_cf) {      // the VALU full-search sweep's f32 pool copy (k_sweep_rgb_fast), on first use
@@ -324,11 +340,13 @@ int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
     char buf[96];
     if (c->last_sweep == 2) {
         const int kind = fic_q_multi_kind(c->q.nchunks, c->q.tiles_per_chunk);      // what fic_launch_rgbq instantiates
-        if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, 3>", NK);
-        else snprintf(buf, sizeof(buf), "k_sweep_q<%d, 3, %s>", NK, kind ? "true" : "false");
+        const int mode = g.n_iso == 8 ? 4 : 3;
+        if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, %d>", NK, mode);
+        else snprintf(buf, sizeof(buf), "k_sweep_q<%d, %d, %s>", NK, mode, kind ? "true" : "false");
     } else if (c->last_sweep == 1) {
-        if (g.full && g.B <= 8) snprintf(buf, sizeof(buf), "k_sweep_rgb_fast<%d>", g.n);
-        else snprintf(buf, sizeof(buf), "k_sweep_rgb");
+        const char* iso = g.n_iso == 8 ? "_iso" : "";
+        if (g.full && g.B <= 8) snprintf(buf, sizeof(buf), "k_sweep_rgb_fast%s<%d>", iso, g.n);
+        else snprintf(buf, sizeof(buf), "k_sweep_rgb%s", iso);
     } else snprintf(buf, sizeof(buf), "(none)");
     snprintf(out, (size_t)capacity, "%s", buf);
     return FIC_OK;
@@ -361,6 +379,21 @@ int fic_rgb_ctx_get_results_host(fic_rgb_ctx* c, int32_t* idx_local, float* a, f
     return FIC_OK;
 }
 
+int fic_rgb_ctx_get_iso_host(fic_rgb_ctx* c, int32_t* iso)
+{
+    if (!c || !iso) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_get_iso_host: null argument");
+    if (!c->encoded_any) return fail(FIC_E_STATE, "fic_rgb_ctx_get_iso_host: nothing encoded yet");
+    const size_t n = (size_t)c->g.planes * c->g.Nr;
+    if (!c->iso) {                                     // n_iso = 1: the identity everywhere
+        memset(iso, 0, n * sizeof(int32_t));
+        return FIC_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(iso, c->iso, n * 4, hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
 // decodeRGB (FC:430-508) from the context's quantised rows, plane by plane, everything device resident
 int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_out, int* iterations_out)
 {
@@ -379,9 +412,10 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
     hipStream_t s = c->last_stream;
     for (int p = 0; p < g.planes; p++) {
         const int32_t* qrows = c->qrows + (size_t)p * g.Nr * 5;
+        const int32_t* iso = c->iso ? c->iso + (size_t)p * g.Nr : nullptr;      // n_iso = 8: paint through src_k
         int rc = decode_loop(kDecodeRgb, 1, npix, c->dec_image, c->dec_state, nullptr, avg_error_out ? avg_error_out + p : nullptr,
                              iterations_out ? iterations_out + p : nullptr, nullptr, s, [&](int counter) {
-            return fic_launch_decode_iteration_rgb(c->dec_scaled, c->dec_image, qrows, c->dec_state, c->dec_sq, counter, g1, s);
+            return fic_launch_decode_iteration_rgb(c->dec_scaled, c->dec_image, qrows, c->dec_state, c->dec_sq, counter, g1, s, iso);
         });
         if (rc == FIC_E_ARGUMENT) return fail(rc, "%s (plane %d of the context)", g_err.c_str(), p);
         if (rc) return rc;
@@ -392,13 +426,13 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
 
 }  // extern "C"
 
-fic_rgb_ctx* ficd::rgb_cache_take(int device, int w, int h, int B, int wK)
+fic_rgb_ctx* ficd::rgb_cache_take(int device, int w, int h, int B, int wK, int n_iso)
 {
     std::lock_guard<std::mutex> lk(g_rgb_mu);
     for (size_t i = g_rgb_cache.size(); i-- > 0;) {
         fic_rgb_ctx* c = g_rgb_cache[i];
         const FicGeom& g = c->g;
-        if (c->device == device && g.W == w && g.H == h && g.B == B && g.wK == wK && g.planes == 1) {
+        if (c->device == device && g.W == w && g.H == h && g.B == B && g.wK == wK && g.n_iso == n_iso && g.planes == 1) {
             g_rgb_cache.erase(g_rgb_cache.begin() + (long)i);
             return c;
         }
@@ -432,13 +466,22 @@ int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK, int de
                         float* bR, float* bG, float* bB, int32_t* qrows5, int32_t* collage_argb)
 {
     if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_argb: null argument");
+    return fic_encode_rgb_iso_argb(argb, w, h, B, wK, 1, device, idx_local, a, bR, bG, bB, nullptr, qrows5, collage_argb);
+}
+
+int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local, float* a,
+                            float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb)
+{
+    if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_iso_argb: null argument");
+    if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso);
     // the GUI re-encodes the same image on every slider move (CTL:125-145): keep the last few working sets
-    fic_rgb_ctx* c = rgb_cache_take(device, w, h, B, wK);
-    if (!c) c = fic_rgb_ctx_create(device, w, h, B, wK, 1);
+    fic_rgb_ctx* c = rgb_cache_take(device, w, h, B, wK, n_iso);
+    if (!c) c = fic_rgb_ctx_create_iso(device, w, h, B, wK, n_iso, 1);
     if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_rgb_ctx_create recorded why
     int rc = fic_rgb_ctx_set_argb_host(c, argb);
     if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c, collage_argb ? 1 : 0, nullptr);
     if (rc == FIC_OK) rc = fic_rgb_ctx_get_results_host(c, idx_local, a, bR, bG, bB, qrows5, collage_argb);
+    if (rc == FIC_OK && iso) rc = fic_rgb_ctx_get_iso_host(c, iso);
     ErrKeep keep;
     if (rc == FIC_OK) rgb_cache_give(c);
     else fic_rgb_ctx_destroy(c);

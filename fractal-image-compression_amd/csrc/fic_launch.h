@@ -100,6 +100,7 @@ struct FicRgbOutputs {
     float* bG;
     float* bB;
     int32_t* qrows;
+    int32_t* iso = nullptr;  // winning isometry [N_r]; NULL: n_iso = 1 (the reference path: the key carries c, no gather)
 };
 struct FicRgbBuffers {
     int32_t* argb;           // input [H][W]
@@ -171,7 +172,8 @@ int fic_launch_sweep_q(const FicBuffers& b, const void* poolQ, const void* dflat
                        int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s, unsigned long long* stats = nullptr, int dbg_noflag = 0,
                        const FicOutputs* fin_out = nullptr, unsigned int* fin_count = nullptr, int r_begin = 0, int r_count = 0);
 int fic_launch_decode_iteration_rgb(int32_t* scaled, int32_t* image, const int32_t* qrows5, FicDecodeState* state,
-                                    uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
+                                    uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s,
+                                    const int32_t* iso = nullptr);   // iso [N_r]: an n_iso = 8 codebook of a context, NULL: identity
 int fic_launch_scale_rgb(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s);   // one image
 
 // decoder (FC:356-421)

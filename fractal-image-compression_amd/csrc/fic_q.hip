@@ -687,8 +687,9 @@ __device__ __forceinline__ float max16_sum(const v16f& a, const v16f& b)
 }
 
 template <int MODE> struct QMode {
-    static constexpr int CSHIFT = (MODE == 0 || MODE == 3) ? 0 : (MODE == 1 ? 3 : 2);   // log2(columns per range block)
+    static constexpr int CSHIFT = (MODE == 0 || MODE == 3) ? 0 : ((MODE == 1 || MODE == 4) ? 3 : 2);   // log2(columns per range block)
     static constexpr int NISO = (MODE == 0 || MODE == 3) ? 1 : 8;
+    static constexpr bool RGB = MODE == 3 || MODE == 4;      // joint RGB (end of file): 3 = 1 isometry, 4 = 8 isometries, one column per copy
 };
 // first isometry of column sub-index c (MODE 2: of the pair {0,2}, {1,3}, {4,5}, {6,7})
 template <int MODE> __device__ __forceinline__ int q_col_iso(int c) { return MODE == 2 ? (c == 0 ? 0 : (c == 1 ? 1 : (c == 2 ? 4 : 6))) : c; }
@@ -724,6 +725,31 @@ __device__ __forceinline__ void q_flush(const QArgs& A, const uint32_t* myq, int
             const uint32_t d = ent & 0x00FFFFFFu;
             if (d >= (uint32_t)A.Nd) continue;                 // a zero row behind the pool, flagged while theta was "none"
             const int col = ctw0 * 32 + (int)(ent >> 24);
+            if constexpr (MODE == 4) {
+                // MODE 3's evaluation for isometry k = column & 7 of range j = column >> 3: kovarianz_k = sum_i greyR[i] *
+                // greyD[src_k(i)] in the RANGE block's order i = 0..n-1 -- the domain pixel gathered at src_k(i), not the column's
+                // (permuted) order: the f32 sums round, so the order is part of the result
+                const int j = col >> 3, k = col & 7;
+                const FicRngStat rs = rst[j];
+                const FicRgbDomStat ds = A.rgb_dst[d];
+                const int16_t* rt = A.rgb_rng + (size_t)j * (B * B);
+                const uint16_t* ps = A.rgb_pool + (size_t)d * (B * B);
+                int ax, bx, cx, ay, by, cy;
+                iso_affine(k, B - 1, ax, bx, cx, ay, by, cy);
+                const int ox = ay * B + ax, oy = by * B + bx, o0 = cy * B + cx;      // src_k(x, y) = o0 + x * ox + y * oy
+                float kov = 0.0f;
+                for (int y = 0; y < B; y++) {
+#pragma unroll 4
+                    for (int x = 0; x < B; x++)
+                        kov = __fadd_rn(kov, (float)((int)rt[y * B + x] * ((int)ps[o0 + x * ox + y * oy] - ds.msum)));
+                }
+                const float vRf = (float)rs.rem;
+                float r = (rs.rem == 0 || ds.vD == 0) ? 0.0f : __fdiv_rn(kov, __fmul_rn(vRf, (float)ds.vD));
+                r = __fmul_rn(r, r);
+                const float e = __fmul_rn(__fmul_rn(vRf, vRf), __fsub_rn(1.0f, r));
+                q_key_min(&keyp[j], ((unsigned long long)f32_orderable(e) << 32) | (d * 8u + (uint32_t)k));
+                continue;
+            }
             if constexpr (MODE == 3) {
                 // getErrorVarianceCovarianceRGB FC:781-803: kovarianz accumulated in f32 in the order i = 0..n-1 (the sums exceed
                 // 2^24: the order is part of the result), r in f32, error = varianzRange^2 * (1 - r^2); rst[].rem = varianzRange
@@ -829,7 +855,7 @@ template <int NK, int MODE>
 __device__ __forceinline__ void q_finalize_tail(const QArgs& A, int plane, int gx, int* s_wdone, int lane)
 {
     (void)lane;
-    if constexpr (MODE == 3) {
+    if constexpr (QMode<MODE>::RGB) {
         return;
     } else {
         constexpr int CSHIFT = QMode<MODE>::CSHIFT, NISO = QMode<MODE>::NISO;
@@ -1437,7 +1463,7 @@ static void q_launch_nm(int multi, dim3 grid, dim3 block, hipStream_t s, const Q
     else hipLaunchKernelGGL((k_sweep_q<NK, MODE, false>), grid, block, 0, s, A);
 }
 int fic_q_multi_kind(int nchunks, int tiles_per_chunk) { return nchunks <= 1 ? 0 : (tiles_per_chunk <= FIC_Q_GFAST_TILES ? 2 : 1); }
-// NK = n / 16; mode 0 / 1 / 2 as fic_q_mode, 3 = joint RGB.  false: no such kernel
+// NK = n / 16; mode 0 / 1 / 2 as fic_q_mode, 3 = joint RGB, 4 = joint RGB with 8 isometries.  false: no such kernel
 static bool q_launch(int NK, int mode, int multi, dim3 grid, dim3 block, hipStream_t s, const QArgs& A, int shape16 = 0)
 {
     if (shape16 && mode == 0 && NK == 4) {
@@ -1457,6 +1483,9 @@ static bool q_launch(int NK, int mode, int multi, dim3 grid, dim3 block, hipStre
     else if (NK == 16 && mode == 0) q_launch_nm<16, 0>(multi, grid, block, s, A);
     else if (NK == 16 && mode == 2) q_launch_nm<16, 2>(multi, grid, block, s, A);
     else if (NK == 16 && mode == 3) q_launch_nm<16, 3>(multi, grid, block, s, A);
+    else if (NK == 1 && mode == 4) q_launch_nm<1, 4>(multi, grid, block, s, A);
+    else if (NK == 4 && mode == 4) q_launch_nm<4, 4>(multi, grid, block, s, A);
+    else if (NK == 16 && mode == 4) q_launch_nm<16, 4>(multi, grid, block, s, A);
     else return false;
     return true;
 }
@@ -1572,6 +1601,15 @@ int fic_launch_sweep_q(const FicBuffers& b, const void* poolQ, const void* dflat
 //  * r is a correctly rounded f32 quotient (FC:800) instead of an f64 quotient cast to f32: still a monotone function of
 //    |kov_J / vD| for a fixed range, which is all the pruning argument of the header needs.
 // Inputs are what k_pool_rgb / k_range_rgb (fic_rgb.hip) already produce: R+G+B per pool pixel, greyR_i, the statistics.
+//
+// MODE 4: the same with the 8 isometries of the square (k_sweep_q<NK, 4>, CSHIFT = 3).  A range block contributes 8
+// adjacent columns; column k is the copy c_k with c_k[src_k(i)] = greyR_i, so its dot product with the natural-order domain operand
+// is sum_i greyR_i A_d[src_k(i)] = kovarianz_k / vD, the value of isometry k.  The bound: E_r depends on the range block only
+// through ||greyR|| (and on the pool through Amax), and a permutation changes neither the norm of the column nor the magnitudes
+// the f16 / f32 rounding argument sums over -- so MODE 3's E_r holds for every one of the 8 columns, and the Java-order term too
+// (it bounds sum |greyR_i greyD_src(i)| by Cauchy-Schwarz, again norms only).  theta belongs to the range: q_share_max shares it over
+// the 8 columns as in grey MODE 1, candidate 0 is (block 0, k = 0), and the search key is (error, d * 8 + k).  A flagged pair is
+// evaluated exactly in q_flush in the RANGE block's order, the domain pixel gathered at src_k(i).
 // =============================================================================================
 __global__ __launch_bounds__(256) void k_pool_qrgb(const uint16_t* __restrict__ pool_sum, const FicRgbDomStat* __restrict__ dst,
                                                    v4i* __restrict__ poolQ, uint32_t* __restrict__ dflat,
@@ -1623,17 +1661,18 @@ __global__ __launch_bounds__(256) void k_pool_qrgb(const uint16_t* __restrict__ 
     }
 }
 
-// one workgroup per 64 range blocks (= 2 column tiles): B fragments, rem := varianzRange, E_r, key / theta reset
+// one workgroup per 64 columns (= 2 column tiles; 64 >> cshift range blocks): B fragments, rem := varianzRange, E_r, key / theta
+// reset.  cshift = 0: a column per range block; 3: column j * 8 + k is the copy c_k[p] = greyR[src_kinv(p)] (kinv the inverse isometry)
 __global__ __launch_bounds__(256) void k_range_qrgb(const int16_t* __restrict__ rng_t, const FicRgbRngStat* __restrict__ rst,
                                                     FicRngStat* __restrict__ qst, float* __restrict__ rngE,
                                                     unsigned long long* __restrict__ key, uint32_t* __restrict__ theta_g,
                                                     v4i* __restrict__ rngQ, const uint32_t* __restrict__ amax, FicGeom g,
-                                                    int nct_alloc)
+                                                    int nct_alloc, int cshift)
 {
     const int n = g.n, NK = n / 16;
-    const int j0 = blockIdx.x * 64;
-    if (threadIdx.x < 64) {
-        const int j = j0 + threadIdx.x;
+    const int j0 = blockIdx.x * 64;                         // first column
+    if (threadIdx.x < (64 >> cshift)) {
+        const int j = (j0 >> cshift) + threadIdx.x;
         if (j < g.Nr) {
             const int16_t* rt = rng_t + (size_t)j * n;
             long long s2 = 0;
@@ -1651,12 +1690,23 @@ __global__ __launch_bounds__(256) void k_range_qrgb(const int16_t* __restrict__ 
     }
     for (int t = threadIdx.x; t < 2 * NK * 64; t += 256) {
         const int lane = t & 63, m = (t >> 6) % NK, ctl = (t >> 6) / NK;
-        const int j = j0 + ctl * 32 + (lane & 31), h = lane >> 5;
+        const int col = j0 + ctl * 32 + (lane & 31), h = lane >> 5;
+        const int j = col >> cshift;
         v4i v = {0, 0, 0, 0};
         if (j < g.Nr) {
-            const int16_t* p = rng_t + (size_t)j * n + 16 * m + 8 * h;
+            if (cshift == 0) {
+                const int16_t* p = rng_t + (size_t)j * n + 16 * m + 8 * h;
 #pragma unroll
-            for (int u = 0; u < 4; u++) v[u] = f16_pair((float)p[2 * u], (float)p[2 * u + 1]);
+                for (int u = 0; u < 4; u++) v[u] = f16_pair((float)p[2 * u], (float)p[2 * u + 1]);
+            } else {
+                const int16_t* p = rng_t + (size_t)j * n;
+                const int kinv = iso_inverse(col & 7), p0 = 16 * m + 8 * h;
+                float f[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) f[u] = (float)p[iso_source(kinv, g.B, (p0 + u) % g.B, (p0 + u) / g.B)];
+#pragma unroll
+                for (int u = 0; u < 4; u++) v[u] = f16_pair(f[2 * u], f[2 * u + 1]);
+            }
         }
         const int ct = j0 / 32 + ctl;
         if (ct < nct_alloc) rngQ[((size_t)ct * NK + m) * 64 + lane] = v;
@@ -1674,9 +1724,10 @@ int fic_launch_rgbq(const uint16_t* pool_sum, const FicRgbDomStat* pool_st, cons
                        (uint32_t*)amax, g);
     FIC_LAUNCH_CHECK();
     const int CT = fic_q_ct(g.B);
-    const int nct = (g.Nr + 31) / 32;
+    const int cshift = g.n_iso == 8 ? 3 : 0;                // 8 isometries: 8 columns per range block (MODE 4)
+    const int nct = (int)((((long long)g.Nr << cshift) + 31) / 32);
     hipLaunchKernelGGL(k_range_qrgb, dim3(nct_alloc / 2), dim3(256), 0, s, rng_t, rng_st, (FicRngStat*)qst, (float*)rngE, key,
-                       (uint32_t*)theta_g, (v4i*)rngQ, (const uint32_t*)amax, g, nct_alloc);
+                       (uint32_t*)theta_g, (v4i*)rngQ, (const uint32_t*)amax, g, nct_alloc, cshift);
     FIC_LAUNCH_CHECK();
     QArgs A;
     A.stats = stats;
@@ -1695,7 +1746,7 @@ int fic_launch_rgbq(const uint16_t* pool_sum, const FicRgbDomStat* pool_st, cons
     if (A.nctg * CT > nct_alloc || (nct_alloc & 1) || g.Nd >= (1 << 24) || A.ndtiles_loop + unroll > ndtiles_alloc || tiles_per_chunk % unroll)
         return (int)hipErrorInvalidValue;
     dim3 grid((unsigned)nchunks * (unsigned)A.nctg), block(64 * FIC_Q_WPG);
-    if (!q_launch(g.B * g.B / 16, 3, fic_q_multi_kind(nchunks, tiles_per_chunk), grid, block, s, A)) return (int)hipErrorInvalidValue;
+    if (!q_launch(g.B * g.B / 16, cshift ? 4 : 3, fic_q_multi_kind(nchunks, tiles_per_chunk), grid, block, s, A)) return (int)hipErrorInvalidValue;
     FIC_LAUNCH_CHECK();
     return 0;
 }

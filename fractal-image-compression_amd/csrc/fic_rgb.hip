@@ -151,6 +151,63 @@ __global__ __launch_bounds__(256) void k_sweep_rgb(const uint16_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// n_iso = 8 (extension): the same error on the explicitly permuted domain block D_k[i] = D[src_k(i)],
+// src_k = iso_source (numbering and map of the grey extension).  kovarianz_k = sum_i greyR_i * greyD[src_k(i)] accumulated in
+// f32 in the RANGE block's order i = 0..n-1 (the sums exceed 2^24: the order is part of the result); varianzRange,
+// varianzDomain, varianzSquare and the means do not depend on the pixel order and stay those of the unpermuted block.
+// Candidates in window order and k = 0..7 inside a candidate, strict '<': the key carries c * 8 + k.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float rgb_kovarianz_iso(const int16_t* __restrict__ rt, const uint16_t* __restrict__ ps, int msum, int B, int k)
+{
+    int ax, bx, cx, ay, by, cy;
+    iso_affine(k, B - 1, ax, bx, cx, ay, by, cy);
+    const int ox = ay * B + ax, oy = by * B + bx, o0 = cy * B + cx;      // src_k(x, y) = o0 + x * ox + y * oy
+    float kov = 0.0f;
+    for (int y = 0; y < B; y++)
+        for (int x = 0; x < B; x++)
+            kov = __fadd_rn(kov, (float)((int)rt[y * B + x] * ((int)ps[o0 + x * ox + y * oy] - msum)));
+    return kov;
+}
+
+// the scan of k_sweep_rgb over (candidate, isometry): one wave per range block, a lane per pair t = c * 8 + k
+__global__ __launch_bounds__(256) void k_sweep_rgb_iso(const uint16_t* __restrict__ pool_sum,
+                                                       const FicRgbDomStat* __restrict__ dst,
+                                                       const int16_t* __restrict__ rng_t,
+                                                       const FicRgbRngStat* __restrict__ rst,
+                                                       unsigned long long* __restrict__ key, FicGeom g)
+{
+    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int j = blockIdx.x * 4 + wave;
+    if (j >= g.Nr) return;
+    pool_sum += (size_t)blockIdx.y * g.Nd * g.n;                          // blockIdx.y = image of the batch
+    dst += (size_t)blockIdx.y * g.Nd;
+    rng_t += (size_t)blockIdx.y * g.Nr * g.n;
+    rst += (size_t)blockIdx.y * g.Nr;
+    key += (size_t)blockIdx.y * g.Nr;
+    FicRgbRngStat rs = rst[j];
+    const int16_t* rt = rng_t + (size_t)j * g.n;
+    float vRf = (float)rs.vR;
+    uint32_t npair = (uint32_t)(g.wK * g.wK) * 8u;
+    unsigned long long best = FIC_KEY_NONE;
+    for (uint32_t t = (uint32_t)lane; t < npair; t += 64) {
+        int gi = window_to_global(g, j, (int)(t >> 3));
+        FicRgbDomStat ds = dst[gi];
+        float kov = rgb_kovarianz_iso(rt, pool_sum + (size_t)gi * g.n, ds.msum, g.B, (int)(t & 7u));
+        float r = (rs.vR == 0 || ds.vD == 0) ? 0.0f : __fdiv_rn(kov, __fmul_rn(vRf, (float)ds.vD));
+        r = __fmul_rn(r, r);
+        float e = __fmul_rn(__fmul_rn(vRf, vRf), __fsub_rn(1.0f, r));
+        unsigned long long kk = ((unsigned long long)f32_orderable(e) << 32) | t;
+        best = kk < best ? kk : best;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        unsigned long long o = __shfl_xor(best, off, 64);
+        best = o < best ? o : best;
+    }
+    if (lane == 0) key[j] = best;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Full search (wK == Dw == Dh), B = 4 / 8: the k_sweep_fast mapping for the joint-RGB error.
 // k_sweep_rgb gives every lane its own candidate, so a wave-level load touches 64 different pool blocks (2-byte
 // reads, 128-byte stride): fine for the GUI's small windows, 8.8e9 pairs/s on a full pool.  Here lane = range block
@@ -213,6 +270,61 @@ __global__ __launch_bounds__(256) void k_sweep_rgb_fast(const float* __restrict_
     if (j < g.Nr && best != FIC_KEY_NONE) atomicMin(&key[j], best);
 }
 
+// n_iso = 8 twin of k_sweep_rgb_fast.  The range block's greyR_i stay in VGPRs in range order and the domain block is
+// wave-uniform in SGPRs, so isometry k is a compile-time choice of WHICH scalar operand feeds step i: chain k adds
+// greyR_i * greyD[src_k(i)] for i = 0..n-1, the eight chains side by side (independent, so they fill the VALU pipeline).
+// One domain block costs 8 n multiply-adds and 8 epilogues; the key carries d * 8 + k.
+template <int N>
+__global__ __launch_bounds__(256) void k_sweep_rgb_fast_iso(const float* __restrict__ pool_cf, const FicRgbDomStat* __restrict__ dst,
+                                                            const int16_t* __restrict__ rng_t, const FicRgbRngStat* __restrict__ rst,
+                                                            unsigned long long* __restrict__ key, FicGeom g, int chunk_len)
+{
+    constexpr int B = N == 16 ? 4 : 8;
+    const int lane = threadIdx.x & 63;
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);                  // 64 range blocks per wave
+    if (tile * 64 >= g.Nr) return;
+    pool_cf += (size_t)blockIdx.z * g.Nd * N;                             // blockIdx.z = image of the batch
+    dst += (size_t)blockIdx.z * g.Nd;
+    rng_t += (size_t)blockIdx.z * g.Nr * N;
+    rst += (size_t)blockIdx.z * g.Nr;
+    key += (size_t)blockIdx.z * g.Nr;
+    const int j = tile * 64 + lane;
+    const int jj = j < g.Nr ? j : g.Nr - 1;                                // tail lanes shadow the last block
+    const int d0 = blockIdx.y * chunk_len;
+    int d1 = d0 + chunk_len;
+    if (d1 > g.Nd) d1 = g.Nd;
+    float rt[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) rt[i] = (float)rng_t[(size_t)jj * N + i];  // greyR_i, |.| <= 765: exact
+    const FicRgbRngStat rs = rst[jj];
+    const float vRf = (float)rs.vR;
+    const float vR2 = __fmul_rn(vRf, vRf);
+    const AS4 float* pc = (const AS4 float*)pool_cf;
+    const AS4 FicRgbDomStat* ds4 = (const AS4 FicRgbDomStat*)dst;
+    unsigned long long best = FIC_KEY_NONE;
+    for (int d = d0; d < d1; d++) {
+        const AS4 float* gd = pc + (size_t)d * N;
+        float kov[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) kov[k] = __fadd_rn(kov[k], __fmul_rn(rt[i], gd[iso_source(k, B, i % B, i / B)]));
+        }
+        const int vD = ds4[d].vD;
+        const bool zero = rs.vR == 0 || vD == 0;
+        const float den = __fmul_rn(vRf, (float)vD);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            float r = zero ? 0.0f : __fdiv_rn(kov[k], den);                                      // FC:795-800
+            r = __fmul_rn(r, r);
+            const float e = __fmul_rn(vR2, __fsub_rn(1.0f, r));                                  // FC:801-802
+            const unsigned long long kk = ((unsigned long long)f32_orderable(e) << 32) | ((uint32_t)d * 8u + (uint32_t)k);
+            best = kk < best ? kk : best;
+        }
+    }
+    if (j < g.Nr && best != FIC_KEY_NONE) atomicMin(&key[j], best);
+}
+
 // getBestDomainblockRGB tail FC:717-734 + writeData RGB quantiser FC:250-254
 __global__ __launch_bounds__(256) void k_finalize_rgb(const uint16_t* __restrict__ pool_sum,
                                                       const FicRgbDomStat* __restrict__ dst,
@@ -227,12 +339,19 @@ __global__ __launch_bounds__(256) void k_finalize_rgb(const uint16_t* __restrict
         pool_sum += p * g.Nd * g.n; dst += p * g.Nd; rng_t += p * g.Nr * g.n; rst += p * g.Nr; key += p * g.Nr;
         out.idx_local += p * g.Nr; out.idx_global += p * g.Nr; out.a += p * g.Nr; out.bR += p * g.Nr; out.bG += p * g.Nr;
         out.bB += p * g.Nr; out.qrows += p * g.Nr * 5;
+        if (out.iso) out.iso += p * g.Nr;
     }
     int c = (int)(uint32_t)key[j];
+    int k = 0;
+    if (out.iso) {                                      // n_iso = 8: the key carries c * 8 + k
+        k = c & 7;
+        c = (int)((uint32_t)c >> 3);
+    }
     int gi = window_to_global(g, j, c);
     FicRgbDomStat ds = dst[gi];
     FicRgbRngStat rs = rst[j];
-    float kov = rgb_kovarianz(rng_t + (size_t)j * g.n, pool_sum + (size_t)gi * g.n, ds.msum, g.n);
+    float kov = out.iso ? rgb_kovarianz_iso(rng_t + (size_t)j * g.n, pool_sum + (size_t)gi * g.n, ds.msum, g.B, k)
+                        : rgb_kovarianz(rng_t + (size_t)j * g.n, pool_sum + (size_t)gi * g.n, ds.msum, g.n);
     float a = __fdiv_rn(kov, ds.varsq);                 // FC:718
     if (a > 1.0f) a = 1.0f;                             // FC:721-724 (NaN passes)
     if (a < -1.0f) a = -1.0f;
@@ -247,6 +366,7 @@ __global__ __launch_bounds__(256) void k_finalize_rgb(const uint16_t* __restrict
     const float qnan = __uint_as_float(0x7FC00000u);
     out.idx_local[j] = c;
     out.idx_global[j] = gi;
+    if (out.iso) out.iso[j] = k;
     out.a[j] = (a != a) ? qnan : a;
     out.bR[j] = (bR != bR) ? qnan : bR;
     out.bG[j] = (bG != bG) ? qnan : bG;
@@ -263,9 +383,14 @@ __global__ __launch_bounds__(256) void k_collage_rgb(const int32_t* __restrict__
         const size_t p = blockIdx.z;                                      // image of the batch
         scaled += p * g.Ws * g.Hs; collage += p * g.W * g.H;
         out.idx_global += p * g.Nr; out.a += p * g.Nr; out.bR += p * g.Nr; out.bG += p * g.Nr; out.bB += p * g.Nr;
+        if (out.iso) out.iso += p * g.Nr;
     }
     int j = (y / g.B) * g.Rw + (x / g.B);
     int rx = x % g.B, ry = y % g.B;
+    if (out.iso) {                                      // n_iso = 8: the pixel at (rx, ry) takes the domain pixel at src_k(rx, ry)
+        const int sp = iso_source(out.iso[j], g.B, rx, ry);
+        rx = sp % g.B; ry = sp / g.B;
+    }
     int gi = out.idx_global[j];
     int c = gi % g.Dw, r = gi / g.Dw;
     int32_t d = scaled[(size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand + rx];
@@ -282,7 +407,7 @@ __global__ __launch_bounds__(256) void k_collage_rgb(const int32_t* __restrict__
 // decodeRGB paint FC:463-499: a = q1/1000000f, bR = q2/100000f, bG = q3/100000f, bB = (float)q4 (FC:446-450);
 // the squared change of the three channels is summed as an int per pixel before the float add (FC:493).
 __global__ __launch_bounds__(256) void k_decode_paint_rgb(const int32_t* __restrict__ scaled, int32_t* __restrict__ image,
-                                                          const int32_t* __restrict__ qrows5,
+                                                          const int32_t* __restrict__ qrows5, const int32_t* __restrict__ iso,
                                                           FicDecodeState* __restrict__ st, uint32_t* __restrict__ sqbuf,
                                                           int counter, FicGeom g)
 {
@@ -300,7 +425,12 @@ __global__ __launch_bounds__(256) void k_decode_paint_rgb(const int32_t* __restr
             st->bad_index = 1;
         } else {
             int c = gi % g.Dw, r = gi / g.Dw;
-            int32_t d = scaled[(size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand + rx];
+            int sx = rx, sy = ry;
+            if (iso) {                                  // n_iso = 8 codebook of a context: domain pixel at src_k(rx, ry)
+                const int sp = iso_source(iso[j] & 7, g.B, rx, ry);
+                sx = sp % g.B; sy = sp / g.B;
+            }
+            int32_t d = scaled[(size_t)(r * g.abstand + sy) * g.Ws + c * g.abstand + sx];
             int vR, vG, vB;
             rgb_paint_px(cf, d, vR, vG, vB);
             size_t p = (size_t)y * g.W + x;
@@ -338,8 +468,8 @@ int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int3
     hipLaunchKernelGGL(k_range_rgb, dim3((g.Nr + 255) / 256, P), dim3(256), 0, s, (const int32_t*)b.argb, b.rng_t, b.rng_st, g);
     FIC_LAUNCH_CHECK();
     if (g.full && q && q->poolQ) {
-        // full search on the matrix cores (fic_q.hip, k_sweep_q<NK, 3>): the MFMA output prunes, flagged pairs are evaluated
-        // with the reference's sequential f32 sums
+        // full search on the matrix cores (fic_q.hip, k_sweep_q<NK, 3>; 8 isometries: <NK, 4>): the MFMA output prunes, flagged
+        // pairs are evaluated with the reference's sequential f32 sums
         FicGeom g1 = g;
         g1.planes = 1;
         for (size_t p = 0; p < P; p++)
@@ -354,22 +484,22 @@ int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int3
                            (const uint16_t*)b.pool_sum, (const FicRgbDomStat*)b.pool_st, b.pool_cf, g);
         FIC_LAUNCH_CHECK();
         if (hipMemsetAsync(b.key, 0xFF, (size_t)P * g.Nr * sizeof(unsigned long long), s) != hipSuccess) return (int)hipErrorUnknown;
+        const bool iso = g.n_iso == 8;
         const int tiles = (g.Nr + 63) / 64;
-        int nchunks = (8192 + tiles * (int)P - 1) / (tiles * (int)P);      // ~8 waves per SIMD
-        if (nchunks > g.Nd / 64) nchunks = g.Nd / 64;
+        int nchunks = (8192 + tiles * (int)P - 1) / (tiles * (int)P);      // ~8192 waves in flight (8 per SIMD where the registers allow it)
+        const int min_len = iso ? 8 : 64;                                  // a domain block of the 8-isometry kernel is 8 candidates' worth of work
+        if (nchunks > g.Nd / min_len) nchunks = g.Nd / min_len;
         if (nchunks < 1) nchunks = 1;
         const int chunk_len = (g.Nd + nchunks - 1) / nchunks;
         nchunks = (g.Nd + chunk_len - 1) / chunk_len;
         dim3 grid((tiles + 3) / 4, nchunks, P);
-        if (g.B == 4)
-            hipLaunchKernelGGL((k_sweep_rgb_fast<16>), grid, dim3(256), 0, s, (const float*)b.pool_cf, (const FicRgbDomStat*)b.pool_st,
-                               (const int16_t*)b.rng_t, (const FicRgbRngStat*)b.rng_st, b.key, g, chunk_len);
-        else
-            hipLaunchKernelGGL((k_sweep_rgb_fast<64>), grid, dim3(256), 0, s, (const float*)b.pool_cf, (const FicRgbDomStat*)b.pool_st,
-                               (const int16_t*)b.rng_t, (const FicRgbRngStat*)b.rng_st, b.key, g, chunk_len);
+        auto kern = g.B == 4 ? (iso ? k_sweep_rgb_fast_iso<16> : k_sweep_rgb_fast<16>) : (iso ? k_sweep_rgb_fast_iso<64> : k_sweep_rgb_fast<64>);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, (const float*)b.pool_cf, (const FicRgbDomStat*)b.pool_st,
+                           (const int16_t*)b.rng_t, (const FicRgbRngStat*)b.rng_st, b.key, g, chunk_len);
     } else {
-        hipLaunchKernelGGL(k_sweep_rgb, dim3((g.Nr + 3) / 4, P), dim3(256), 0, s, (const uint16_t*)b.pool_sum,
-                           (const FicRgbDomStat*)b.pool_st, (const int16_t*)b.rng_t, (const FicRgbRngStat*)b.rng_st, b.key, g);
+        hipLaunchKernelGGL(g.n_iso == 8 ? k_sweep_rgb_iso : k_sweep_rgb, dim3((g.Nr + 3) / 4, P), dim3(256), 0, s,
+                           (const uint16_t*)b.pool_sum, (const FicRgbDomStat*)b.pool_st, (const int16_t*)b.rng_t,
+                           (const FicRgbRngStat*)b.rng_st, b.key, g);
     }
     FIC_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_finalize_rgb, dim3((g.Nr + 255) / 256, P), dim3(256), 0, s, (const uint16_t*)b.pool_sum,
@@ -394,12 +524,12 @@ int fic_launch_scale_rgb(const int32_t* argb, int32_t* scaled, const FicGeom& g,
 
 // one decodeRGB iteration (FC:458-505): scaleImageRGB of the current image, paint, loop control
 int fic_launch_decode_iteration_rgb(int32_t* scaled, int32_t* image, const int32_t* qrows5, FicDecodeState* state,
-                                    uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
+                                    uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s, const int32_t* iso)
 {
     hipLaunchKernelGGL(k_scale_rgb, dim3((g.Ws + 255) / 256, g.Hs), dim3(256), 0, s, (const int32_t*)image, scaled, g);
     FIC_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_decode_paint_rgb, dim3((g.W + 255) / 256, g.H), dim3(256), 0, s, (const int32_t*)scaled, image,
-                       qrows5, state, sqbuf, counter, g);
+                       qrows5, iso, state, sqbuf, counter, g);
     FIC_LAUNCH_CHECK();
     return fic_launch_decode_step(state, sqbuf, counter, g.W * g.H, 1, s);
 }

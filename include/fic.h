@@ -178,6 +178,27 @@ FIC_API int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* ctx, uint64_t* out8, int reset)
 FIC_API int fic_rgb_ctx_get_results_host(fic_rgb_ctx* ctx, int32_t* idx_local, float* a, float* bR, float* bG, float* bB,
                                          int32_t* qrows5, int32_t* collage_argb);
 FIC_API int fic_rgb_ctx_decode_host(fic_rgb_ctx* ctx, int32_t* argb_out, float* avg_error_out, int* iterations_out);
+/* Joint RGB with the 8 isometries of the square (n_iso = 8; an extension like the grey one: the reference has none).  The
+ * error of getErrorVarianceCovarianceRGB is applied to the explicitly permuted domain block D_k[i] = D[src_k(i)], src_k the
+ * map of the grey extension (k = 0 identity, 1 rot90cw, 2 rot180, 3 rot270cw, 4 mirror L-R, 5 mirror T-B, 6 transpose,
+ * 7 anti-transpose): kovarianz_k = sum_i greyR[i] * greyD[src_k(i)] accumulated in f32 in the range block's order
+ * i = 0..n-1; varianzRange, varianzDomain, varianzSquare and the channel means are those of the unpermuted block.  Scan:
+ * candidates in window order and k = 0..7 inside a candidate, strict '<' (a tie goes to the lower (c, k)).  The collage and
+ * the decoder paint pixel (rx, ry) of a range block from the domain pixel at src_k(rx, ry).
+ *   n_iso   1 or 8 (FIC_E_ARGUMENT otherwise, before any device work); 1 gives the bits of the entries above
+ *   iso     [N_r] winning isometry (all 0 with n_iso = 1); may be NULL.  qrows5 keeps its shape: the .run format has no
+ *           isometry column, so an n_iso = 8 codebook is decoded from its context (fic_rgb_ctx_decode_host), not from a stream
+ * Sweep policy: that of fic_rgb_ctx_encode with the pair count times 8 -- the matrix-core sweep ("k_sweep_q<NK, 4, ..>" /
+ * "k_sweep_qs<NK, 4>": 8 permuted range columns per block, flagged pairs evaluated exactly in the range block's order) for full
+ * search when 8 N_r N_d >= 3e7 or B = 16, else the VALU sweeps ("k_sweep_rgb_fast_iso<n>": full search at B = 4 / 8,
+ * "k_sweep_rgb_iso": windowed search); "sweep", FIC_RGB_SWEEP, "chunks", "q_eshift" and "sweep_stats" work as with n_iso = 1, all
+ * choices give the same bits.  A window of 2^28 or more candidates is FIC_E_GEOMETRY (the search key carries c * 8 + k). */
+FIC_API int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
+                                    float* a, float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5,
+                                    int32_t* collage_argb);
+FIC_API fic_rgb_ctx* fic_rgb_ctx_create_iso(int device, int w, int h, int B, int wK, int n_iso, int planes);
+/* iso [planes][N_r] of the last encode (zeros on an n_iso = 1 context) */
+FIC_API int fic_rgb_ctx_get_iso_host(fic_rgb_ctx* ctx, int32_t* iso);
 
 /* writeData, RGB branch (FractalCompression.java:230-238, 248-257): header {1,w,h,B,wK} + 5 ints per row. */
 FIC_API int64_t fic_write_run_rgb(const int32_t* qrows5, int n_ranges, int w, int h, int B, int wK, uint8_t* out,
@@ -382,7 +403,8 @@ FIC_API int fic_ctx_debug_pool_host(fic_ctx* ctx, uint8_t* pix, uint32_t* sum, u
 FIC_API int fic_ctx_debug_q_host(fic_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 /* Test hook, joint RGB: the same for the matrix-core RGB sweep ("sweep" = 2) of the LAST plane encoded: which = 0 A fragments
  * [domain tiles + padding][NK][64] x 8 f16, 1 flat-tile flags, 2 B fragments [column tiles + padding][NK][64] x 8 f16, 3 E_r f32 [N_r],
- * 4 {0, varianzRange} i32 pairs [N_r], 5 Amax (f32 bits, one u32). */
+ * 4 {0, varianzRange} i32 pairs [N_r], 5 Amax (f32 bits, one u32).  On an n_iso = 8 context the B fragments hold 8 adjacent
+ * columns per range block, column 8 j + k the copy c_k of range j with c_k[src_k(i)] = greyR[i]; the other stores are unchanged. */
 FIC_API int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 
 #ifdef __cplusplus
