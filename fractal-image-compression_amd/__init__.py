@@ -8,10 +8,15 @@ from . import capi, synth, sharding
 from .capi import FicError, declared_symbols, geometry, write_run_gray, decode_gray_run, decode_rgb_run, encode_rgb, write_run_rgb
 from .capi import encode_gray_quadtree, write_run_quadtree, decode_quadtree_run
 from .capi import encode_rgb_quadtree, write_run_rgb_quadtree, decode_rgb_quadtree_run
+from .capi import write_run_gray_iso, write_run_rgb_iso, decode_gray_iso_run, decode_rgb_iso_run
+from .capi import encode_rgb_quadtree_iso, write_run_rgb_quadtree_iso, decode_rgb_quadtree_iso_run, debug_rgb_quadtree_iso_sse
+from .capi import RgbEncoder
 from .host import Encoder, FractalCompression, RasterImage, encode_gray, encode_rgb_per_channel
 from .sharding import ShardedEncoder, shard_spans, shard_planes, gather_records, pack_records, unpack_records
 
 __all__ = ["capi", "synth", "sharding", "FicError", "declared_symbols", "geometry", "write_run_gray", "decode_gray_run", "decode_rgb_run", "encode_rgb", "write_run_rgb", "Encoder",
            "FractalCompression", "RasterImage", "encode_gray", "ShardedEncoder", "shard_spans", "shard_planes",
            "gather_records", "pack_records", "unpack_records", "encode_gray_quadtree", "write_run_quadtree",
-           "decode_quadtree_run", "encode_rgb_quadtree", "write_run_rgb_quadtree", "decode_rgb_quadtree_run"]
+           "decode_quadtree_run", "encode_rgb_quadtree", "write_run_rgb_quadtree", "decode_rgb_quadtree_run",
+           "write_run_gray_iso", "write_run_rgb_iso", "decode_gray_iso_run", "decode_rgb_iso_run", "encode_rgb_quadtree_iso",
+           "write_run_rgb_quadtree_iso", "decode_rgb_quadtree_iso_run", "debug_rgb_quadtree_iso_sse", "RgbEncoder"]

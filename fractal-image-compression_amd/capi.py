@@ -134,6 +134,15 @@ def lib():
         "fic_decode_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
         "fic_decode_rgb_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
         "fic_ctx_decode_zoom_host": (C.c_int, [vp, C.c_int, u8p, f32p, ip]),
+        "fic_rgb_ctx_decode_zoom_host": (C.c_int, [vp, C.c_int, i32p, f32p, ip]),
+        "fic_write_run_gray_iso": (C.c_int64, [i32p, i32p] + [C.c_int] * 5 + [u8p, C.c_int64]),
+        "fic_write_run_rgb_iso": (C.c_int64, [i32p, i32p] + [C.c_int] * 5 + [u8p, C.c_int64]),
+        "fic_decode_gray_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_decode_rgb_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_encode_rgb_quadtree_iso_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_write_run_rgb_quadtree_iso": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
+        "fic_decode_rgb_quadtree_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
+        "fic_debug_rgb_quadtree_iso_sse": (C.c_int, [i32p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -403,13 +412,17 @@ class RgbEncoder:
             r["collage"] = col
         return r
 
-    def decode(self):
-        """decodeRGB from the context's quantised rows: (argb int32 [planes, H*W], avgError float32 [planes], iterations)."""
-        P = self.planes
-        out = np.zeros((P, self.height * self.width), np.int32)
+    def decode(self, zoom=1):
+        """decodeRGB from the context's quantised rows: (argb int32 [planes, H*W], avgError float32 [planes], iterations).
+        zoom = 2 / 4: on the geometry (zoom*w, zoom*h, zoom*B, wK), [planes, zoom*H * zoom*W] out (fic_rgb_ctx_decode_zoom_host)."""
+        P, z = self.planes, int(zoom)
+        out = np.zeros((P, self.height * self.width * (z * z if z in (1, 2, 4) else 1)), np.int32)
         avg = np.zeros(P, np.float32)
         it = np.zeros(P, np.int32)
-        check(lib().fic_rgb_ctx_decode_host(self._h, ptr(out, C.c_int32), ptr(avg, C.c_float), ptr(it, C.c_int)))
+        if z == 1:
+            check(lib().fic_rgb_ctx_decode_host(self._h, ptr(out, C.c_int32), ptr(avg, C.c_float), ptr(it, C.c_int)))
+        else:
+            check(lib().fic_rgb_ctx_decode_zoom_host(self._h, z, ptr(out, C.c_int32), ptr(avg, C.c_float), ptr(it, C.c_int)))
         return out, avg, it
 
 
@@ -571,3 +584,87 @@ def decode_rgb_quadtree_run(run, device=0, avg_error_in=0.0, zoom=1):
     check(lib().fic_decode_rgb_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_int32), cap, C.byref(wo),
                                             C.byref(ho), C.byref(avg), C.byref(it)))
     return out[:cap].reshape(h, w), np.float32(avg.value), it.value
+
+
+# ---- streams with an isometry column: tags 4 and 5 (fixed B), tag 6 (colour quadtree) --------------------------
+def _write_run_iso(fn, rows, iso, QW, w, h, B, wK):
+    q = np.ascontiguousarray(rows, np.int32).reshape(-1, QW)
+    k = np.ascontiguousarray(iso, np.int32).reshape(-1)
+    if k.size != q.shape[0]:
+        raise FicError(-3, "one isometry per row")
+    out = np.zeros(24 + 4 * (QW + 1) * q.shape[0], np.uint8)
+    n = fn(ptr(q, C.c_int32), ptr(k, C.c_int32), q.shape[0], w, h, B, wK, ptr(out, C.c_uint8), out.size)
+    check(int(n))
+    return out[:int(n)].tobytes()
+
+
+def write_run_gray_iso(qrows, iso, w, h, B, wK):
+    """Grey fixed-B stream with an isometry column (tag 4): header {4, w, h, 0, B, wK}, then {idx_local, qa, qb, iso} per range
+    block, big-endian int32 (fic_write_run_gray_iso).  iso: int [N_r] in 0..7 (zeros for an n_iso = 1 codebook)."""
+    return _write_run_iso(lib().fic_write_run_gray_iso, qrows, iso, 3, w, h, B, wK)
+
+
+def write_run_rgb_iso(qrows5, iso, w, h, B, wK):
+    """Colour fixed-B stream with an isometry column (tag 5): header {5, w, h, 0, B, wK}, then {idx_local, q1, q2, q3, q4, iso} per
+    range block (fic_write_run_rgb_iso)."""
+    return _write_run_iso(lib().fic_write_run_rgb_iso, qrows5, iso, 5, w, h, B, wK)
+
+
+def decode_gray_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
+    """Decoder of a tag-4 stream on the GPU (fic_decode_gray_iso_run): (gray uint8 [zoom*H, zoom*W], avgError float32 after the
+    call, iterations)."""
+    out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_gray_iso_run, run, 24, "run stream", np.uint8, device, avg_error_in, zoom)
+    return out.reshape(h, w), avg, it
+
+
+def decode_rgb_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
+    """Decoder of a tag-5 stream on the GPU (fic_decode_rgb_iso_run): (argb int32 [zoom*H * zoom*W], avgError float32, iterations,
+    zoom*w, zoom*h) like decode_rgb_run."""
+    return _decode_run_zoom(lib().fic_decode_rgb_iso_run, run, 24, "run stream", np.int32, device, avg_error_in, zoom)
+
+
+QT_RGB_ISO_LEAF_FIELDS = QT_RGB_LEAF_FIELDS + ("iso",)
+
+
+def encode_rgb_quadtree_iso(argb, w, h, B_max, B_min, wK=0, n_iso=8, threshold=float("inf"), device=0):
+    """Joint-RGB quadtree encode with n_iso = 1 or 8 isometries (fic_encode_rgb_quadtree_iso_argb): the leaf table int32
+    [n_leaves, 9] with the columns QT_RGB_ISO_LEAF_FIELDS, in stream order.  n_iso = 1: encode_rgb_quadtree's rows and iso = 0."""
+    a = _argb_image(argb, w, h)
+    cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
+    out = np.zeros((max(cap, 1), 9), np.int32)
+    n = C.c_int()
+    check(lib().fic_encode_rgb_quadtree_iso_argb(ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso, float(threshold), device,
+                                                 ptr(out, C.c_int32), out.shape[0], C.byref(n)))
+    return out[:n.value].copy()
+
+
+def debug_rgb_quadtree_iso_sse(argb, w, h, B_max, B_min, wK=0, n_iso=8, device=0):
+    """Per-level collage SSE of encode_rgb_quadtree_iso: {B: uint32 [Rh, Rw]} (fic_debug_rgb_quadtree_iso_sse)."""
+    a = _argb_image(argb, w, h)
+    levels = _qt_levels(B_max, B_min)
+    sizes = [(h // B) * (w // B) for B in levels]
+    out = np.zeros(max(sum(sizes), 1), np.uint32)
+    check(lib().fic_debug_rgb_quadtree_iso_sse(ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso, device, ptr(out, C.c_uint32), out.size))
+    r, o = {}, 0
+    for B, n in zip(levels, sizes):
+        r[B] = out[o:o + n].reshape(h // B, w // B)
+        o += n
+    return r
+
+
+def write_run_rgb_quadtree_iso(leaves, w, h, B_max, B_min, wK):
+    """Colour quadtree stream with an isometry column (tag 6): header {6, w, h, 0, B_max, B_min, wK, n_leaves}, then {B, idx_local,
+    q1, q2, q3, q4, iso} per leaf (fic_write_run_rgb_quadtree_iso).  `leaves`: int32 [n, 9] as encode_rgb_quadtree_iso returns it."""
+    q = np.ascontiguousarray(leaves, np.int32).reshape(-1, 9)
+    out = np.zeros(32 + 28 * q.shape[0], np.uint8)
+    n = lib().fic_write_run_rgb_quadtree_iso(ptr(q, C.c_int32), q.shape[0], w, h, B_max, B_min, wK, ptr(out, C.c_uint8), out.size)
+    check(int(n))
+    return out.tobytes()
+
+
+def decode_rgb_quadtree_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
+    """Decoder of a tag-6 stream on the GPU (fic_decode_rgb_quadtree_iso_run): (argb int32 [zoom*H, zoom*W], avgError float32
+    after the call, iterations)."""
+    out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_rgb_quadtree_iso_run, run, 32, "colour quadtree stream", np.int32, device,
+                                          avg_error_in, zoom)
+    return out.reshape(h, w), avg, it

@@ -1,5 +1,6 @@
 // fic_capi_decode.cpp -- C ABI, decoder entries: FractalCompression.decode on .run streams (FC:547-553 -> decodeGreyScale
-// FC:356-421, decodeRGB FC:430-508) and the decode of a context's own codebook.  Host-side orchestration only.
+// FC:356-421, decodeRGB FC:430-508), the decode of a context's own codebook, and the fixed-B streams with an isometry column
+// (tags 4 and 5: writers and decoders).  Host-side orchestration only.
 #include "fic_internal.h"
 
 using namespace ficd;
@@ -316,6 +317,140 @@ int fic_decode_rgb_run(const uint8_t* run, int64_t len, int device, int32_t* arg
                        int* w_out, int* h_out, float* avg_error_io, int* iterations)
 {
     return fic_decode_rgb_run_zoom(run, len, 1, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
+}
+
+// ---- fixed-B streams with an isometry column: tags 4 (grey) and 5 (colour), DESIGN.md 4.17 ------------------------------------
+// Header {tag, w, h, 0, B, wK} -- the 0 where a .run holds its block size, so no older reader takes the stream --, then per
+// range block in scanline order its quantised row and its isometry 0..7.
+}  // extern "C"
+
+namespace {
+constexpr int kIsoHeaderInts = 6;
+struct IsoStream {
+    int tag, QW;             // ints of a quantised row: 3 grey {idx_local, qa, qb}, 5 colour {idx_local, q1, q2, q3, q4}
+    const char *writer, *reader;
+};
+constexpr IsoStream kIsoGrey{4, 3, "fic_write_run_gray_iso", "fic_decode_gray_iso_run"},
+                    kIsoRgb{5, 5, "fic_write_run_rgb_iso", "fic_decode_rgb_iso_run"};
+
+int64_t write_iso_run(const IsoStream& S, const int32_t* qrows, const int32_t* iso, int n_ranges, int w, int h, int B, int wK,
+                      uint8_t* out, int64_t capacity)
+{
+    if (!qrows || !iso || !out) return fail(FIC_E_ARGUMENT, "%s: null argument", S.writer);
+    FicGeom g;
+    const int rc = make_geometry(w, h, B, wK, 1, 1, &g);
+    if (rc) return rc;
+    if (n_ranges != g.Nr) return fail(FIC_E_ARGUMENT, "%s: %d rows, the %dx%d image has %d range blocks of side %d", S.writer, n_ranges, w, h, g.Nr, B);
+    for (int j = 0; j < g.Nr; j++)
+        if (iso[j] < 0 || iso[j] > 7) return fail(FIC_E_ARGUMENT, "%s: row %d: isometry %d outside 0..7", S.writer, j, iso[j]);
+    const int per = S.QW + 1;
+    const int64_t need = 4 * (kIsoHeaderInts + per * (int64_t)g.Nr);
+    if (capacity < need) return fail(FIC_E_CAPACITY, "%s: need %lld bytes, have %lld", S.writer, (long long)need, (long long)capacity);
+    const int32_t hdr[kIsoHeaderInts] = {S.tag, w, h, 0, B, wK};
+    for (int i = 0; i < kIsoHeaderInts; i++) put_be32(out + 4 * i, hdr[i]);
+    uint8_t* p = out + 4 * kIsoHeaderInts;
+    for (int j = 0; j < g.Nr; j++) {
+        for (int k = 0; k < S.QW; k++, p += 4) put_be32(p, qrows[(size_t)S.QW * j + k]);
+        put_be32(p, iso[j]);
+        p += 4;
+    }
+    return need;
+}
+
+// Reader + decoder: the stream checked on the host, rows and isometries uploaded, then the loop of the stream's twin
+// (fic_decode_gray_run_zoom / fic_decode_rgb_run_zoom) with the isometry column handed to the paint kernel.
+template <typename Px>
+int decode_iso_run(const IsoStream& S, const uint8_t* run, int64_t len, int zoom, int device, Px* out, int64_t capacity, int* w_out,
+                   int* h_out, float* avg_error_io, int* iterations)
+{
+    constexpr bool kRgb = sizeof(Px) == 4;
+    if (!run || len < 4 * kIsoHeaderInts) return fail(FIC_E_ARGUMENT, "%s: stream shorter than the 24-byte header", S.reader);
+    int32_t hd[kIsoHeaderInts];
+    for (int i = 0; i < kIsoHeaderInts; i++) hd[i] = get_be32(run + 4 * i);
+    if (hd[0] != S.tag || hd[3] != 0)
+        return fail(FIC_E_ARGUMENT, "%s: header starts {%d, .., .., %d}, this stream has {%d, w, h, 0}", S.reader, hd[0], hd[3], S.tag);
+    const int w0 = hd[1], h0 = hd[2], B = hd[4], wK = hd[5];
+    FicGeom g0, g;
+    int rc = make_geometry(w0, h0, B, wK, 1, 1, &g0);
+    if (rc) return rc;
+    const int per = S.QW + 1;
+    const int64_t need = 4 * (kIsoHeaderInts + per * (int64_t)g0.Nr);
+    if (len != need)
+        return fail(FIC_E_ARGUMENT, "%s: %lld bytes, %d range blocks need exactly %lld", S.reader, (long long)len, g0.Nr, (long long)need);
+    std::vector<int32_t> q((size_t)g0.Nr * S.QW), iso((size_t)g0.Nr);
+    const uint8_t* p = run + 4 * kIsoHeaderInts;
+    for (int j = 0; j < g0.Nr; j++) {
+        for (int k = 0; k < S.QW; k++, p += 4) q[(size_t)S.QW * j + k] = get_be32(p);
+        iso[j] = get_be32(p);
+        p += 4;
+        const int idx = q[(size_t)S.QW * j];
+        if (idx < 0 || idx >= wK * wK || iso[j] < 0 || iso[j] > 7)
+            return fail(FIC_E_ARGUMENT, "%s: row %d: idx_local %d outside the %dx%d window or isometry %d outside 0..7", S.reader, j, idx, wK, wK, iso[j]);
+    }
+    rc = make_decode_geometry(w0, h0, B, wK, 1, 1, zoom, &g);
+    if (rc) return rc;
+    const int w = g.W, h = g.H;
+    if (w_out) *w_out = w;
+    if (h_out) *h_out = h;
+    const size_t npix = (size_t)w * h;
+    if (!out || capacity < (int64_t)npix) return fail(FIC_E_CAPACITY, "%s: output needs %zu pixels", S.reader, npix);
+    rc = check_device(device);
+    if (rc) return rc;
+    const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g.Ws * g.Hs * sizeof(Px)), o_q = o_image + align256(npix * sizeof(Px)),
+                 o_iso = o_q + align256(q.size() * 4), o_state = o_iso + align256(iso.size() * 4),
+                 o_sq = o_state + align256(sizeof(FicDecodeState)), total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
+    Arena ar;
+    rc = arena_take(device, total, &ar);
+    if (rc) return rc;
+    Px* d_scaled = (Px*)(ar.base + o_scaled);
+    Px* d_image = (Px*)(ar.base + o_image);
+    int32_t* d_q = (int32_t*)(ar.base + o_q);
+    int32_t* d_iso = (int32_t*)(ar.base + o_iso);
+    FicDecodeState* d_state = (FicDecodeState*)(ar.base + o_state);
+    uint32_t* d_sq = (uint32_t*)(ar.base + o_sq);
+    hipError_t e = hipMemcpy(d_q, q.data(), q.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_iso, iso.data(), iso.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s: %s", S.reader, hipGetErrorString(e));
+    float avg = avg_error_io ? *avg_error_io : 0.0f;
+    if (rc == FIC_OK)
+        rc = decode_loop(kRgb ? kDecodeRgb : kDecodeGrey, 1, npix, d_image, d_state, &avg, &avg, iterations, nullptr, nullptr, [&](int counter) {
+            if constexpr (kRgb) return fic_launch_decode_iteration_rgb(d_scaled, d_image, d_q, d_state, d_sq, counter, g, nullptr, d_iso);
+            else return fic_launch_decode_iteration(d_scaled, d_image, d_q, d_iso, d_state, d_sq, counter, g, nullptr);
+        });
+    if (rc == FIC_OK) {
+        e = hipMemcpy(out, d_image, npix * sizeof(Px), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s: %s", S.reader, hipGetErrorString(e));
+    }
+    if (rc == FIC_OK && avg_error_io) *avg_error_io = avg;
+    arena_give(ar);
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t fic_write_run_gray_iso(const int32_t* qrows, const int32_t* iso, int n_ranges, int w, int h, int B, int wK, uint8_t* out,
+                               int64_t capacity)
+{
+    return write_iso_run(kIsoGrey, qrows, iso, n_ranges, w, h, B, wK, out, capacity);
+}
+
+int64_t fic_write_run_rgb_iso(const int32_t* qrows5, const int32_t* iso, int n_ranges, int w, int h, int B, int wK, uint8_t* out,
+                              int64_t capacity)
+{
+    return write_iso_run(kIsoRgb, qrows5, iso, n_ranges, w, h, B, wK, out, capacity);
+}
+
+int fic_decode_gray_iso_run(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity, int* w_out,
+                            int* h_out, float* avg_error_io, int* iterations)
+{
+    return decode_iso_run<uint8_t>(kIsoGrey, run, len, zoom, device, gray_out, capacity, w_out, h_out, avg_error_io, iterations);
+}
+
+int fic_decode_rgb_iso_run(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out, int64_t capacity_pixels, int* w_out,
+                           int* h_out, float* avg_error_io, int* iterations)
+{
+    return decode_iso_run<int32_t>(kIsoRgb, run, len, zoom, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // fic_capi_quadtree.cpp -- C ABI, quadtree (variable block size) codec, grey and joint RGB: encode every level with the
-// one-shot machinery, collage SSE + split + compaction on the device (fic_quadtree.hip), the tag-2 (grey) and tag-3 (colour)
-// stream writers / readers, and the decoders of leaves of mixed size.  Host-side orchestration only.  Semantics: DESIGN.md
-// sections 4.13 (grey) and 4.14 (colour).
+// one-shot machinery, collage SSE + split + compaction on the device (fic_quadtree.hip), the tag-2 (grey), tag-3 (colour) and
+// tag-6 (colour with an isometry column) stream writers / readers, and the decoders of leaves of mixed size.  Host-side
+// orchestration only.  Semantics: DESIGN.md sections 4.13 (grey), 4.14 (colour) and 4.17 (colour with the 8 isometries).
 #include "fic_internal.h"
 
 using namespace ficd;
@@ -9,7 +9,7 @@ using namespace ficd;
 namespace {
 
 constexpr int kQtMaxLevels = 3;   // 16 -> 8 -> 4
-constexpr int kQtHeaderInts = 8;  // {2, w, h, B_max, B_min, wK, n_iso, n_leaves}; colour: {3, w, h, 0, B_max, B_min, wK, n_leaves}
+constexpr int kQtHeaderInts = 8;  // {2, w, h, B_max, B_min, wK, n_iso, n_leaves}; colour: {3 or 6, w, h, 0, B_max, B_min, wK, n_leaves}
 
 // The levels B_max, B_max / 2, ..., B_min and their geometries (wK = 0: full search at every level, wK_B = Dw_B).
 struct QtLevels {
@@ -82,7 +82,7 @@ bool qt_tile(const QtLevels& L, int n, S side, E emit)
     return i == n;
 }
 
-// ---- the host side of a pixel format (QtGrey / QtRgb, fic_launch.h) ------------------------------------------------------
+// ---- the host side of a pixel format (QtGrey / QtRgb / QtRgbIso, fic_launch.h) --------------------------------------------
 // The one-shot contexts an encode runs its levels through, their device buffers, the stream layout and the public names.
 struct QtHeader {
     int w, h, B_max, B_min, wK, n_iso, n;
@@ -126,6 +126,15 @@ struct QtGreyHost : QtGrey {
         return FIC_OK;
     }
     static int levels_refused(int rc) { return rc; }
+    static bool row_ok(const int32_t*) { return true; }              // the writer takes the iso column as it is
+    // the leaf's row from the stream ints behind {B, idx_local}: {qa, qb[, iso]} -> q = {qa, qb, iso, 0}; returns the isometry
+    static int fill(Leaf& e, const uint8_t* r, int n_iso)
+    {
+        e.q[0] = get_be32(r);
+        e.q[1] = get_be32(r + 4);
+        e.q[2] = n_iso == 8 ? get_be32(r + 8) : 0;
+        return e.q[2];
+    }
 };
 
 struct QtRgbHost : QtRgb {
@@ -166,6 +175,58 @@ struct QtRgbHost : QtRgb {
         return FIC_OK;
     }
     static int levels_refused(int) { return fail(FIC_E_ARGUMENT, "%s: %s", kReader, g_err.c_str()); }
+    static bool row_ok(const int32_t*) { return true; }
+    static int fill(Leaf& e, const uint8_t* r, int)                  // {q1, q2, q3, q4}, no isometry
+    {
+        for (int k = 0; k < 4; k++) e.q[k] = get_be32(r + 4 * k);
+        return 0;
+    }
+};
+
+// Colour with an isometry column: the joint-RGB contexts of n_iso = 1 or 8, tag 6.  The stream always holds
+// the column (zeros for an n_iso = 1 codebook) and its reader takes every isometry 0..7.
+struct QtRgbIsoHost : QtRgbIso {
+    using Dev = QtRgbIso;
+    using Ctx = fic_rgb_ctx;
+    static constexpr const char *kKind = "colour quadtree (isometries)", *kWriter = "fic_write_run_rgb_quadtree_iso",
+                                *kReader = "fic_decode_rgb_quadtree_iso_run";
+    static constexpr const DecodeKind& kDecode = kDecodeRgb;
+    static Ctx* take(int device, const FicGeom& g)
+    {
+        Ctx* c = rgb_cache_take(device, g.W, g.H, g.B, g.wK, g.n_iso);
+        return c ? c : fic_rgb_ctx_create_iso(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
+    }
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's
+    static void give(Ctx* c, bool ok) { QtRgbHost::give(c, ok); }
+    static int prepare(Ctx*) { return 0; }
+    static QtViews<Px> views(const Ctx* c, const Ctx*)
+    {
+        QtViews<Px> v{};
+        rgb_ctx_views(c, &v.image, &v.scaled, &v.qrows, &v.iso);
+        return v;
+    }
+    static int scale(const Px* image, Px* scaled, const FicGeom& g) { return fic_launch_scale_rgb(image, scaled, g, nullptr); }
+    static int run_ints(int) { return 7; }                           // stream row {B, idx_local, q1, q2, q3, q4, iso}
+    static void pack(const QtHeader& H, int32_t* hd)
+    {
+        const int32_t v[kQtHeaderInts] = {6, H.w, H.h, 0, H.B_max, H.B_min, H.wK, H.n};
+        memcpy(hd, v, sizeof(v));
+    }
+    static int unpack(const int32_t* hd, QtHeader* H)
+    {
+        if (hd[0] != 6 || hd[3] != 0)
+            return fail(FIC_E_ARGUMENT, "%s: header starts {%d, .., .., %d}, a colour quadtree stream with isometries has {6, w, h, 0}",
+                        kReader, hd[0], hd[3]);
+        *H = QtHeader{hd[1], hd[2], hd[4], hd[5], hd[6], 8, hd[7]};
+        return FIC_OK;
+    }
+    static int levels_refused(int rc) { return rc; }                 // bad levels FIC_E_ARGUMENT, else the geometry's / window's own code
+    static bool row_ok(const int32_t* leaf) { return leaf[8] >= 0 && leaf[8] <= 7; }
+    static int fill(Leaf& e, const uint8_t* r, int)                  // {q1, q2, q3, q4, iso}
+    {
+        for (int k = 0; k < 4; k++) e.q[k] = get_be32(r + 4 * k);
+        return e.k = get_be32(r + 16);
+    }
 };
 
 // The encode behind fic_encode_*_quadtree_* and the SSE test hooks: every level through the one-shot contexts, then the
@@ -257,6 +318,8 @@ int64_t qt_write_run(const int32_t* leaves, int n_leaves, int w, int h, int B_ma
         return leaves[LW * i + 0] == x && leaves[LW * i + 1] == y;
     });
     if (!tiles) return fail(FIC_E_ARGUMENT, "%s: the leaves do not tile the %dx%d image in quadtree order", Fmt::kWriter, w, h);
+    for (int i = 0; i < n_leaves; i++)
+        if (!Fmt::row_ok(leaves + LW * i)) return fail(FIC_E_ARGUMENT, "%s: leaf %d: isometry outside 0..7", Fmt::kWriter, i);
     const int per = Fmt::run_ints(n_iso);
     const int64_t need = 4 * (kQtHeaderInts + per * (int64_t)n_leaves);
     if (capacity < need) return fail(FIC_E_CAPACITY, "%s: need %lld bytes, have %lld", Fmt::kWriter, (long long)need, (long long)capacity);
@@ -299,15 +362,17 @@ int qt_decode_run(const uint8_t* run, int64_t len, int zoom, int device, typenam
     if (len != need)
         return fail(FIC_E_ARGUMENT, "%s: %lld bytes, %d leaves need exactly %lld", Fmt::kReader, (long long)len, n, (long long)need);
     const uint8_t* rows = run + 4 * kQtHeaderInts;
-    std::vector<FicQtLeaf> lv[kQtMaxLevels];
+    using Leaf = typename Fmt::Leaf;
+    std::vector<Leaf> lv[kQtMaxLevels];
     int sqoff = 0;
     const bool ok = qt_tile(L, n, [&](int i) { return get_be32(rows + 4 * per * (size_t)i); }, [&](int i, int x, int y, int l) {
         const FicGeom& g = L.g[l];
         const uint8_t* r = rows + 4 * per * (size_t)i;
         const int idx = get_be32(r + 4);
-        FicQtLeaf e{zoom * x, zoom * y, 0, sqoff, {0, 0, 0, 0}};
-        for (int k = 2; k < per; k++) e.q[k - 2] = get_be32(r + 4 * k);
-        if (idx < 0 || idx >= g.wK * g.wK || (Fmt::kIso && (e.q[2] < 0 || e.q[2] >= H.n_iso))) return false;
+        Leaf e{};
+        e.x = zoom * x; e.y = zoom * y; e.sqoff = sqoff;
+        const int iso = Fmt::fill(e, r + 8, H.n_iso);
+        if (idx < 0 || idx >= g.wK * g.wK || iso < 0 || iso >= H.n_iso) return false;
         e.gi = host_window_to_global(g, (y / g.B) * g.Rw + x / g.B, idx);
         if (e.gi < 0 || e.gi >= g.Nd) return false;
         lv[l].push_back(e);
@@ -327,14 +392,14 @@ int qt_decode_run(const uint8_t* run, int64_t len, int zoom, int device, typenam
     size_t o_lv[kQtMaxLevels];
     const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g0.Ws * g0.Hs * sizeof(Px));
     size_t off = o_image + align256(npix * sizeof(Px));
-    for (int l = 0; l < L.nl; l++) { o_lv[l] = off; off += align256((lv[l].size() + 1) * sizeof(FicQtLeaf)); }
+    for (int l = 0; l < L.nl; l++) { o_lv[l] = off; off += align256((lv[l].size() + 1) * sizeof(Leaf)); }
     const size_t o_state = off, o_sq = o_state + align256(sizeof(FicDecodeState)), total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
     Arena ar;
     rc = arena_take(device, total, &ar);
     if (rc) return rc;
     for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
         if (lv[l].empty()) continue;
-        hipError_t e = hipMemcpy(ar.base + o_lv[l], lv[l].data(), lv[l].size() * sizeof(FicQtLeaf), hipMemcpyHostToDevice);
+        hipError_t e = hipMemcpy(ar.base + o_lv[l], lv[l].data(), lv[l].size() * sizeof(Leaf), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s: %s", Fmt::kReader, hipGetErrorString(e));
     }
     Px* d_scaled = (Px*)(ar.base + o_scaled);
@@ -347,7 +412,7 @@ int qt_decode_run(const uint8_t* run, int64_t len, int zoom, int device, typenam
         rc = decode_loop(Fmt::kDecode, 1, npix, d_image, d_state, &avg, &avg, iterations, nullptr, nullptr, [&](int counter) {
             if (Fmt::scale(d_image, d_scaled, g0)) return -1;
             for (int l = 0; l < L.nl; l++)
-                if (fic_launch_decode_paint_leaves<typename Fmt::Dev>(d_scaled, d_image, (const FicQtLeaf*)(ar.base + o_lv[l]),
+                if (fic_launch_decode_paint_leaves<typename Fmt::Dev>(d_scaled, d_image, (const Leaf*)(ar.base + o_lv[l]),
                                                                       (int)lv[l].size(), d_state, d_sq, counter, Z.g[l], nullptr))
                     return -1;
             return fic_launch_decode_step(d_state, d_sq, counter, (int)npix, 1, nullptr);
@@ -434,6 +499,33 @@ int fic_decode_rgb_quadtree_run(const uint8_t* run, int64_t len, int device, int
                                 int* h_out, float* avg_error_io, int* iterations)
 {
     return fic_decode_rgb_quadtree_run_zoom(run, len, 1, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
+}
+
+// ---- colour with the 8 isometries ------------------------------------------------------------------------
+int fic_encode_rgb_quadtree_iso_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                     int device, int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_iso_argb: null argument");
+    return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_debug_rgb_quadtree_iso_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,
+                                   uint32_t* sse, int64_t capacity)
+{
+    if (!argb || !sse) return fail(FIC_E_ARGUMENT, "fic_debug_rgb_quadtree_iso_sse: null argument");
+    return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, __builtin_inff(), device, nullptr, 0, nullptr, sse, capacity);
+}
+
+int64_t fic_write_run_rgb_quadtree_iso(const int32_t* leaves, int n_leaves, int w, int h, int B_max, int B_min, int wK, uint8_t* out,
+                                       int64_t capacity)
+{
+    return qt_write_run<QtRgbIsoHost>(leaves, n_leaves, w, h, B_max, B_min, wK, 8, out, capacity);
+}
+
+int fic_decode_rgb_quadtree_iso_run(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out, int64_t capacity_pixels,
+                                    int* w_out, int* h_out, float* avg_error_io, int* iterations)
+{
+    return qt_decode_run<QtRgbIsoHost>(run, len, zoom, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
 }
 
 }  // extern "C"

@@ -394,34 +394,62 @@ int fic_rgb_ctx_get_iso_host(fic_rgb_ctx* c, int32_t* iso)
     return FIC_OK;
 }
 
-// decodeRGB (FC:430-508) from the context's quantised rows, plane by plane, everything device resident
-int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_out, int* iterations_out)
+// decodeRGB (FC:430-508) from the context's quantised rows, plane by plane, everything device resident.  zoom = 1 runs in the
+// context's own scratch; a zoomed decode takes an arena of the zoomed size (as fic_ctx_decode_zoom_host does).
+int fic_rgb_ctx_decode_zoom_host(fic_rgb_ctx* c, int zoom, int32_t* argb_out, float* avg_error_out, int* iterations_out)
 {
-    if (!c || !argb_out) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_decode_host: null argument");
+    if (!c || !argb_out) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_decode_zoom_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->encoded_any) return fail(FIC_E_STATE, "fic_rgb_ctx_decode_host: nothing encoded yet");
-    HIP_TRY(hipSetDevice(c->device));
+    if (!c->encoded_any) return fail(FIC_E_STATE, "fic_rgb_ctx_decode_zoom_host: nothing encoded yet");
     const FicGeom& g = c->g;
     FicGeom g1 = g;
+    if (zoom != 1) {
+        const int rc = make_decode_geometry(g.W, g.H, g.B, g.wK, 1, 1, zoom, &g1);
+        if (rc) return rc;
+    }
     g1.planes = 1;
-    const size_t npix = (size_t)g.W * g.H;
-    if (!c->dec_image) { int rc = dev_alloc(&c->dec_image, npix); if (rc) return rc; }
-    if (!c->dec_scaled) { int rc = dev_alloc(&c->dec_scaled, (size_t)g.Ws * g.Hs); if (rc) return rc; }
-    if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, 1); if (rc) return rc; }
-    if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(1, npix)); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)g1.W * g1.H;
+    int32_t *d_image, *d_scaled;
+    FicDecodeState* d_state;
+    uint32_t* d_sq;
+    Arena ar;
+    if (zoom == 1) {
+        if (!c->dec_image) { int rc = dev_alloc(&c->dec_image, npix); if (rc) return rc; }
+        if (!c->dec_scaled) { int rc = dev_alloc(&c->dec_scaled, (size_t)g.Ws * g.Hs); if (rc) return rc; }
+        if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, 1); if (rc) return rc; }
+        if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(1, npix)); if (rc) return rc; }
+        d_image = c->dec_image; d_scaled = c->dec_scaled; d_state = c->dec_state; d_sq = c->dec_sq;
+    } else {
+        const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g1.Ws * g1.Hs * 4), o_state = o_image + align256(npix * 4),
+                     o_sq = o_state + align256(sizeof(FicDecodeState)), total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
+        const int rc = arena_take(c->device, total, &ar);
+        if (rc) return rc;
+        d_scaled = (int32_t*)(ar.base + o_scaled); d_image = (int32_t*)(ar.base + o_image);
+        d_state = (FicDecodeState*)(ar.base + o_state); d_sq = (uint32_t*)(ar.base + o_sq);
+    }
     hipStream_t s = c->last_stream;
-    for (int p = 0; p < g.planes; p++) {
+    int rc = FIC_OK;
+    for (int p = 0; p < g.planes && rc == FIC_OK; p++) {
         const int32_t* qrows = c->qrows + (size_t)p * g.Nr * 5;
         const int32_t* iso = c->iso ? c->iso + (size_t)p * g.Nr : nullptr;      // n_iso = 8: paint through src_k
-        int rc = decode_loop(kDecodeRgb, 1, npix, c->dec_image, c->dec_state, nullptr, avg_error_out ? avg_error_out + p : nullptr,
-                             iterations_out ? iterations_out + p : nullptr, nullptr, s, [&](int counter) {
-            return fic_launch_decode_iteration_rgb(c->dec_scaled, c->dec_image, qrows, c->dec_state, c->dec_sq, counter, g1, s, iso);
+        rc = decode_loop(kDecodeRgb, 1, npix, d_image, d_state, nullptr, avg_error_out ? avg_error_out + p : nullptr,
+                         iterations_out ? iterations_out + p : nullptr, nullptr, s, [&](int counter) {
+            return fic_launch_decode_iteration_rgb(d_scaled, d_image, qrows, d_state, d_sq, counter, g1, s, iso);
         });
-        if (rc == FIC_E_ARGUMENT) return fail(rc, "%s (plane %d of the context)", g_err.c_str(), p);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy(argb_out + (size_t)p * npix, c->dec_image, npix * 4, hipMemcpyDeviceToHost));
+        if (rc == FIC_E_ARGUMENT) rc = fail(rc, "%s (plane %d of the context)", std::string(g_err).c_str(), p);
+        if (rc == FIC_OK) {
+            hipError_t e = hipMemcpy(argb_out + (size_t)p * npix, d_image, npix * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_rgb_ctx_decode_zoom_host: %s", hipGetErrorString(e));
+        }
     }
-    return FIC_OK;
+    if (zoom != 1) arena_give(ar);
+    return rc;
+}
+
+int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_out, int* iterations_out)
+{
+    return fic_rgb_ctx_decode_zoom_host(c, 1, argb_out, avg_error_out, iterations_out);
 }
 
 }  // extern "C"
@@ -453,8 +481,9 @@ void ficd::rgb_cache_give(fic_rgb_ctx* c)
     if (evict) fic_rgb_ctx_destroy(evict);
 }
 
-void ficd::rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5)
+void ficd::rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5, const int32_t** iso)
 {
+    if (iso) *iso = c->iso;
     if (argb) *argb = c->argb;
     if (scaled) *scaled = c->scaled;
     if (qrows5) *qrows5 = c->qrows;

@@ -70,10 +70,12 @@ int encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B
                    int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows);
 
 // idle single-image joint-RGB contexts of the one-shot RGB entry (fic_capi_rgb.cpp), and the device buffers of image 0 of a
-// context: the input in use [H][W], its scaleImageRGB copy [H/2][W/2] and the quantised rows [N_r][5] of the last encode
+// context: the input in use [H][W], its scaleImageRGB copy [H/2][W/2], the quantised rows [N_r][5] of the last encode and
+// its winning isometries [N_r] (NULL on an n_iso = 1 context: the identity)
 fic_rgb_ctx* rgb_cache_take(int device, int w, int h, int B, int wK, int n_iso = 1);
 void rgb_cache_give(fic_rgb_ctx* c);
-void rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5);
+void rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5,
+                   const int32_t** iso = nullptr);
 
 // device arenas of the stream decoders (fic_capi_decode.cpp): one allocation of at least `bytes` on `device`, returned after use
 struct Arena {

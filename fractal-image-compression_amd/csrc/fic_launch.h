@@ -188,37 +188,51 @@ int fic_launch_decode_iteration(uint8_t* scaled, uint8_t* image, const int32_t* 
                                 FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
 
 // quadtree codec (fic_quadtree.hip), grey and joint RGB.  The pixel format of an image and its quantised rows:
-//   QtGrey  bytes,       rows {idx_local, qa, qb} + an isometry column  -> leaf rows [7] {x, y, B, idx_local, qa, qb, iso}
-//   QtRgb   packed ARGB, rows {idx_local, q1, q2, q3, q4}               -> leaf rows [8] {x, y, B, idx_local, q1, q2, q3, q4}
+//   QtGrey    bytes,       rows {idx_local, qa, qb} + an isometry column  -> leaf rows [7] {x, y, B, idx_local, qa, qb, iso}
+//   QtRgb     packed ARGB, rows {idx_local, q1, q2, q3, q4}               -> leaf rows [8] {x, y, B, idx_local, q1, q2, q3, q4}
+//   QtRgbIso  packed ARGB, the same rows + an isometry column (4.17)      -> leaf rows [9] {x, y, B, idx_local, q1, q2, q3, q4, iso}
+// One leaf of the decoder's per-level lists: position, global domain block (the level's window_to_global), offset of its B*B
+// squares in `sqbuf` (prefix sum of B^2 over the leaves before it), quantised row: {qa, qb, iso, 0} grey, {q1, q2, q3, q4} colour.
+struct FicQtLeaf {
+    int32_t x, y, gi, sqoff, q[4];
+};
+// The same with the isometry beside the full colour row (QtRgbIso only: the two older formats keep their 32-byte leaf)
+struct FicQtLeafIso {
+    int32_t x, y, gi, sqoff, q[4], k;
+};
 struct QtGrey {
     using Px = uint8_t;
+    using Leaf = FicQtLeaf;
     static constexpr int QW = 3;             // ints per quantised row
     static constexpr bool kIso = true;       // an isometry column beside the rows (NULL: n_iso = 1, iso 0)
     static constexpr int kLeafInts = 3 + QW + 1;
 };
 struct QtRgb {
     using Px = int32_t;
+    using Leaf = FicQtLeaf;
     static constexpr int QW = 5;
     static constexpr bool kIso = false;
     static constexpr int kLeafInts = 3 + QW;
 };
-// One leaf of the decoder's per-level lists: position, global domain block (the level's window_to_global), offset of its B*B
-// squares in `sqbuf` (prefix sum of B^2 over the leaves before it), quantised row: {qa, qb, iso, 0} grey, {q1, q2, q3, q4} colour.
-struct FicQtLeaf {
-    int32_t x, y, gi, sqoff, q[4];
+struct QtRgbIso {
+    using Px = int32_t;
+    using Leaf = FicQtLeafIso;
+    static constexpr int QW = 5;
+    static constexpr bool kIso = true;
+    static constexpr int kLeafInts = 3 + QW + 1;
 };
 // sse u32 [g.Nr]: collage SSE (colour: over the three channels) of every range block of one level from its quantised rows
-// [N_r][Fmt::QW]; image the original [H][W], scaled its 2:1 copy [Hs][Ws] (k_scale / scaleImageRGB); iso: QtGrey only
+// [N_r][Fmt::QW]; image the original [H][W], scaled its 2:1 copy [Hs][Ws] (k_scale / scaleImageRGB); iso: formats with kIso only
 template <typename Fmt>
 int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* scaled, const int32_t* qrows, const int32_t* iso,
                         uint32_t* sse, const FicGeom& g, hipStream_t s);
 // split + compaction over nl levels (B_max >> l): counts int [Ntop], offs int [Ntop + 1] (offs[Ntop] = leaves), leaves int32
-// [leaves][Fmt::kLeafInts] (NULL: count only); room for the largest possible count is the caller's.  iso: QtGrey only
+// [leaves][Fmt::kLeafInts] (NULL: count only); room for the largest possible count is the caller's.  iso: formats with kIso only
 template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
                           hipStream_t s);
 // one paint (decodeGreyScale / decodeRGB) of the n leaves of side g.B (one plane; g = that level's geometry)
 template <typename Fmt>
-int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const FicQtLeaf* lv, int n,
+int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,
                                    FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);

@@ -2,11 +2,12 @@
 // block, the split decision + leaf compaction, and the decoder's paint of leaves of mixed size.  An extension like
 // n_iso = 8: the reference encodes with one block size (FC:14).  gfx950 (MI355X / CDNA4) only, wave64; -ffp-contract=off
 // like every other translation unit (the paint arithmetic is k_decode_paint's / k_decode_paint_rgb's, one rounding per
-// operation).  DESIGN.md sections 4.13 (grey) and 4.14 (colour).
+// operation).  DESIGN.md sections 4.13 (grey), 4.14 (colour) and 4.17 (colour with the 8 isometries).
 //
-// The kernels that touch pixels are templated on the pixel format (QtGrey / QtRgb, fic_launch.h) and share their indexing,
-// their atomics and the reduction of the decoder's squares; only the per-pixel arithmetic of a block row is written per format
-// (qt_row_sse / qt_paint_row on bytes: qt_row_values; on packed ARGB: rgb_row_coef / rgb_paint_px, fic_devfn.h).
+// The kernels that touch pixels are templated on the pixel format (QtGrey / QtRgb / QtRgbIso, fic_launch.h) and share their
+// indexing, their atomics and the reduction of the decoder's squares; only the per-pixel arithmetic of a block row is written
+// per pixel type (qt_row_sse / qt_paint_row on bytes: qt_row_values; on packed ARGB: rgb_domain_seg + rgb_row_coef /
+// rgb_paint_px, fic_devfn.h).  QtRgb passes the constant isometry 0 to the ARGB code, which then is the code it always was.
 //
 //   k_leaf_sse<Fmt, B>       SSE of the quantised row of every range block of one level against the original image (colour:
 //                            summed over the three channels)
@@ -78,19 +79,47 @@ __device__ __forceinline__ const int32_t* rgb_domain_row(const int32_t* __restri
     return scaled + (size_t)(r * g.abstand + ry) * g.Ws + c * g.abstand;
 }
 
-// The same over the channels R, G, B: q = {q1, q2, q3, q4} (no isometries).
+// The S domain pixels that the range pixels x0 .. x0 + S - 1 of pixel row ry are painted from under isometry k of side B
+// (range pixel (rx, ry) takes the domain pixel at src_k(rx, ry)).  k = 0: S contiguous ints of the domain row;
+// else the run starts at src_k(x0, ry) and steps by the isometry's x-increment -- along a row (mirrored or not), or, for the
+// four transposing isometries, down or up a column of the scaled image, one int per domain row.
+template <int B, int S>
+__device__ __forceinline__ void rgb_domain_seg(const int32_t* __restrict__ scaled, const FicGeom& g, int gi, int k, int ry, int x0,
+                                               int32_t (&dom)[S])
+{
+    if (k == 0) {
+        __builtin_memcpy(dom, rgb_domain_row(scaled, g, gi, ry) + x0, 4 * S);
+    } else {
+        const int32_t* d0 = rgb_domain_row(scaled, g, gi, 0);
+        int ax, bx_, cx, ay, by_, cy;
+        iso_affine(k, B - 1, ax, bx_, cx, ay, by_, cy);
+        const int sx = ay * g.Ws + ax, s0 = (cy + by_ * ry) * g.Ws + cx + bx_ * ry + sx * x0;
+#pragma unroll
+        for (int x = 0; x < S; x++) dom[x] = d0[s0 + sx * x];
+    }
+}
+
+// The same over the channels R, G, B: q = {q1, q2, q3, q4}, k the block's isometry (the constant 0 for QtRgb).
 template <int B>
 __device__ __forceinline__ uint32_t qt_row_sse(const int32_t* __restrict__ prow, const int32_t* __restrict__ scaled, const FicGeom& g,
-                                               int gi, int, int ry, const int32_t* __restrict__ q)
+                                               int gi, int k, int ry, const int32_t* __restrict__ q)
 {
     const FicRgbCoef cf = rgb_row_coef(q[0], q[1], q[2], q[3]);
-    const int32_t* drow = rgb_domain_row(scaled, g, gi, ry);
     uint32_t s = 0;
-#pragma unroll
-    for (int x = 0; x < B; x++) {
+    auto add = [&](int x, int32_t d) {
         int vR, vG, vB;
-        rgb_paint_px(cf, drow[x], vR, vG, vB);
+        rgb_paint_px(cf, d, vR, vG, vB);
         s += rgb_sq(prow[x], vR, vG, vB);
+    };
+    if (k == 0) {       // read straight from the row, not through rgb_domain_seg's copy: k_leaf_sse<QtRgb, B> keeps its instruction count
+        const int32_t* drow = rgb_domain_row(scaled, g, gi, ry);
+#pragma unroll
+        for (int x = 0; x < B; x++) add(x, drow[x]);
+    } else {
+        int32_t dom[B];
+        rgb_domain_seg<B, B>(scaled, g, gi, k, ry, 0, dom);
+#pragma unroll
+        for (int x = 0; x < B; x++) add(x, dom[x]);
     }
     return s;
 }
@@ -128,7 +157,7 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const typename Fmt::Px* __rest
 // scanline order.  One thread per top-level block walks its subtree (at most 1 + 4 + 16 nodes) with a small explicit stack:
 // k_qt_count counts the leaves, k_qt_scan (one workgroup) turns the counts into offsets, k_qt_scatter walks again and writes
 // the rows at its offset: {x, y, B} and the level's quantised row, {idx_local, qa, qb, iso} (grey) or {idx_local, q1, q2, q3,
-// q4} (colour).
+// q4} (colour; QtRgbIso: + iso).
 // ---------------------------------------------------------------------------------------------
 struct FicQtLevels {
     const uint32_t* sse[3];
@@ -210,7 +239,7 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
     if (t == FIC_QT_SCAN_THREADS - 1) offs[n] = part[t];
 }
 
-// Leaf rows of Fmt::QW + 3 ints, grey one more: the iso column follows the quantised row
+// Leaf rows of Fmt::QW + 3 ints, formats with kIso one more: the iso column follows the quantised row
 template <typename Fmt>
 __global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __restrict__ offs, int32_t* __restrict__ leaves)
 {
@@ -259,16 +288,19 @@ __device__ __forceinline__ uint32_t qt_paint_row(uint8_t* __restrict__ prow, uin
     return sq;
 }
 
-// The same for decodeRGB (FC:458-499): the squares are dR^2 + dG^2 + dB^2 per pixel (FC:493).
-template <int B, int S>
+// The same for decodeRGB (FC:458-499): the squares are dR^2 + dG^2 + dB^2 per pixel (FC:493).  Leaf: FicQtLeaf (isometry 0)
+// or FicQtLeafIso (the leaf's own).
+__device__ __forceinline__ int qt_leaf_iso(const FicQtLeaf&) { return 0; }
+__device__ __forceinline__ int qt_leaf_iso(const FicQtLeafIso& e) { return e.k; }
+template <int B, int S, typename Leaf>
 __device__ __forceinline__ uint32_t qt_paint_row(int32_t* __restrict__ prow, uint32_t* __restrict__ srow, const int32_t* __restrict__ scaled,
-                                                 const FicGeom& g, const FicQtLeaf& e, int ry, int x0)
+                                                 const FicGeom& g, const Leaf& e, int ry, int x0)
 {
     const FicRgbCoef cf = rgb_row_coef(e.q[0], e.q[1], e.q[2], e.q[3]);
     int32_t cur[S], dom[S];
     uint32_t sqv[S], sq = 0;
     __builtin_memcpy(cur, prow, 4 * S);
-    __builtin_memcpy(dom, rgb_domain_row(scaled, g, e.gi, ry) + x0, 4 * S);
+    rgb_domain_seg<B, S>(scaled, g, e.gi, qt_leaf_iso(e), ry, x0, dom);
 #pragma unroll
     for (int x = 0; x < S; x++) {
         int vR, vG, vB;
@@ -303,13 +335,14 @@ __device__ __forceinline__ void qt_ssd_add(unsigned long long sq, unsigned long 
 // row of a leaf up to B = 16; at the decode-only sides 32 and 64 (zoomed decodes) per row SEGMENT of 16 grey or
 // 4 packed ARGB pixels (16 bytes of the image per thread either way, a whole row would not fit a thread's registers), ordered
 // (leaf, pixel row, segment): neighbours in a wave touch neighbouring bytes of the same image row.  The exact integer sum of
-// the squares goes to state->ssd[counter] like k_decode_paint's.
+// the squares goes to state->ssd[counter] like k_decode_paint's.  Under an isometry (QtRgbIso) a thread's 4-pixel segment reads
+// a run of 4 domain pixels from src_k(x0, ry) on, in the isometry's x direction (rgb_domain_seg).
 // ---------------------------------------------------------------------------------------------
 template <typename Fmt, int B>
 constexpr int qt_paint_seg() { return B <= 16 ? B : (sizeof(typename Fmt::Px) == 1 ? 16 : 4); }
 template <typename Fmt, int B>
 __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt::Px* __restrict__ scaled, typename Fmt::Px* __restrict__ image,
-                                                             const FicQtLeaf* __restrict__ lv, int n, FicDecodeState* __restrict__ state,
+                                                             const typename Fmt::Leaf* __restrict__ lv, int n, FicDecodeState* __restrict__ state,
                                                              uint32_t* __restrict__ sqbuf, int counter, FicGeom g)
 {
     FicDecodeState* st = state;
@@ -319,7 +352,7 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt:
     constexpr int S = qt_paint_seg<Fmt, B>(), NS = B / S;
     if (t < n * B * NS) {
         const int x0 = (t % NS) * S, u = t / NS;
-        const FicQtLeaf e = lv[u / B];
+        const typename Fmt::Leaf e = lv[u / B];
         const int ry = u % B;
         sq = qt_paint_row<B, S>(image + (size_t)(e.y + ry) * g.W + e.x + x0, sqbuf + (size_t)e.sqoff + (size_t)ry * B + x0, scaled, g, e,
                                 ry, x0);
@@ -371,7 +404,7 @@ int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrow
 }
 
 template <typename Fmt>
-int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const FicQtLeaf* lv, int n,
+int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,
                                    FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s)
 {
     if (n <= 0) return 0;
@@ -388,7 +421,8 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
                                           hipStream_t);                                                                               \
     template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \
                                             int, int, int, float, int*, int*, int32_t*, hipStream_t);                                 \
-    template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const FicQtLeaf*, int, FicDecodeState*, uint32_t*,     \
+    template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const Fmt::Leaf*, int, FicDecodeState*, uint32_t*,     \
                                                      int, const FicGeom&, hipStream_t);
 FIC_QT_INSTANTIATE(QtGrey)
 FIC_QT_INSTANTIATE(QtRgb)
+FIC_QT_INSTANTIATE(QtRgbIso)

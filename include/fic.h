@@ -187,7 +187,8 @@ FIC_API int fic_rgb_ctx_decode_host(fic_rgb_ctx* ctx, int32_t* argb_out, float* 
  * the decoder paint pixel (rx, ry) of a range block from the domain pixel at src_k(rx, ry).
  *   n_iso   1 or 8 (FIC_E_ARGUMENT otherwise, before any device work); 1 gives the bits of the entries above
  *   iso     [N_r] winning isometry (all 0 with n_iso = 1); may be NULL.  qrows5 keeps its shape: the .run format has no
- *           isometry column, so an n_iso = 8 codebook is decoded from its context (fic_rgb_ctx_decode_host), not from a stream
+ *           isometry column, so an n_iso = 8 codebook is written with fic_write_run_rgb_iso (tag 5, below) and decoded with
+ *           fic_decode_rgb_iso_run, or from its context (fic_rgb_ctx_decode_host / fic_rgb_ctx_decode_zoom_host)
  * Sweep policy: that of fic_rgb_ctx_encode with the pair count times 8 -- the matrix-core sweep ("k_sweep_q<NK, 4, ..>" /
  * "k_sweep_qs<NK, 4>": 8 permuted range columns per block, flagged pairs evaluated exactly in the range block's order) for full
  * search when 8 N_r N_d >= 3e7 or B = 16, else the VALU sweeps ("k_sweep_rgb_fast_iso<n>": full search at B = 4 / 8,
@@ -250,9 +251,39 @@ FIC_API int fic_decode_quadtree_run_zoom(const uint8_t* run, int64_t len, int zo
                                          int* w, int* h, float* avg_error_io, int* iterations);
 FIC_API int fic_decode_rgb_quadtree_run_zoom(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out,
                                              int64_t capacity_pixels, int* w, int* h, float* avg_error_io, int* iterations);
-/* fic_ctx_decode_host at zoom: gray_out [planes][zoom*h][zoom*w].  The way to zoom a fixed-B n_iso = 8 codebook (the .run
- * format has no isometry column), and batched planes. */
+/* fic_ctx_decode_host at zoom: gray_out [planes][zoom*h][zoom*w].  Zooms a fixed-B n_iso = 8 codebook straight from its
+ * context (as a stream it goes through fic_write_run_gray_iso / fic_decode_gray_iso_run, tag 4, below), and batched planes. */
 FIC_API int fic_ctx_decode_zoom_host(fic_ctx* ctx, int zoom, uint8_t* gray_out, float* avg_error_out, int* iterations_out);
+/* The colour twin: fic_rgb_ctx_decode_host at zoom, argb_out [planes][zoom*h][zoom*w], for n_iso = 1 and n_iso = 8 contexts.
+ * zoom = 1 gives the bits of fic_rgb_ctx_decode_host. */
+FIC_API int fic_rgb_ctx_decode_zoom_host(fic_rgb_ctx* ctx, int zoom, int32_t* argb_out, float* avg_error_out, int* iterations_out);
+
+/* ---- fixed-B streams with an isometry column (tags 4 and 5) -------------------------------------- */
+/* An extension like the quadtree streams: the .run format of the reference has no place for the isometry of an n_iso = 8
+ * codebook.  Big-endian int32 like writeData: header {4, w, h, 0, B, wK} (grey) or {5, w, h, 0, B, wK} (colour), then per range
+ * block in scanline order {idx_local, qa, qb, iso} or {idx_local, q1, q2, q3, q4, iso}; iso in 0..7 with the numbering of
+ * fic_encode_rgb_iso_argb.  An n_iso = 1 codebook is written with a column of zeros.  The 0 sits where a .run holds its block
+ * size: Java's decodeRGB divides by it, fic_decode_rgb_run refuses it with FIC_E_GEOMETRY, fic_decode_gray_run refuses the
+ * non-zero tag with FIC_E_NOT_GREY and the quadtree readers refuse any tag but their own, so no older reader misreads the stream.
+ * Writers, host only: return the bytes written (24 + 4 * (QW + 1) * N_r) or a negative code -- FIC_E_ARGUMENT for a null
+ * pointer, n_ranges other than the geometry's N_r or an iso outside 0..7, FIC_E_GEOMETRY / FIC_E_WINDOW as fic_geometry and the
+ * window check give them, FIC_E_CAPACITY for a short buffer. */
+FIC_API int64_t fic_write_run_gray_iso(const int32_t* qrows, const int32_t* iso, int n_ranges, int w, int h, int B, int wK,
+                                       uint8_t* out, int64_t capacity);
+FIC_API int64_t fic_write_run_rgb_iso(const int32_t* qrows5, const int32_t* iso, int n_ranges, int w, int h, int B, int wK,
+                                      uint8_t* out, int64_t capacity);
+/* Decoders, with `zoom` in {1, 2, 4} as in the section above: the loop of fic_decode_gray_run_zoom / fic_decode_rgb_run_zoom on
+ * the geometry (zoom*w, zoom*h, zoom*B, wK) with range pixel (rx, ry) painted from the domain pixel at src_k(rx, ry) of side
+ * zoom*B -- what fic_ctx_decode_zoom_host / fic_rgb_ctx_decode_zoom_host compute on a context that holds the same rows and
+ * isometries (pixels, avgError, iterations); with a column of zeros, what the tag-0 / tag-1 stream of the same rows decodes
+ * to.  avg_error_io as in fic_decode_gray_run; *w / *h return the zoomed size (also on FIC_E_CAPACITY).  Checked on the host
+ * before any device work: FIC_E_ARGUMENT for another tag, a non-zero 4th int, a length other than the header's (truncated or
+ * oversized), an idx_local outside 0 .. wK^2 - 1, an iso outside 0..7 or a zoom outside {1, 2, 4}; FIC_E_GEOMETRY /
+ * FIC_E_WINDOW for a header the geometry or window check refuses. */
+FIC_API int fic_decode_gray_iso_run(const uint8_t* run, int64_t len, int zoom, int device, uint8_t* gray_out, int64_t capacity,
+                                    int* w, int* h, float* avg_error_io, int* iterations);
+FIC_API int fic_decode_rgb_iso_run(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out,
+                                   int64_t capacity_pixels, int* w, int* h, float* avg_error_io, int* iterations);
 
 /* ---- quadtree (variable block size) grey codec -------------------------------------------------- */
 /* An extension like n_iso = 8: the reference encodes with one block size (FC:14).  Levels B_max in {8, 16}, B_min in {4, 8},
@@ -326,6 +357,33 @@ FIC_API int fic_decode_rgb_quadtree_run(const uint8_t* run, int64_t len, int dev
  * each in scanline order. */
 FIC_API int fic_debug_rgb_quadtree_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int device, uint32_t* sse,
                                        int64_t capacity);
+
+/* ---- quadtree joint-RGB codec with the 8 isometries (tag 6) ------------------------------------- */
+/* The colour quadtree codec above with n_iso = 1 or 8 (FIC_E_ARGUMENT otherwise): levels, geometry, wK, split rule, leaf order
+ * and argument checks are those of fic_encode_rgb_quadtree_argb; every level B is encoded exactly as
+ * fic_encode_rgb_iso_argb(argb, w, h, B, wK_B, n_iso) encodes it (the same cached working sets and sweep policy), and the
+ * collage SSE of a range block takes the domain pixel of range pixel (rx, ry) at src_k(rx, ry), k the block's winning
+ * isometry: what fic_decode_rgb_quadtree_iso_run paints.
+ *   leaves   int32 [capacity][9] {x, y, B, idx_local, q1, q2, q3, q4, iso}.  With n_iso = 1 the first 8 columns are the rows
+ *            of fic_encode_rgb_quadtree_argb and iso is 0. */
+FIC_API int fic_encode_rgb_quadtree_iso_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                             float threshold, int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+/* Stream, host only: header {6, w, h, 0, B_max, B_min, wK, n_leaves}, then per leaf {B, idx_local, q1, q2, q3, q4, iso} in
+ * quadtree order (the 0 as in tag 3: no older reader takes the stream).  The rule of fic_write_run_rgb_quadtree, and
+ * FIC_E_ARGUMENT for an iso outside 0..7. */
+FIC_API int64_t fic_write_run_rgb_quadtree_iso(const int32_t* leaves, int n_leaves, int w, int h, int B_max, int B_min, int wK,
+                                               uint8_t* out, int64_t capacity);
+/* Decoder with `zoom` in {1, 2, 4}: the loop of fic_decode_rgb_quadtree_run_zoom with every leaf painted through its
+ * isometry at side zoom*B.  With a column of zeros it decodes like the tag-3 stream of the same leaves; with threshold = +inf
+ * like the tag-5 stream of the fixed-B_max codebook.  Checked before any device work: every check of the tag-3 reader with
+ * FIC_E_ARGUMENT (tag other than 6, non-zero 4th int, bad levels, sizes that do not tile, idx_local outside its level's window,
+ * n_leaves outside 1 .. the B_min block count, a length other than the header's), an iso outside 0..7 likewise; a geometry or
+ * window the levels' own check refuses fails with FIC_E_GEOMETRY / FIC_E_WINDOW. */
+FIC_API int fic_decode_rgb_quadtree_iso_run(const uint8_t* run, int64_t len, int zoom, int device, int32_t* argb_out,
+                                            int64_t capacity_pixels, int* w, int* h, float* avg_error_io, int* iterations);
+/* Test hook with the layout of fic_debug_rgb_quadtree_sse. */
+FIC_API int fic_debug_rgb_quadtree_iso_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,
+                                           uint32_t* sse, int64_t capacity);
 
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
