@@ -1,25 +1,11 @@
 // fic_capi.cpp -- C ABI (include/fic.h) over the gfx950 kernels.  Host-side orchestration only:
 // validation, device buffers, launch order, result copies.  No compute happens on the CPU and
 // there is no CPU fallback: without a HIP device every compute entry returns FIC_E_NO_DEVICE.
-// (decoder entries: fic_capi_decode.cpp; joint-RGB contexts: fic_capi_rgb.cpp; multi-device entry: fic_capi_multi.cpp)
+// (decoder entries: fic_capi_decode.cpp; joint-RGB contexts: fic_capi_rgb.cpp; multi-device entry: fic_capi_multi.cpp;
+// error state, geometry and every stream writer / parser: fic_stream.cpp)
 #include "fic_internal.h"
 
 namespace ficd {
-
-thread_local std::string g_err;
-thread_local int g_err_code = 0;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    g_err_code = code;
-    return code;
-}
 
 int check_device(int device)
 {
@@ -27,64 +13,6 @@ int check_device(int device)
     if (ndev <= 0 || device < 0 || device >= ndev) return fail(FIC_E_NO_DEVICE, "no HIP device %d (this library has no CPU path)", device);
     HIP_TRY(hipSetDevice(device));
     return FIC_OK;
-}
-
-static int ilog2(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) l++;
-    return l;
-}
-
-// Geometry as the reference derives it (FC:111-116, FC:1019-1022) + what it needs to not throw.  B_top: the largest side taken.
-static int geometry_for(int w, int h, int B, int wK, int n_iso, int planes, int B_top, FicGeom* out)
-{
-    if (B != 4 && B != 8 && B != 16 && !(B_top >= B && (B == 32 || B == 64)))
-        return fail(FIC_E_GEOMETRY, "blockgroesse B=%d unsupported (GUI values 4, 8, 16; B=2 divides by zero at FC:1022)", B);
-    if (w <= 0 || h <= 0 || (w % 2) || (h % 2))
-        return fail(FIC_E_GEOMETRY, "image %dx%d: width and height must be positive and even (scaleImage FC:970-1007 overruns otherwise)", w, h);
-    if ((w % B) || (h % B))
-        return fail(FIC_E_GEOMETRY, "image %dx%d is not a multiple of B=%d (ArrayIndexOutOfBounds in the reference)", w, h, B);
-    FicGeom g;
-    memset(&g, 0, sizeof(g));
-    g.W = w; g.H = h; g.B = B; g.n = B * B; g.lgn = ilog2(B * B);
-    g.Ws = w / 2; g.Hs = h / 2; g.abstand = B / 4;
-    g.Rw = w / B; g.Rh = h / B; g.Nr = g.Rw * g.Rh;
-    g.Dw = g.Rw * 2 - 3; g.Dh = g.Rh * 2 - 3;
-    if (g.Dw < 1 || g.Dh < 1)
-        return fail(FIC_E_GEOMETRY, "image %dx%d with B=%d has no domain blocks (Dw=%d Dh=%d)", w, h, B, g.Dw, g.Dh);
-    g.Nd = g.Dw * g.Dh;
-    if ((long long)g.Nd * 8 >= 0x7FFFFFFFll || (long long)w * h >= 0x7FFFFFFFll)
-        return fail(FIC_E_GEOMETRY, "image %dx%d too large for 32-bit candidate indices", w, h);
-    if (out == nullptr) return FIC_OK;
-    if (wK < 1 || wK > g.Dw || wK > g.Dh)
-        return fail(FIC_E_WINDOW, "widthKernel wK=%d outside 1..min(Dw=%d,Dh=%d) (negative index at FC:145)", wK, g.Dw, g.Dh);
-    if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: only 1 (reference) or 8 (extension)", n_iso);
-    if (planes < 1) return fail(FIC_E_ARGUMENT, "planes=%d", planes);
-    g.wK = wK; g.n_iso = n_iso; g.planes = planes;
-    g.DW = g.n / 4;
-    int NR = 1, NC = 1;
-    fic_fast_variant(B, n_iso, &NR, &NC);
-    g.NR = NR;
-    int tsz = 64 * NR;
-    g.tiles = (g.Nr + tsz - 1) / tsz;
-    g.Nr_pad = g.tiles * tsz;
-    g.Nd_pad = g.Nd + FIC_POOL_PAD;
-    g.full = (wK == g.Dw && wK == g.Dh) ? 1 : 0;
-    *out = g;
-    return FIC_OK;
-}
-
-int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* out) { return geometry_for(w, h, B, wK, n_iso, planes, 16, out); }
-
-// The geometry (zoom * w, zoom * h, zoom * B, wK) a stream of the valid geometry (w, h, B, wK) decodes on at zoom 1, 2 or 4:
-// the same block counts, so every row keeps its meaning.  The sides 32 and 64 exist for the decoders only.
-int make_decode_geometry(int w, int h, int B, int wK, int n_iso, int planes, int zoom, FicGeom* out)
-{
-    if (zoom != 1 && zoom != 2 && zoom != 4) return fail(FIC_E_ARGUMENT, "zoom=%d: only 1, 2 or 4", zoom);
-    if ((long long)w * zoom >= 0x7FFFFFFFll || (long long)h * zoom >= 0x7FFFFFFFll)
-        return fail(FIC_E_GEOMETRY, "image %dx%d at zoom %d too large for 32-bit candidate indices", w, h, zoom);
-    return geometry_for(w * zoom, h * zoom, B * zoom, wK, n_iso, planes, 64, out);
 }
 
 }  // namespace ficd
@@ -462,8 +390,6 @@ const char* fic_version(void) { return "fic-hip 0.3 (gfx950, +xcheck sweeps)"; }
 #else
 const char* fic_version(void) { return "fic-hip 0.3 (gfx950)"; }
 #endif
-const char* fic_last_error(void) { return g_err.c_str(); }
-int fic_last_error_code(void) { return g_err_code; }
 
 int fic_device_count(void)
 {
@@ -493,19 +419,6 @@ int fic_is_greyscale_argb(const int32_t* argb, int w, int h)
         if (r != g || g != b) return 0;
     }
     return 1;
-}
-
-int64_t fic_write_run_gray(const int32_t* qrows, int n_ranges, int w, int h, int B, int wK, uint8_t* out,
-                           int64_t capacity)
-{
-    if (!qrows || !out || n_ranges < 0) return fail(FIC_E_ARGUMENT, "fic_write_run_gray: bad argument");
-    int64_t need = 20 + 12 * (int64_t)n_ranges;
-    if (capacity < need) return fail(FIC_E_CAPACITY, "fic_write_run_gray: need %lld bytes, have %lld", (long long)need, (long long)capacity);
-    const int32_t hdr[5] = {0, w, h, B, wK};          // FC:234-238
-    for (int i = 0; i < 5; i++) put_be32(out + 4 * i, hdr[i]);
-    uint8_t* p = out + 20;
-    for (int64_t i = 0; i < 3 * (int64_t)n_ranges; i++, p += 4) put_be32(p, qrows[i]);   // FC:241-245
-    return need;
 }
 
 fic_ctx* fic_ctx_create(int device, int w, int h, int B, int wK, int n_iso, int planes)

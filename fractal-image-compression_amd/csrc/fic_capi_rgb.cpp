@@ -1,5 +1,5 @@
 // fic_capi_rgb.cpp -- C ABI, joint-RGB path: encodeRGB (FC:171-219) as one-shot entry and as batched device-resident
-// contexts (fic_rgb_ctx_*), decodeRGB from a context's codebook, the RGB writeData branch.  Host-side orchestration only.
+// contexts (fic_rgb_ctx_*), decodeRGB from a context's codebook (on the decode job of fic_capi_decode.cpp).  Host-side orchestration only.
 #include "fic_internal.h"
 
 using namespace ficd;
@@ -410,40 +410,27 @@ int fic_rgb_ctx_decode_zoom_host(fic_rgb_ctx* c, int zoom, int32_t* argb_out, fl
     g1.planes = 1;
     HIP_TRY(hipSetDevice(c->device));
     const size_t npix = (size_t)g1.W * g1.H;
-    int32_t *d_image, *d_scaled;
-    FicDecodeState* d_state;
-    uint32_t* d_sq;
-    Arena ar;
+    DecodeJob J;
     if (zoom == 1) {
         if (!c->dec_image) { int rc = dev_alloc(&c->dec_image, npix); if (rc) return rc; }
         if (!c->dec_scaled) { int rc = dev_alloc(&c->dec_scaled, (size_t)g.Ws * g.Hs); if (rc) return rc; }
         if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, 1); if (rc) return rc; }
         if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(1, npix)); if (rc) return rc; }
-        d_image = c->dec_image; d_scaled = c->dec_scaled; d_state = c->dec_state; d_sq = c->dec_sq;
+        J.borrow(kDecodeRgb, g1, c->last_stream, c->dec_scaled, c->dec_image, c->dec_state, c->dec_sq);
     } else {
-        const size_t o_scaled = 0, o_image = o_scaled + align256((size_t)g1.Ws * g1.Hs * 4), o_state = o_image + align256(npix * 4),
-                     o_sq = o_state + align256(sizeof(FicDecodeState)), total = o_sq + align256(fic_decode_sq_words(1, npix) * 4);
-        const int rc = arena_take(c->device, total, &ar);
+        const int rc = J.open("fic_rgb_ctx_decode_zoom_host", c->device, kDecodeRgb, g1, c->last_stream);
         if (rc) return rc;
-        d_scaled = (int32_t*)(ar.base + o_scaled); d_image = (int32_t*)(ar.base + o_image);
-        d_state = (FicDecodeState*)(ar.base + o_state); d_sq = (uint32_t*)(ar.base + o_sq);
     }
-    hipStream_t s = c->last_stream;
     int rc = FIC_OK;
     for (int p = 0; p < g.planes && rc == FIC_OK; p++) {
         const int32_t* qrows = c->qrows + (size_t)p * g.Nr * 5;
         const int32_t* iso = c->iso ? c->iso + (size_t)p * g.Nr : nullptr;      // n_iso = 8: paint through src_k
-        rc = decode_loop(kDecodeRgb, 1, npix, d_image, d_state, nullptr, avg_error_out ? avg_error_out + p : nullptr,
-                         iterations_out ? iterations_out + p : nullptr, nullptr, s, [&](int counter) {
-            return fic_launch_decode_iteration_rgb(d_scaled, d_image, qrows, d_state, d_sq, counter, g1, s, iso);
+        rc = J.run("fic_rgb_ctx_decode_zoom_host", nullptr, avg_error_out ? avg_error_out + p : nullptr,
+                   iterations_out ? iterations_out + p : nullptr, nullptr, argb_out + (size_t)p * npix, [&](int counter) {
+            return fic_launch_decode_iteration_rgb((int32_t*)J.scaled, (int32_t*)J.image, qrows, J.state, J.sq, counter, g1, J.stream, iso);
         });
         if (rc == FIC_E_ARGUMENT) rc = fail(rc, "%s (plane %d of the context)", std::string(g_err).c_str(), p);
-        if (rc == FIC_OK) {
-            hipError_t e = hipMemcpy(argb_out + (size_t)p * npix, d_image, npix * 4, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_rgb_ctx_decode_zoom_host: %s", hipGetErrorString(e));
-        }
     }
-    if (zoom != 1) arena_give(ar);
     return rc;
 }
 
@@ -515,18 +502,6 @@ int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, in
     if (rc == FIC_OK) rgb_cache_give(c);
     else fic_rgb_ctx_destroy(c);
     return rc;
-}
-
-int64_t fic_write_run_rgb(const int32_t* qrows5, int n_ranges, int w, int h, int B, int wK, uint8_t* out, int64_t capacity)
-{
-    if (!qrows5 || !out || n_ranges < 0) return fail(FIC_E_ARGUMENT, "fic_write_run_rgb: bad argument");
-    int64_t need = 20 + 20 * (int64_t)n_ranges;
-    if (capacity < need) return fail(FIC_E_CAPACITY, "fic_write_run_rgb: need %lld bytes, have %lld", (long long)need, (long long)capacity);
-    const int32_t hdr[5] = {1, w, h, B, wK};          // FC:234-238, isRGB = 1
-    for (int i = 0; i < 5; i++) put_be32(out + 4 * i, hdr[i]);
-    uint8_t* p = out + 20;
-    for (int64_t i = 0; i < 5 * (int64_t)n_ranges; i++, p += 4) put_be32(p, qrows5[i]);   // FC:249-256
-    return need;
 }
 
 }  // extern "C"

@@ -24,6 +24,21 @@ struct FicGeom {
 
 #define FIC_POOL_PAD 8
 
+// The instantiation of k_sweep_fast (fic_sweep.hip) for (B, n_iso): NR range blocks per lane (what FicGeom::NR and the tile
+// padding follow), NC isometries per workgroup.  -1 and nothing written: none (the decoders' sides 32 and 64 among them).
+inline int fic_fast_variant(int B, int n_iso, int* NR, int* NC)
+{
+    int nr = 0, nc = 0;
+    if (B == 4) { nr = n_iso == 1 ? 4 : 1; nc = n_iso == 1 ? 1 : 8; }
+    else if (B == 8) { nr = n_iso == 1 ? 2 : 1; nc = n_iso == 1 ? 1 : 8; }
+    else if (B == 16) { nr = n_iso == 1 ? 2 : 1; nc = n_iso == 1 ? 1 : 2; }
+    else return -1;
+    if (n_iso != 1 && n_iso != 8) return -1;
+    if (NR) *NR = nr;
+    if (NC) *NC = nc;
+    return 0;
+}
+
 // Per-domain-block statistics streamed beside the pixels (8 bytes).
 //   sum = sum of the n pixels  (Domainblock.mittelWert = sum / n,  DB:92-98)
 //   s32 = (float) sqrt((double) variance)   -- ONLY used by the conservative prune test

@@ -1,5 +1,6 @@
-// fic_internal.h -- shared by the translation units of the C ABI (fic_capi*.cpp): error reporting, the context type,
-// geometry validation, small device-memory helpers and the caches' release hooks.  Not part of the public interface.
+// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the context type, small
+// device-memory helpers, the decode job and the caches' release hooks; error reporting, geometry validation and the stream
+// formats come with fic_stream.h.  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -7,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -14,13 +16,9 @@
 #include "../../include/fic.h"
 #include "fic_device.h"
 #include "fic_launch.h"
+#include "fic_stream.h"
 
 namespace ficd {
-
-// message + code of the last failure on the calling thread (fic_last_error / fic_last_error_code)
-extern thread_local std::string g_err;
-extern thread_local int g_err_code;
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -35,12 +33,6 @@ struct ErrKeep {
     ~ErrKeep() { g_err = msg; g_err_code = code; }
 };
 
-// Geometry as the reference derives it (FC:111-116, FC:1019-1022) + what it needs to not throw; out == nullptr: validate only
-int make_geometry(int w, int h, int B, int wK, int n_iso, int planes, FicGeom* out);
-// Decoders only: the geometry (zoom w, zoom h, zoom B, wK) of a decode at zoom 1, 2 or 4 of a stream whose own geometry
-// (w, h, B, wK) make_geometry accepts; block sides up to 64.  FIC_E_ARGUMENT for another zoom.
-int make_decode_geometry(int w, int h, int B, int wK, int n_iso, int planes, int zoom, FicGeom* out);
-
 template <typename T>
 int dev_alloc(T** p, size_t count)
 {
@@ -51,17 +43,6 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Makes `device` current, or refuses it with FIC_E_NO_DEVICE (fic_capi.cpp)
 int check_device(int device);
-
-// DataOutputStream.writeInt / DataInputStream.readInt of the .run streams (FC:234-256, 372-374): big-endian int32
-inline void put_be32(uint8_t* p, int32_t v)
-{
-    uint32_t u = (uint32_t)v;
-    p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u;
-}
-inline int32_t get_be32(const uint8_t* p)
-{
-    return (int32_t)(((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3]);
-}
 
 // idle single-plane grey contexts of the one-shot / multi-device entries (fic_capi.cpp)
 fic_ctx* cache_take(int device, int w, int h, int B, int wK, int n_iso);
@@ -77,14 +58,12 @@ void rgb_cache_give(fic_rgb_ctx* c);
 void rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5,
                    const int32_t** iso = nullptr);
 
-// device arenas of the stream decoders (fic_capi_decode.cpp): one allocation of at least `bytes` on `device`, returned after use
+// device arena of a decode (fic_capi_decode.cpp): one allocation kept between calls, taken and given back by a DecodeJob
 struct Arena {
     int device = -1;
     size_t bytes = 0;
     char* base = nullptr;
 };
-int arena_take(int device, size_t bytes, Arena* out);
-void arena_give(const Arena& a);
 // What the two decoders of the reference differ in around their loop: the pixel of generateGrayImage (FC:1142-1148) the image
 // starts from, and the names a row outside the pool is reported with.
 struct DecodeKind {
@@ -94,10 +73,35 @@ struct DecodeKind {
     const char* paint_line;  // where the reference throws ArrayIndexOutOfBounds
 };
 constexpr DecodeKind kDecodeGrey{1, 128u, "decode", "FC:394"}, kDecodeRgb{4, 0xff808080u, "decodeRGB", "FC:477"};
-// the decoder's loop control (decodeGreyScale FC:381-418, decodeRGB FC:458-505; fic_capi_decode.cpp) around
-// `iteration(counter)`, which enqueues one iteration -- scale, paint, fic_launch_decode_step -- on s
-int decode_loop(const DecodeKind& kind, int planes, size_t npix, void* d_image, FicDecodeState* d_state, const float* avg_in,
-                float* avg_out, int* iters_out, int* seq_out, hipStream_t s, const std::function<int(int)>& iteration);
+
+// The device side of one decode of g.planes images on the geometry g (fic_capi_decode.cpp): the workspace of the loop --
+// the scaled copy [planes][Hs][Ws] and the image [planes][H][W] in pixels of kind.px_bytes, the loop state [planes], sqbuf --
+// and the int32 spans uploaded for it (rows, isometries, per-level leaf lists).  The workspace is carved from an arena
+// (open) or is the caller's (borrow: the contexts' zoom-1 decodes); an arena goes back when the job goes out of scope.
+struct DecodeJob {
+    const DecodeKind* kind = nullptr;
+    FicGeom g{};
+    hipStream_t stream = nullptr;        // the null stream for the stream decoders, a context's last_stream
+    void *scaled = nullptr, *image = nullptr;
+    FicDecodeState* state = nullptr;
+    uint32_t* sq = nullptr;
+    std::vector<const int32_t*> spans;   // the device copies of open()'s `upload`, in its order
+    Arena arena;
+    DecodeJob() = default;
+    DecodeJob(const DecodeJob&) = delete;
+    DecodeJob& operator=(const DecodeJob&) = delete;
+    ~DecodeJob();
+    // the caller has made `device` current
+    int open(const char* who, int device, const DecodeKind& kind, const FicGeom& g, hipStream_t s,
+             std::initializer_list<const std::vector<int32_t>*> upload = {});
+    void borrow(const DecodeKind& kind, const FicGeom& g, hipStream_t s, void* scaled, void* image, FicDecodeState* state, uint32_t* sq);
+    // The decoder's loop (decodeGreyScale FC:381-418, decodeRGB FC:458-505) around `iteration(counter)`, which enqueues one
+    // iteration -- scale, paint, fic_launch_decode_step -- on `stream`; then the image [planes][H][W] to host_out.  avg_in
+    // [planes]: avgError carried in (NULL: 0); avg_out / iters_out / seq_out [planes] may be NULL and may alias avg_in.  On
+    // failure nothing of the caller's is written.
+    int run(const char* who, const float* avg_in, float* avg_out, int* iters_out, int* seq_out, void* host_out,
+            const std::function<int(int)>& iteration);
+};
 
 // what fic_release_cache() frees besides the grey contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp

@@ -315,23 +315,10 @@ int fic_launch_sweep_generic(const FicBuffers& b, const FicGeom& g, int r_begin,
     return 0;
 }
 
-// Kernel-variant table of the fast sweep: (B, n_iso) -> <DW, NR, NC>.
+// The instantiations k_sweep_fast<DW, NR, NC> the launcher below picks by (B, n_iso); NR and NC are fic_fast_variant's (fic_device.h).
 //   B=4 : n_iso 1 -> <4,4,1>    n_iso 8 -> <4,1,8>
 //   B=8 : n_iso 1 -> <16,2,1>   n_iso 8 -> <16,1,8>
 //   B=16: n_iso 1 -> <64,2,1>   n_iso 8 -> <64,1,2> (4 isometry groups on grid.y)
-int fic_fast_variant(int B, int n_iso, int* NR, int* NC)
-{
-    int nr = 0, nc = 0;
-    if (B == 4) { nr = n_iso == 1 ? 4 : 1; nc = n_iso == 1 ? 1 : 8; }
-    else if (B == 8) { nr = n_iso == 1 ? 2 : 1; nc = n_iso == 1 ? 1 : 8; }
-    else if (B == 16) { nr = n_iso == 1 ? 2 : 1; nc = n_iso == 1 ? 1 : 2; }
-    else return -1;
-    if (n_iso != 1 && n_iso != 8) return -1;
-    if (NR) *NR = nr;
-    if (NC) *NC = nc;
-    return 0;
-}
-
 int fic_launch_sweep_fast(const FicBuffers& b, const FicGeom& g, int tile0, int ntiles, int chunk_len, int nchunks,
                           hipStream_t s)
 {
