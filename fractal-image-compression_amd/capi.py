@@ -62,7 +62,7 @@ def lib():
     _torch_first()
     L = C.CDLL(so)
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
-    i32p, f32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    i32p, f32p, u8p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
     sig = {
         "fic_version": (C.c_char_p, []),
         "fic_last_error": (C.c_char_p, []),
@@ -143,6 +143,12 @@ def lib():
         "fic_write_run_rgb_quadtree_iso": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
         "fic_decode_rgb_quadtree_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
         "fic_debug_rgb_quadtree_iso_sse": (C.c_int, [i32p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
+        "fic_encode_gray_quadtree_budget_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
+        "fic_encode_gray_quadtree_budget_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
+        "fic_encode_rgb_quadtree_budget_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
+        "fic_encode_rgb_quadtree_iso_budget_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
+        "fic_quadtree_leaves_for_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+        "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -668,3 +674,67 @@ def decode_rgb_quadtree_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
     out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_rgb_quadtree_iso_run, run, 32, "colour quadtree stream", np.int32, device,
                                           avg_error_in, zoom)
     return out.reshape(h, w), avg, it
+
+
+# ---- quadtree encode to a leaf budget ---------------------------------------------------------------------------
+QT_STATS_FIELDS = ("collage_sse", "leaves_B_max", "leaves_B_half", "leaves_B_quarter")
+
+
+def quadtree_leaves_for_bytes(tag, n_iso, max_bytes):
+    """The largest leaf count whose quadtree stream of `tag` (2, 3, 6) fits max_bytes (fic_quadtree_leaves_for_bytes)."""
+    return check(int(lib().fic_quadtree_leaves_for_bytes(int(tag), int(n_iso), int(max_bytes))))
+
+
+def _budget(tag, n_iso, max_leaves, max_bytes):
+    if (max_leaves is None) == (max_bytes is None):
+        raise ValueError("pass exactly one of max_leaves= and max_bytes=")
+    return int(max_leaves) if max_bytes is None else quadtree_leaves_for_bytes(tag, n_iso, max_bytes)
+
+
+def _encode_budget(fn, head, M, w, h, B_min, cols, device):
+    """One budget entry of the C ABI: (leaves int32 [n, cols], threshold float32, stats uint64 [4] as QT_STATS_FIELDS)."""
+    cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
+    out = np.zeros((max(cap, 1), cols), np.int32)
+    n, t, stats = C.c_int(), C.c_float(), np.zeros(4, np.uint64)
+    check(fn(*head, M, device, ptr(out, C.c_int32), out.shape[0], C.byref(n), C.byref(t), ptr(stats, C.c_uint64)))
+    return out[:n.value].copy(), np.float32(t.value), stats
+
+
+def encode_gray_quadtree_budget(gray, B_max, B_min, wK=0, n_iso=1, max_leaves=None, max_bytes=None, device=0):
+    """encode_gray_quadtree to a size limit: at most max_leaves leaves, or a tag-2 stream of at most max_bytes bytes (exactly
+    one of the two), at the smallest threshold that allows it (fic_encode_gray_quadtree_budget_u8 / _argb).  Returns (leaves,
+    threshold, stats): the leaf table of encode_gray_quadtree at `threshold` (float32), and uint64 [4] = QT_STATS_FIELDS."""
+    M = _budget(2, n_iso, max_leaves, max_bytes)
+    g = np.asarray(gray)
+    if g.dtype == np.uint8:
+        g = np.ascontiguousarray(g)
+        fn, p = lib().fic_encode_gray_quadtree_budget_u8, ptr(g, C.c_uint8)
+    else:
+        g = np.ascontiguousarray(g, np.int32)
+        fn, p = lib().fic_encode_gray_quadtree_budget_argb, ptr(g, C.c_int32)
+    h, w = g.shape
+    return _encode_budget(fn, (p, w, h, B_max, B_min, wK, n_iso), M, w, h, B_min, 7, device)
+
+
+def encode_rgb_quadtree_budget(argb, w, h, B_max, B_min, wK=0, max_leaves=None, max_bytes=None, device=0):
+    """encode_rgb_quadtree to a size limit (tag 3; fic_encode_rgb_quadtree_budget_argb): (leaves [n, 8], threshold, stats)."""
+    M = _budget(3, 1, max_leaves, max_bytes)
+    a = _argb_image(argb, w, h)
+    return _encode_budget(lib().fic_encode_rgb_quadtree_budget_argb, (ptr(a, C.c_int32), w, h, B_max, B_min, wK), M, w, h, B_min, 8, device)
+
+
+def encode_rgb_quadtree_iso_budget(argb, w, h, B_max, B_min, wK=0, n_iso=8, max_leaves=None, max_bytes=None, device=0):
+    """encode_rgb_quadtree_iso to a size limit (tag 6; fic_encode_rgb_quadtree_iso_budget_argb): (leaves [n, 9], threshold, stats)."""
+    M = _budget(6, n_iso, max_leaves, max_bytes)
+    a = _argb_image(argb, w, h)
+    return _encode_budget(lib().fic_encode_rgb_quadtree_iso_budget_argb, (ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso), M, w, h, B_min, 9,
+                          device)
+
+
+def debug_qt_select(keys, rank, device=0):
+    """The budget's radix select on `keys` (uint32 [n]): (key of rank `rank` in descending order, 0 past the last; the smallest
+    float32 >= key / 256; the number of keys above it) (fic_debug_qt_select)."""
+    k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+    key, t, above = C.c_uint32(), C.c_float(), C.c_int64()
+    check(lib().fic_debug_qt_select(device, ptr(k, C.c_uint32), k.size, int(rank), C.byref(key), C.byref(t), C.byref(above)))
+    return key.value, np.float32(t.value), above.value

@@ -2,7 +2,7 @@
 // one-shot machinery, collage SSE + split + compaction on the device (fic_quadtree.hip), and the decoders of leaves of mixed
 // size on the decode job (fic_internal.h).  The tag-2 (grey), tag-3 (colour) and tag-6 (colour with an isometry column) stream
 // writers and parsers are in fic_stream.cpp.  Host-side orchestration only.  Semantics: DESIGN.md sections 4.13 (grey), 4.14
-// (colour) and 4.17 (colour with the 8 isometries).
+// (colour), 4.17 (colour with the 8 isometries) and 4.18 (encode to a leaf budget).
 #include "fic_internal.h"
 
 using namespace ficd;
@@ -89,17 +89,30 @@ struct QtRgbIsoHost : QtRgbIso {
     static int scale(const Px* image, Px* scaled, const FicGeom& g) { return fic_launch_scale_rgb(image, scaled, g, nullptr); }
 };
 
+// Encode to a leaf budget: the threshold is chosen on the device, from the SSE arrays of this encode, as the
+// smallest float whose tree has at most max_leaves leaves.
+struct QtBudget {
+    int64_t max_leaves;
+    float* threshold_out;    // the threshold chosen (also set on FIC_E_CAPACITY)
+    uint64_t* stats4;        // NULL or {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4}
+};
+
 // The encode behind fic_encode_*_quadtree_* and the SSE test hooks: every level through the one-shot contexts, then the
-// per-level SSE, the split and the compaction on the device.  leaves / sse_out may be NULL.
+// per-level SSE, the split and the compaction on the device.  leaves / sse_out may be NULL.  budget: NULL, or the threshold
+// comes from the budget's select instead of the argument.
 template <typename Fmt>
 int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
-              int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity)
+              int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity,
+              const QtBudget* budget = nullptr)
 {
     if (!gray && !argb) return fail(FIC_E_ARGUMENT, "%s encode: null image", Fmt::kStream.kind);
     if (threshold != threshold) return fail(FIC_E_ARGUMENT, "%s encode: threshold is NaN", Fmt::kStream.kind);
     QtLevels L;
     int rc = qt_levels(w, h, B_max, B_min, wK, n_iso, &L);
     if (rc) return rc;
+    if (budget && budget->max_leaves < L.g[0].Nr)
+        return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %lld, the image has %d blocks of side %d", Fmt::kStream.kind,
+                    (long long)budget->max_leaves, L.g[0].Nr, B_max);
     size_t sse_total = 0;
     for (int l = 0; l < L.nl; l++) sse_total += (size_t)L.g[l].Nr;
     if (sse_out && sse_capacity < (int64_t)sse_total)
@@ -119,8 +132,11 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     const size_t max_leaves = (size_t)L.g[L.nl - 1].Nr;
     size_t o_sse[kQtMaxLevels], off = 0;
     for (int l = 0; l < L.nl; l++) { o_sse[l] = off; off += align256((size_t)L.g[l].Nr * 4); }
-    const size_t o_cnt = off, o_offs = o_cnt + align256((size_t)top.Nr * 4), o_leaves = o_offs + align256(((size_t)top.Nr + 1) * 4),
-                 total = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4);
+    const size_t o_cnt = off, o_offs = o_cnt + align256((size_t)top.Nr * 4), o_leaves = o_offs + align256(((size_t)top.Nr + 1) * 4);
+    // a budget: the split keys of every block above B_min, the select's histograms and result, the tree's statistics
+    const int n1 = L.nl == 3 ? L.g[1].Nr : 0, nkeys = top.Nr + n1;
+    const size_t o_keys = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4), o_sel = o_keys + (budget ? align256((size_t)nkeys * 4) : 0),
+                 o_stats = o_sel + (budget ? align256(FIC_QT_SELECT_WORDS * 4) : 0), total = o_stats + (budget ? 256 : 0);
     if (rc == FIC_OK) rc = dev_alloc(&scratch, total);
     if (rc == FIC_OK && Fmt::prepare(c[0])) rc = fail(FIC_E_HIP, "k_scale launch failed");
     const uint32_t* sse[kQtMaxLevels];
@@ -136,6 +152,19 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
         if (fic_launch_leaf_sse<typename Fmt::Dev>(v.image, v.scaled, v.qrows, v.iso, (uint32_t*)(scratch + o_sse[l]), L.g[l], nullptr))
             rc = fail(FIC_E_HIP, "k_leaf_sse launch failed");
     }
+    if (rc == FIC_OK && budget) {
+        // rank S = (M - Ntop) / 3 in descending order: the S blocks of larger key may split, the block of rank S must not
+        const int64_t S = (budget->max_leaves - top.Nr) / 3;
+        uint32_t* d_sel = (uint32_t*)(scratch + o_sel);
+        if (fic_launch_qt_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, n1, (uint32_t*)(scratch + o_keys), nullptr) ||
+            fic_launch_qt_select((const uint32_t*)(scratch + o_keys), (uint32_t)nkeys, (uint32_t)(S < nkeys ? S : nkeys), d_sel, nullptr))
+            rc = fail(FIC_E_HIP, "%s budget select launch failed", Fmt::kStream.kind);
+        if (rc == FIC_OK) {     // by value into the compaction, like n below; the caller gets it anyway
+            hipError_t e = hipMemcpy(&threshold, d_sel + 4 * 256 + 1, sizeof(float), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
+            else *budget->threshold_out = threshold;
+        }
+    }
     int* d_offs = (int*)(scratch + o_offs);
     if (rc == FIC_OK && fic_launch_qt_compact<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, threshold,
                                                                  (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr))
@@ -146,6 +175,15 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
     if (rc == FIC_OK && n_leaves) *n_leaves = n;
+    if (rc == FIC_OK && budget && budget->stats4) {
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stats4");
+        if (fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, threshold, (unsigned long long*)(scratch + o_stats), nullptr))
+            rc = fail(FIC_E_HIP, "%s tree statistics launch failed", Fmt::kStream.kind);
+        else {
+            hipError_t e = hipMemcpy(budget->stats4, scratch + o_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
+        }
+    }
     if (rc == FIC_OK && leaves) {
         if (capacity < n) rc = fail(FIC_E_CAPACITY, "%s encode: %d leaves, room for %lld", Fmt::kStream.kind, n, (long long)capacity);
         else {
@@ -215,6 +253,48 @@ int fic_encode_gray_quadtree_argb(const int32_t* argb, int w, int h, int B_max, 
     return qt_encode<QtGreyHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
 }
 
+int fic_encode_gray_quadtree_budget_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int64_t max_leaves,
+                                       int device, int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out, uint64_t* stats4)
+{
+    if (!gray || !leaves || !n_leaves || !threshold_out) return fail(FIC_E_ARGUMENT, "fic_encode_gray_quadtree_budget_u8: null argument");
+    const QtBudget b{max_leaves, threshold_out, stats4};
+    return qt_encode<QtGreyHost>(gray, nullptr, w, h, B_max, B_min, wK, n_iso, 0.0f, device, leaves, capacity, n_leaves, nullptr, 0, &b);
+}
+
+int fic_encode_gray_quadtree_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int64_t max_leaves,
+                                         int device, int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out, uint64_t* stats4)
+{
+    if (!argb || !leaves || !n_leaves || !threshold_out) return fail(FIC_E_ARGUMENT, "fic_encode_gray_quadtree_budget_argb: null argument");
+    const QtBudget b{max_leaves, threshold_out, stats4};
+    return qt_encode<QtGreyHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, 0.0f, device, leaves, capacity, n_leaves, nullptr, 0, &b);
+}
+
+// Test hook: the select of an encode to a budget (k_qt_select_hist x 4, k_qt_select_final) on the caller's keys
+int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int64_t rank, uint32_t* key_out, float* threshold_out, int64_t* above_out)
+{
+    if (!keys || !key_out || !threshold_out || !above_out) return fail(FIC_E_ARGUMENT, "fic_debug_qt_select: null argument");
+    if (n < 1 || n >= 0x7FFFFFFFll || rank < 0) return fail(FIC_E_ARGUMENT, "fic_debug_qt_select: n = %lld, rank = %lld", (long long)n, (long long)rank);
+    int rc = check_device(device);
+    if (rc) return rc;
+    char* scratch = nullptr;
+    const size_t o_sel = align256((size_t)n * 4);
+    rc = dev_alloc(&scratch, o_sel + FIC_QT_SELECT_WORDS * 4);
+    if (rc) return rc;
+    uint32_t res[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemcpy(scratch, keys, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && fic_launch_qt_select((const uint32_t*)scratch, (uint32_t)n, (uint32_t)(rank < n ? rank : n), (uint32_t*)(scratch + o_sel), nullptr))
+        rc = fail(FIC_E_HIP, "fic_debug_qt_select: launch failed");
+    if (rc == FIC_OK && e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 4, sizeof(res), hipMemcpyDeviceToHost);
+    if (rc == FIC_OK && e != hipSuccess) rc = fail(FIC_E_HIP, "fic_debug_qt_select: %s", hipGetErrorString(e));
+    ErrKeep keep;
+    (void)hipFree(scratch);
+    if (rc) return rc;
+    *key_out = res[0];
+    memcpy(threshold_out, &res[1], sizeof(float));
+    *above_out = res[2];
+    return FIC_OK;
+}
+
 int fic_debug_quadtree_sse(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int device, uint32_t* sse,
                            int64_t capacity)
 {
@@ -239,6 +319,14 @@ int fic_encode_rgb_quadtree_argb(const int32_t* argb, int w, int h, int B_max, i
 {
     if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_argb: null argument");
     return qt_encode<QtRgbHost>(nullptr, argb, w, h, B_max, B_min, wK, 1, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_encode_rgb_quadtree_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int64_t max_leaves, int device,
+                                        int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out, uint64_t* stats4)
+{
+    if (!argb || !leaves || !n_leaves || !threshold_out) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_budget_argb: null argument");
+    const QtBudget b{max_leaves, threshold_out, stats4};
+    return qt_encode<QtRgbHost>(nullptr, argb, w, h, B_max, B_min, wK, 1, 0.0f, device, leaves, capacity, n_leaves, nullptr, 0, &b);
 }
 
 int fic_debug_rgb_quadtree_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int device, uint32_t* sse,
@@ -266,6 +354,15 @@ int fic_encode_rgb_quadtree_iso_argb(const int32_t* argb, int w, int h, int B_ma
 {
     if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_iso_argb: null argument");
     return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_encode_rgb_quadtree_iso_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int64_t max_leaves,
+                                            int device, int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out,
+                                            uint64_t* stats4)
+{
+    if (!argb || !leaves || !n_leaves || !threshold_out) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_iso_budget_argb: null argument");
+    const QtBudget b{max_leaves, threshold_out, stats4};
+    return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, 0.0f, device, leaves, capacity, n_leaves, nullptr, 0, &b);
 }
 
 int fic_debug_rgb_quadtree_iso_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,

@@ -231,6 +231,17 @@ template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
                           hipStream_t s);
+// Encode to a leaf budget, on the same per-level SSE arrays.  keys u32 [Ntop + n1]: the split key e(v) of every
+// block above B_min, level 0 first; n1 = N_r of level 1 with three levels, else 0.
+int fic_launch_qt_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
+                       hipStream_t s);
+// Radix select over n < 2^31 keys: work u32 [FIC_QT_SELECT_WORDS] = four 256-bin histograms, then {K, bits of the threshold,
+// #{keys > K}, 0}, K the key of rank `rank` <= n in descending order (0 past the last key), the threshold the smallest float >= K / 256
+constexpr int FIC_QT_SELECT_WORDS = 4 * 256 + 4;
+int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s);
+// stats u64 [4] = {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4} of the tree under `threshold`
+int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
+                             unsigned long long* stats, hipStream_t s);
 // one paint (decodeGreyScale / decodeRGB) of the n leaves of side g.B (one plane; g = that level's geometry)
 template <typename Fmt>
 int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,

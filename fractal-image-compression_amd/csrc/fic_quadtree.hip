@@ -15,6 +15,9 @@
 //                            top-down split of every top-level (B_max) block, leaf count, exclusive scan, ordered scatter
 //   k_decode_paint_leaves<Fmt, B>
 //                            one decoder paint of the leaves of one level (three launches per iteration, one per level)
+//   k_qt_keys / k_qt_select_hist / k_qt_select_final / k_qt_tree_stats
+//                            encode to a leaf budget: the split keys e(v), a radix select of the key that
+//                            the budget falls on and its threshold, the collage SSE and the leaves per level of the tree
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -262,6 +265,129 @@ __global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __
 }
 
 // ---------------------------------------------------------------------------------------------
+// Encode to a leaf budget.  Block v of side B above B_min splits under threshold t iff (double) SSE_v >
+// (double) t * B * B, that is iff k(v) = SSE_v * (256 / B^2) > 256 t: one denominator for every level (x1 at B = 16, x4 at
+// B = 8; below 2^26 for an encoder's own rows, saturated at 2^32 - 1 for k_leaf_sse's all-ones mark).  v is reached only when
+// every ancestor splits, so with e(v) = min(k(v), k(parent(v)), ..) the tree under t has Ntop + 3 #{v : e(v) > 256 t} leaves.
+// k_qt_keys writes e(v), the blocks of level 0 first, then (three levels) those of level 1; one thread per block.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t qt_key(const FicQtLevels& L, int l, int j)
+{
+    const int B = L.B_max >> l;
+    const unsigned long long k = (unsigned long long)L.sse[l][j] * (unsigned long long)(256 / (B * B));
+    return k > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)k;
+}
+
+__global__ __launch_bounds__(256) void k_qt_keys(FicQtLevels L, int n1, uint32_t* __restrict__ keys)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < L.Ntop) {
+        keys[t] = qt_key(L, 0, t);
+    } else if (t < L.Ntop + n1) {
+        const int j = t - L.Ntop, x = j % L.Rw[1], y = j / L.Rw[1];
+        const uint32_t k = qt_key(L, 1, j), kp = qt_key(L, 0, (y / 2) * L.Rw[0] + x / 2);
+        keys[t] = k < kp ? k : kp;
+    }
+}
+
+// Radix select of the key of rank `rank` in descending order (rank 0: the largest), four passes of 8 bits from the top byte.
+// bins u32 [4][256], zeroed by the launcher: bins[p] is the histogram of byte 3 - p over the keys whose higher bytes are the
+// prefix chosen so far.  The keys are thought followed by endlessly many zeros, so a rank past the last key selects 0.
+//
+// qt_select_resolve: prefix and remaining rank after the first `npass` passes, from their final bins alone; every workgroup
+// that needs them computes them again (256 values per pass; wave 0 holds four bins per lane and scans the lane sums from the
+// top), so no state is written by more than one workgroup.  Per pass the digit d is the largest with #{digit >= d} > rem,
+// 0 when there is none (the zeros behind the keys); rem then drops by #{digit > d}.  Called by all 256 threads.
+__device__ __forceinline__ void qt_select_resolve(const uint32_t* __restrict__ bins, int npass, uint32_t rank, uint32_t& prefix, uint32_t& rem)
+{
+    __shared__ uint32_t s_prefix, s_rem;
+    if (threadIdx.x == 0) { s_prefix = 0; s_rem = rank; }
+    __syncthreads();
+    for (int p = 0; p < npass; p++) {
+        const uint32_t pre = s_prefix, r = s_rem;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int lane = threadIdx.x;
+            const uint4 b = *(const uint4*)(bins + 256 * p + 4 * lane);
+            const uint32_t own = b.x + b.y + b.z + b.w;
+            uint32_t incl = own;                            // keys of digit >= 4 lane
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t v = __shfl_down(incl, off, 64);
+                if (lane + off < 64) incl += v;
+            }
+            const uint32_t above = incl - own;              // keys of digit >= 4 (lane + 1)
+            if (above <= r && r < incl) {                   // one lane at most
+                const uint32_t c3 = above + b.w, c2 = c3 + b.z, c1 = c2 + b.y;
+                const int d = r < c3 ? 3 : (r < c2 ? 2 : (r < c1 ? 1 : 0));
+                s_prefix = (pre << 8) | (uint32_t)(4 * lane + d);
+                s_rem = r - (d == 3 ? above : (d == 2 ? c3 : (d == 1 ? c2 : c1)));
+            } else if (lane == 0 && incl <= r) {            // fewer keys than the rank asks for: digit 0
+                s_prefix = pre << 8;
+                s_rem = r - (incl - b.x);
+            }
+        }
+        __syncthreads();
+    }
+    prefix = s_prefix;
+    rem = s_rem;
+}
+
+// One pass: 256 threads per workgroup with a grid stride over the keys, a 256-bin histogram in LDS, one global atomic per
+// non-empty bin.
+__global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t rank, uint32_t* __restrict__ bins,
+                                                        int pass)
+{
+    __shared__ uint32_t hist[256];
+    hist[threadIdx.x] = 0;
+    uint32_t prefix, rem;
+    qt_select_resolve(bins, pass, rank, prefix, rem);       // its barriers also cover hist's zeroes
+    const int shift = 24 - 8 * pass;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const uint32_t k = keys[i];
+        if (pass == 0 || (k >> (shift + 8)) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint32_t c = hist[threadIdx.x];
+    if (c) atomicAdd(&bins[256 * pass + threadIdx.x], c);
+}
+
+// One workgroup: resolves the last pass.  out = {K, the bits of the threshold, #{keys > K}, 0}; the threshold is the smallest
+// float >= K / 256: K rounded up to a float, times 2^-8 (exact).
+__global__ __launch_bounds__(256) void k_qt_select_final(const uint32_t* __restrict__ bins, uint32_t rank, uint32_t* __restrict__ out)
+{
+    uint32_t K, rem;
+    qt_select_resolve(bins, 4, rank, K, rem);
+    if (threadIdx.x == 0) {
+        out[0] = K;
+        out[1] = __float_as_uint(__fmul_rn(__uint2float_ru(K), 0x1p-8f));
+        out[2] = rank - rem;
+        out[3] = 0;
+    }
+}
+
+// stats u64 [4], zeroed by the launcher: the collage SSE summed over the leaves of the tree under L.threshold, and its leaves
+// of side B_max, B_max / 2, B_max / 4.  One thread per top-level block, k_qt_count's walk; wave sums, then one atomic per
+// wave and non-zero value.
+__global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L, unsigned long long* __restrict__ stats)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long v[4] = {0, 0, 0, 0};
+    if (t < L.Ntop)
+        qt_walk(L, t, [&](int x, int y, int l) {
+            const int B = L.B_max >> l;
+            v[0] += L.sse[l][(y / B) * L.Rw[l] + x / B];
+            v[1 + l]++;
+        });
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+        if ((threadIdx.x & 63) == 0 && v[i]) atomicAdd(&stats[i], v[i]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // One segment -- S pixels from x0 on; the whole row up to B = 16 -- of pixel row ry of one decoder paint of leaf e, grey
 // (FC:385-407): paints prow, stores the squared changes to srow (both at the segment), returns their sum.
 // ---------------------------------------------------------------------------------------------
@@ -374,16 +500,15 @@ int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* s
     return 0;
 }
 
-template <typename Fmt>
-int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
-                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s)
+// qrows / iso NULL: for the kernels that read the SSE alone
+static FicQtLevels qt_levels_arg(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw, int nl,
+                                 int B_max, int Rw_top, int Ntop, float threshold)
 {
     FicQtLevels L{};
     for (int l = 0; l < nl; l++) {
         L.sse[l] = sse[l];
-        L.qrows[l] = qrows[l];
-        L.iso[l] = iso[l];
+        L.qrows[l] = qrows ? qrows[l] : nullptr;
+        L.iso[l] = iso ? iso[l] : nullptr;
         L.Rw[l] = Rw[l];
     }
     L.nl = nl;
@@ -391,6 +516,47 @@ int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrow
     L.Rw_top = Rw_top;
     L.Ntop = Ntop;
     L.threshold = threshold;
+    return L;
+}
+
+int fic_launch_qt_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
+                       hipStream_t s)
+{
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f);
+    hipLaunchKernelGGL(k_qt_keys, dim3((Ntop + n1 + 255) / 256), dim3(256), 0, s, L, n1, keys);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s)
+{
+    if (hipMemsetAsync(work, 0, FIC_QT_SELECT_WORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
+    const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
+    for (int pass = 0; pass < 4; pass++) {
+        hipLaunchKernelGGL(k_qt_select_hist, dim3(nb), dim3(256), 0, s, keys, n, rank, work, pass);
+        FIC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_qt_select_final, dim3(1), dim3(256), 0, s, (const uint32_t*)work, rank, work + 4 * 256);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
+                             unsigned long long* stats, hipStream_t s)
+{
+    if (hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold);
+    hipLaunchKernelGGL(k_qt_tree_stats, dim3((Ntop + 255) / 256), dim3(256), 0, s, L, stats);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename Fmt>
+int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
+                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
+                          hipStream_t s)
+{
+    const FicQtLevels L = qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold);
     const int nb = (Ntop + 255) / 256;
     hipLaunchKernelGGL(k_qt_count, dim3(nb), dim3(256), 0, s, L, counts);
     FIC_LAUNCH_CHECK();

@@ -364,4 +364,16 @@ int64_t fic_write_run_rgb_quadtree_iso(const int32_t* leaves, int n_leaves, int 
     return write_quadtree(kQtRgbIsoStream, leaves, n_leaves, w, h, B_max, B_min, wK, 8, out, capacity);
 }
 
+int64_t fic_quadtree_leaves_for_bytes(int tag, int n_iso, int64_t max_bytes)
+{
+    const QtFormat* F = nullptr;
+    for (const QtFormat* f : {&kQtGreyStream, &kQtRgbStream, &kQtRgbIsoStream})
+        if (f->tag == tag) F = f;
+    if (!F) return fail(FIC_E_ARGUMENT, "fic_quadtree_leaves_for_bytes: tag %d is no quadtree stream (2, 3, 6)", tag);
+    if ((n_iso != 1 && n_iso != 8) || (tag == 3 && n_iso != 1))
+        return fail(FIC_E_ARGUMENT, "fic_quadtree_leaves_for_bytes: n_iso=%d for tag %d", n_iso, tag);
+    if (max_bytes < 4 * kQtHeaderInts) return fail(FIC_E_CAPACITY, "%s: %lld bytes do not hold the 32-byte header", F->writer, (long long)max_bytes);
+    return (max_bytes - 4 * kQtHeaderInts) / (4 * qt_run_ints(*F, n_iso));
+}
+
 }  // extern "C"

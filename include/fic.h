@@ -385,6 +385,43 @@ FIC_API int fic_decode_rgb_quadtree_iso_run(const uint8_t* run, int64_t len, int
 FIC_API int fic_debug_rgb_quadtree_iso_sse(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int device,
                                            uint32_t* sse, int64_t capacity);
 
+/* ---- quadtree encode to a leaf budget ------------------------------------------- */
+/* The quadtree encodes above with a size limit in place of the threshold: the tree of at most max_leaves leaves at the
+ * smallest threshold that allows it.  Levels, geometry, wK, per-level codebooks, collage SSE, split rule, leaf order and leaf
+ * rows are those of the fixed-threshold entry of the same name; the levels are encoded once, and the threshold is chosen on
+ * the device from the SSE arrays of that encode.  With N_top the blocks of side B_max, k(v) = SSE_v * (256 / B^2) for a block v
+ * of side B > B_min (v splits under t iff k(v) > 256 t) and e(v) the minimum of k over v and its ancestors, the tree under t has
+ * N_top + 3 #{v : e(v) > 256 t} leaves.  Let S = (max_leaves - N_top) / 3 and K the (S+1)-th largest e(v), 0 when there are S
+ * or fewer: *threshold_out = the smallest float >= K / 256, which is the smallest non-negative float whose tree has at most
+ * max_leaves leaves, and `leaves` is exactly what the fixed-threshold entry returns for it.  Blocks that share the key K all
+ * stay whole, so the tree may have fewer than max_leaves leaves; it never has more.
+ *   max_leaves     >= N_top, else FIC_E_ARGUMENT (checked with the other arguments, before any device work)
+ *   threshold_out  the threshold chosen; set on FIC_E_CAPACITY too, like *n_leaves
+ *   stats4         NULL, or uint64 [4] = {collage SSE summed over the leaves, leaves of side B_max, B_max / 2, B_max / 4} */
+FIC_API int fic_encode_gray_quadtree_budget_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                               int64_t max_leaves, int device, int32_t* leaves, int64_t capacity, int* n_leaves,
+                                               float* threshold_out, uint64_t* stats4);
+FIC_API int fic_encode_gray_quadtree_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                                 int64_t max_leaves, int device, int32_t* leaves, int64_t capacity, int* n_leaves,
+                                                 float* threshold_out, uint64_t* stats4);
+/* The same for the colour codec (tag 3; threshold in decodeRGB's unit) and for colour with n_iso = 1 or 8 isometries (tag 6). */
+FIC_API int fic_encode_rgb_quadtree_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int64_t max_leaves,
+                                                int device, int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out,
+                                                uint64_t* stats4);
+FIC_API int fic_encode_rgb_quadtree_iso_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                                    int64_t max_leaves, int device, int32_t* leaves, int64_t capacity,
+                                                    int* n_leaves, float* threshold_out, uint64_t* stats4);
+/* Host only: the largest leaf count whose quadtree stream of `tag` (2 grey, 3 colour, 6 colour with isometries) fits
+ * max_bytes: a 32-byte header, then 4 (tag 2, n_iso = 1), 5 (tag 2, n_iso = 8), 6 (tag 3) or 7 (tag 6) ints per leaf.  0 when
+ * only the header fits.  FIC_E_ARGUMENT for another tag, an n_iso other than 1 or 8, or tag 3 with n_iso = 8; FIC_E_CAPACITY
+ * when max_bytes < 32.  Whether the count is a valid budget (>= N_top) is the encode's to say. */
+FIC_API int64_t fic_quadtree_leaves_for_bytes(int tag, int n_iso, int64_t max_bytes);
+/* Test hook: the budget's radix select alone, on the caller's keys uint32 [n], 1 <= n < 2^31.  *key_out = the key of rank
+ * `rank` >= 0 in descending order (rank 0: the largest; 0 for rank >= n), *threshold_out = the smallest float >= key / 256,
+ * *above_out = the number of keys greater than the key. */
+FIC_API int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int64_t rank, uint32_t* key_out, float* threshold_out,
+                                int64_t* above_out);
+
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
  *                     group-Fourier form, for 8 isometries at B = 8; k_sweep_fast otherwise)
