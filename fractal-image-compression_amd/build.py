@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libfic_hip.so")
-SOURCES = ["fic_prep.hip", "fic_sweep.hip", "fic_q.hip", "fic_d4.hip", "fic_decode.hip", "fic_rgb.hip", "fic_quadtree.hip", "fic_stream.cpp", "fic_capi.cpp", "fic_capi_decode.cpp", "fic_capi_rgb.cpp", "fic_capi_multi.cpp", "fic_capi_quadtree.cpp"]
+SOURCES = ["fic_prep.hip", "fic_sweep.hip", "fic_lsq.hip", "fic_q.hip", "fic_d4.hip", "fic_decode.hip", "fic_rgb.hip", "fic_quadtree.hip", "fic_stream.cpp", "fic_capi.cpp", "fic_capi_lsq.cpp", "fic_capi_decode.cpp", "fic_capi_rgb.cpp", "fic_capi_multi.cpp", "fic_capi_quadtree.cpp"]
 # round 1's exact-covariance matrix-core sweeps ("sweep" = 3 / 4): superseded by k_sweep_q, kept as independent cross-checks
 # for the test-suite.  FIC_BUILD_XCHECK=0 leaves them out (a deployment build; tests that need them skip).
 XCHECK_SOURCES = ["fic_mfma.hip", "fic_bf16.hip"]

@@ -148,6 +148,11 @@ def lib():
         "fic_encode_rgb_quadtree_budget_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
         "fic_encode_rgb_quadtree_iso_budget_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
         "fic_quadtree_leaves_for_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+        "fic_ctx_get_lsq_error_host": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "fic_encode_gray_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p, C.POINTER(C.c_int64)]),
+        "fic_encode_gray_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p, C.POINTER(C.c_int64)]),
+        "fic_encode_gray_quadtree_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_encode_gray_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
@@ -230,17 +235,41 @@ def decode_gray_run(run, device=0, avg_error_in=0.0, zoom=1):
     return out[:cap].reshape(h, w), np.float32(avg.value), it.value
 
 
-def encode_gray_oneshot(gray, B, wK, n_iso=1, device=0):
-    """The one-shot C entry point fic_encode_gray_u8 (host buffers in and out; what the JNI shim binds)."""
-    g = np.ascontiguousarray(gray, np.uint8)
+SEARCHES = {"reference": 0, "lsq": 1}
+
+
+def search_id(search):
+    """"reference" (the reference's criterion) / "lsq" (least squares), or the option value 0 / 1 itself."""
+    if search in SEARCHES:
+        return SEARCHES[search]
+    if search in (0, 1):
+        return int(search)
+    raise FicError(-3, f"search must be 'reference' or 'lsq', not {search!r}")
+
+
+def encode_gray_oneshot(gray, B, wK, n_iso=1, device=0, search="reference"):
+    """The one-shot C entry point fic_encode_gray_u8 (host buffers in and out; what the JNI shim binds).  search="lsq":
+    fic_encode_gray_lsq_u8, with the winners' errors as "E" (int64 [N_r]).  An int32 [H, W] input is taken as ARGB pixels
+    (the _argb twins)."""
+    g = np.asarray(gray)
+    argb = g.dtype != np.uint8
+    g = np.ascontiguousarray(g, np.int32 if argb else np.uint8)
     h, w = g.shape
+    p = ptr(g, C.c_int32 if argb else C.c_uint8)
     Rw, Rh, Dw, Dh = geometry(w, h, B)
     nr = Rw * Rh
     r = {"idx_local": np.zeros(nr, np.int32), "a": np.zeros(nr, np.float32), "b": np.zeros(nr, np.float32),
          "iso": np.zeros(nr, np.int32), "qrows": np.zeros((nr, 3), np.int32)}
-    check(lib().fic_encode_gray_u8(ptr(g, C.c_uint8), w, h, B, Dw if wK is None else wK, n_iso, device,
-                                   ptr(r["idx_local"], C.c_int32), ptr(r["a"], C.c_float), ptr(r["b"], C.c_float),
-                                   ptr(r["iso"], C.c_int32), ptr(r["qrows"], C.c_int32)))
+    out = [ptr(r["idx_local"], C.c_int32), ptr(r["a"], C.c_float), ptr(r["b"], C.c_float), ptr(r["iso"], C.c_int32),
+           ptr(r["qrows"], C.c_int32)]
+    L = lib()
+    if search_id(search):
+        r["E"] = np.zeros(nr, np.int64)
+        fn = L.fic_encode_gray_lsq_argb if argb else L.fic_encode_gray_lsq_u8
+        check(fn(p, w, h, B, Dw if wK is None else wK, n_iso, device, *out, ptr(r["E"], C.c_int64)))
+    else:
+        fn = L.fic_encode_gray_argb if argb else L.fic_encode_gray_u8
+        check(fn(p, w, h, B, Dw if wK is None else wK, n_iso, device, *out))
     return r
 
 
@@ -457,19 +486,21 @@ def _qt_levels(B_max, B_min):
     return [B for B in (16, 8, 4) if B_min <= B <= B_max]
 
 
-def encode_gray_quadtree(gray, B_max, B_min, wK=0, n_iso=1, threshold=float("inf"), device=0):
+def encode_gray_quadtree(gray, B_max, B_min, wK=0, n_iso=1, threshold=float("inf"), device=0, search="reference"):
     """Quadtree encode of `gray`: uint8 [H, W] (fic_encode_gray_quadtree_u8) or the int32 ARGB pixels of RasterImage.argb as
     [H, W] (fic_encode_gray_quadtree_argb).  wK = 0: full search at every level.  Returns the leaf table int32 [n_leaves, 7] with the columns
-    QT_LEAF_FIELDS, in stream order (top-level blocks in scanline order, children TL, TR, BL, BR depth first)."""
+    QT_LEAF_FIELDS, in stream order (top-level blocks in scanline order, children TL, TR, BL, BR depth first).
+    search="lsq": the per-level codebooks come from the least-squares search (fic_encode_gray_quadtree_lsq_u8 / _argb)."""
     g = np.asarray(gray)
+    lsq = search_id(search)
     if g.dtype == np.uint8:
         g = np.ascontiguousarray(g)
         h, w = g.shape
-        fn, p = lib().fic_encode_gray_quadtree_u8, ptr(g, C.c_uint8)
+        fn, p = (lib().fic_encode_gray_quadtree_lsq_u8 if lsq else lib().fic_encode_gray_quadtree_u8), ptr(g, C.c_uint8)
     else:
         g = np.ascontiguousarray(g, np.int32)
         h, w = g.shape
-        fn, p = lib().fic_encode_gray_quadtree_argb, ptr(g, C.c_int32)
+        fn, p = (lib().fic_encode_gray_quadtree_lsq_argb if lsq else lib().fic_encode_gray_quadtree_argb), ptr(g, C.c_int32)
     cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
     out = np.zeros((max(cap, 1), 7), np.int32)
     n = C.c_int()

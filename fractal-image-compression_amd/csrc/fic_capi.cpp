@@ -28,7 +28,7 @@ int ctx_free_all(fic_ctx* c)
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     c->ev.clear();
     if (c->own_stream) { (void)hipStreamDestroy(c->own_stream); c->own_stream = nullptr; }
-    void* ptrs[] = {c->gray_own, c->argb_stage, c->collage, c->decoded, c->dec_state, c->dec_sq, c->mfma_poolB, c->mfma_rngA, c->mfma_sw, c->mfma_rconst, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, c->q_fin, c->q_stats, c->d4_rng, c->d4_pool, c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var,
+    void* ptrs[] = {c->gray_own, c->argb_stage, c->collage, c->decoded, c->dec_state, c->dec_sq, c->mfma_poolB, c->mfma_rngA, c->mfma_sw, c->mfma_rconst, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, c->q_fin, c->q_stats, c->d4_rng, c->d4_pool, c->lsq.pool, c->lsq.rng, c->lsq.slotE, c->lsq.slotC, c->lsq.E, c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var,
                     c->b.pool_s64, c->b.rng_pix, c->b.rng_st, c->b.key, c->o.idx_local, c->o.idx_global, c->o.iso,
                     c->o.a, c->o.b, c->o.err, c->o.qrows, c->o.records};
     for (void* p : ptrs)
@@ -119,13 +119,14 @@ int time_end(fic_ctx* c, hipStream_t s)
 // Pool chunks per range tile for the VALU sweeps (k_sweep_fast, k_sweep_d4).  Measured (profiles/r01l_chunk_sweep.txt):
 // every chunk pays a start-up (its first block is evaluated exactly and tau restarts), so chunks stay >= 4096 blocks
 // while aiming at ~48 K wave tasks for load balance; only a launch that could not otherwise fill the chip (one small
-// image) splits finer.  `base_waves` = wave tasks per chunk.
-int valu_chunk_count(const fic_ctx* c, long long base_waves)
+// image) splits finer.  `base_waves` = wave tasks per chunk.  (k_sweep_lsq_fast pays more per start-up -- its epilogue is
+// 64-bit integer work -- and asks for `target` = 6144 wave tasks, about one resident round: profiles/lsq_timing.txt.)
+int valu_chunk_count(const fic_ctx* c, long long base_waves, long long target = 49152)
 {
     const FicGeom& g = c->g;
     int nchunks = c->opt_chunks;
     if (nchunks <= 0) {
-        long long want = (49152 + base_waves - 1) / base_waves;
+        long long want = (target + base_waves - 1) / base_waves;
         long long cap = g.Nd / 4096;
         if (cap < 1) cap = 1;
         long long nc = want < cap ? want : cap;
@@ -381,14 +382,83 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
     return FIC_OK;
 }
 
+// Least-squares search ("search" = 1, fic_lsq.hip) of the span: pool build and range prep as for the VALU
+// sweeps, the extra sums, k_sweep_lsq_generic (windows, "sweep" = 1) or k_sweep_lsq_fast (full search), k_finalize_lsq.
+int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
+{
+    const FicGeom& g = c->g;
+    int kind = c->opt_sweep;
+    if (kind < 0 || kind > 2) return fail(FIC_E_ARGUMENT, "least-squares search: sweep must be 0 (auto), 1 (generic) or 2 (fast), not %d", kind);
+    if (kind == 0) kind = g.full ? 2 : 1;
+    if (kind == 2 && !g.full) return fail(FIC_E_ARGUMENT, "fast sweep needs full search (wK == Dw == Dh)");
+    if ((long long)g.wK * g.wK * g.n_iso >= (1ll << 32)) return fail(FIC_E_GEOMETRY, "least-squares search: the window has 2^32 candidates or more");
+    const size_t P = (size_t)g.planes;
+    const int tsz = 64 * g.NR;
+    const int tile0 = range_begin / tsz;
+    const int tile1 = (range_begin + range_count + tsz - 1) / tsz;
+    const int ntiles = tile1 - tile0;
+    int nchunks = 1, chunk_len = 0, nslots = 1;
+    if (kind == 2) {
+        int NR, NC;
+        fic_fast_variant(g.B, g.n_iso, &NR, &NC);
+        nchunks = valu_chunk_count(c, (long long)ntiles * (g.n_iso / NC) * g.planes, 6144);
+        chunk_len = (g.Nd + nchunks - 1) / nchunks;
+        chunk_len = (chunk_len + 1) & ~1;              // even: the sweep consumes blocks in pairs
+        nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
+        nslots = fic_lsq_slots(g, nchunks);
+    }
+    if (!c->lsq.pool) {
+        HIP_TRY(hipMalloc(&c->lsq.pool, P * g.Nd_pad * 16));
+        HIP_TRY(hipMemsetAsync(c->lsq.pool, 0, P * g.Nd_pad * 16, s));    // the tail the prefetch over-reads
+    }
+    if (!c->lsq.rng) HIP_TRY(hipMalloc(&c->lsq.rng, P * g.Nr_pad * 8));
+    if (!c->lsq.E) HIP_TRY(hipMalloc(&c->lsq.E, P * g.Nr * 8));
+    if (c->lsq_slots < (size_t)nslots) {
+        HIP_TRY(hipStreamSynchronize(c->last_stream));
+        if (c->lsq.slotE) (void)hipFree(c->lsq.slotE);
+        if (c->lsq.slotC) (void)hipFree(c->lsq.slotC);
+        c->lsq.slotE = nullptr;
+        c->lsq.slotC = nullptr;
+        c->lsq_slots = 0;
+        HIP_TRY(hipMalloc(&c->lsq.slotE, P * nslots * g.Nr_pad * 8));
+        HIP_TRY(hipMalloc((void**)&c->lsq.slotC, P * nslots * g.Nr_pad * 4));
+        c->lsq_slots = (size_t)nslots;
+    }
+    if (fic_launch_scale(c->b.gray, c->b.scaled, g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
+    if (fic_launch_pool(c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var, c->b.pool_s64, g, s))
+        return fail(FIC_E_HIP, "k_pool launch failed");
+    if (!c->b.rng_pix) {
+        int rca = dev_alloc(&c->b.rng_pix, P * g.Nr_pad * g.n_iso * g.DW);
+        if (rca) return rca;
+    }
+    if (fic_launch_range(c->b.gray, c->b.rng_pix, c->b.rng_st, g, s, 1)) return fail(FIC_E_HIP, "k_range launch failed");
+    if (fic_launch_lsq_stat(c->b, c->lsq, g, s)) return fail(FIC_E_HIP, "k_lsq_stat launch failed");
+    int rc = time_begin(c, s);
+    if (rc) return rc;
+    if (kind == 1) {
+        if (fic_launch_sweep_lsq_generic(c->b, c->lsq, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_sweep_lsq_generic launch failed");
+    } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats)) {
+        return fail(FIC_E_HIP, "k_sweep_lsq_fast launch failed");
+    }
+    rc = time_end(c, s);
+    if (rc) return rc;
+    if (fic_launch_finalize_lsq(c->b, c->o, c->lsq, nslots, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_finalize_lsq launch failed");
+    c->last_chunks = nchunks;
+    c->last_kind = kind;
+    c->last_fused = 0;
+    c->last_search = 1;
+    c->encoded_any = true;
+    return FIC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 #ifdef FIC_BUILD_XCHECK
-const char* fic_version(void) { return "fic-hip 0.3 (gfx950, +xcheck sweeps)"; }
+const char* fic_version(void) { return "fic-hip 0.4 (gfx950, +xcheck sweeps)"; }
 #else
-const char* fic_version(void) { return "fic-hip 0.3 (gfx950)"; }
+const char* fic_version(void) { return "fic-hip 0.4 (gfx950)"; }
 #endif
 
 int fic_device_count(void)
@@ -534,6 +604,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
     hipStream_t s = (hipStream_t)hip_stream;
     c->last_stream = s;
     if (range_count == 0) return FIC_OK;
+    if (c->opt_search == 1) return lsq_encode(c, range_begin, range_count, s);
 
     // which sweep
     int kind = c->opt_sweep;
@@ -614,6 +685,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
     c->last_chunks = nchunks;
     c->last_kind = kind;
     c->last_fused = fused_prep ? 1 : 0;
+    c->last_search = 0;
     // kinds 5 and 6 build no lane-transposed isometry copies: the finaliser recomputes the winner's covariance from the image
     if (!fused_prep &&
         fic_launch_finalize(c->b, c->o, g, range_begin, range_count, s, (kind == 5 || kind == 6) ? 1 : 0)) return fail(FIC_E_HIP, "k_finalize launch failed");
@@ -704,9 +776,16 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
 {
     if (!c || !name) return fail(FIC_E_ARGUMENT, "fic_ctx_set_option: null argument");
     if (!strcmp(name, "sweep")) {
+        if (c->opt_search == 1 && (value < 0 || value > 2))
+            return fail(FIC_E_ARGUMENT, "sweep must be 0 (auto), 1 (generic) or 2 (fast) under the least-squares search (\"search\" = 1)");
         if (value < 0 || value > 6)
             return fail(FIC_E_ARGUMENT, "sweep must be 0 (auto), 1 (generic), 2 (fast, VALU), 3 (matrix-core, exact covariances), 4 (matrix-core, i8 operands), 5 (VALU, group-Fourier isometries) or 6 (matrix-core, normalised f16 prune GEMM)");
         c->opt_sweep = value;
+    } else if (!strcmp(name, "search")) {
+        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "search must be 0 (the reference's criterion) or 1 (least squares)");
+        if (value == 1 && c->opt_sweep > 2)
+            return fail(FIC_E_ARGUMENT, "the least-squares search (\"search\" = 1) has sweeps 0 (auto), 1 (generic) and 2 (fast), not %d", c->opt_sweep);
+        c->opt_search = value;
     } else if (!strcmp(name, "chunks")) {
         if (value < 0) return fail(FIC_E_ARGUMENT, "chunks must be >= 0");
         c->opt_chunks = value;
@@ -786,6 +865,7 @@ int fic_ctx_last_kernel(fic_ctx* c, char* out, int capacity)
     else if (kind == 6 && fic_q_shape16(g)) snprintf(buf, sizeof(buf), "k_sweep_q16<%d, %s>", NK, multi);
     else if (kind == 6 && shorts) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, %d>", NK, g.n_iso == 1 ? 0 : (g.B == 4 ? 1 : 2));
     else if (kind == 6) snprintf(buf, sizeof(buf), "k_sweep_q<%d, %d, %s>", NK, g.n_iso == 1 ? 0 : (g.B == 4 ? 1 : 2), multi);
+    else if (c->last_search == 1) snprintf(buf, sizeof(buf), kind == 2 ? "k_sweep_lsq_fast" : "k_sweep_lsq_generic");
     else if (kind == 5) snprintf(buf, sizeof(buf), "k_sweep_d4");
     else if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_fast");
     else if (kind == 1) snprintf(buf, sizeof(buf), "k_sweep_generic");

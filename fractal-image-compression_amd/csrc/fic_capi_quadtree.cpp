@@ -27,10 +27,16 @@ struct QtGreyHost : QtGrey {
         Ctx* c = cache_take(device, g.W, g.H, g.B, g.wK, g.n_iso);
         return c ? c : fic_ctx_create(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
     }
-    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb)   // exactly the one-shot encode of this level
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int search)   // exactly the one-shot encode of this level
     {
-        const int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
-        return rc ? rc : fic_ctx_encode(c, 0, -1, nullptr);
+        int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
+        if (rc || !search) return rc ? rc : fic_ctx_encode(c, 0, -1, nullptr);
+        // least squares: the cached context goes back in the reference's mode whatever happens
+        rc = fic_ctx_set_option(c, "search", search);
+        if (rc == FIC_OK) rc = fic_ctx_encode(c, 0, -1, nullptr);
+        ErrKeep keep;
+        (void)fic_ctx_set_option(c, "search", 0);
+        return rc;
     }
     static void give(Ctx* c, bool ok) { ok ? cache_give(c) : fic_ctx_destroy(c); }
     // every level reads the top context's scaled copy, made here: the original, 2:1 scaled (FC:970-1007)
@@ -49,7 +55,7 @@ struct QtRgbHost : QtRgb {
         Ctx* c = rgb_cache_take(device, g.W, g.H, g.B, g.wK);
         return c ? c : fic_rgb_ctx_create(device, g.W, g.H, g.B, g.wK, 1);
     }
-    static int encode(Ctx* c, const uint8_t*, const int32_t* argb)        // exactly the one-shot RGB encode of this level
+    static int encode(Ctx* c, const uint8_t*, const int32_t* argb, int = 0)   // exactly the one-shot RGB encode of this level
     {
         const int rc = fic_rgb_ctx_set_argb_host(c, argb);
         return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
@@ -77,7 +83,7 @@ struct QtRgbIsoHost : QtRgbIso {
         Ctx* c = rgb_cache_take(device, g.W, g.H, g.B, g.wK, g.n_iso);
         return c ? c : fic_rgb_ctx_create_iso(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
     }
-    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int = 0) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's
     static void give(Ctx* c, bool ok) { QtRgbHost::give(c, ok); }
     static int prepare(Ctx*) { return 0; }
     static QtViews<Px> views(const Ctx* c, const Ctx*)
@@ -99,11 +105,12 @@ struct QtBudget {
 
 // The encode behind fic_encode_*_quadtree_* and the SSE test hooks: every level through the one-shot contexts, then the
 // per-level SSE, the split and the compaction on the device.  leaves / sse_out may be NULL.  budget: NULL, or the threshold
-// comes from the budget's select instead of the argument.
+// comes from the budget's select instead of the argument.  search: the criterion of the per-level codebooks (grey only: 0 the
+// reference's, 1 least squares); everything after them is the same code.
 template <typename Fmt>
 int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
               int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity,
-              const QtBudget* budget = nullptr)
+              const QtBudget* budget = nullptr, int search = 0)
 {
     if (!gray && !argb) return fail(FIC_E_ARGUMENT, "%s encode: null image", Fmt::kStream.kind);
     if (threshold != threshold) return fail(FIC_E_ARGUMENT, "%s encode: threshold is NaN", Fmt::kStream.kind);
@@ -125,7 +132,7 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
         c[l] = Fmt::take(device, L.g[l]);
         if (!c[l]) { rc = g_err_code ? g_err_code : FIC_E_HIP; break; }
-        rc = Fmt::encode(c[l], gray, argb);
+        rc = Fmt::encode(c[l], gray, argb, search);
     }
     // scratch: SSE per level, counts / offsets per top-level block, the leaf table (room for every block of B_min)
     const FicGeom& top = L.g[0];
@@ -251,6 +258,20 @@ int fic_encode_gray_quadtree_argb(const int32_t* argb, int w, int h, int B_max, 
 {
     if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_gray_quadtree_argb: null argument");
     return qt_encode<QtGreyHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_encode_gray_quadtree_lsq_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                    int device, int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!gray || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_gray_quadtree_lsq_u8: null argument");
+    return qt_encode<QtGreyHost>(gray, nullptr, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0, nullptr, 1);
+}
+
+int fic_encode_gray_quadtree_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                      int device, int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_gray_quadtree_lsq_argb: null argument");
+    return qt_encode<QtGreyHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0, nullptr, 1);
 }
 
 int fic_encode_gray_quadtree_budget_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int64_t max_leaves,

@@ -138,6 +138,9 @@ struct fic_ctx {
     unsigned long long* q_stats = nullptr;   // "sweep_stats" = 1: device counters of k_sweep_q (fic_ctx_sweep_stats)
     uint32_t* d4_rng = nullptr;      // k_sweep_d4: range / domain slots of the group-Fourier form (n_iso = 8, B = 8 / 16)
     uint32_t* d4_pool = nullptr;
+    FicLsq lsq{};                    // least-squares search ("search" = 1): statistics, per-chunk slots, the winners' E (on first use)
+    size_t lsq_slots = 0;            // slots per plane the slot stores have room for
+    int opt_search = 0, last_search = 0;
     bool have_input = false;
     bool encoded_any = false;
     hipStream_t last_stream = nullptr;

@@ -170,6 +170,26 @@ int fic_launch_sweep_q(const FicBuffers& b, const void* poolQ, const void* dflat
                        void* theta_g, const FicGeom& g, int ct_begin, int ct_end, int ndtiles, int ndtiles_alloc,
                        int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s, unsigned long long* stats = nullptr, int dbg_noflag = 0,
                        const FicOutputs* fin_out = nullptr, unsigned int* fin_count = nullptr, int r_begin = 0, int r_count = 0);
+// least-squares domain search (fic_lsq.hip, option "search" = 1).  Its stores, beside FicBuffers:
+//   pool  : u32x4 [planes][Nd_pad]          {S_d, S_dd, V = n S_dd - S_d^2, bits of (float) sqrt((double) V)}
+//   rng   : u32x2 [planes][Nr_pad]          {S_r, S_rr}
+//   slotE : i64   [planes][nslots][Nr_pad]  smallest E of one (pool chunk, isometry group) of the sweep, and in
+//   slotC : u32   [planes][nslots][Nr_pad]  its candidate c = wloc * n_iso + k     (the generic sweep: one slot)
+//   E     : i64   [planes][Nr]              the winner's E (fic_ctx_get_lsq_error_host)
+struct FicLsq {
+    void* pool;
+    void* rng;
+    void* slotE;
+    uint32_t* slotC;
+    void* E;
+};
+int fic_lsq_slots(const FicGeom& g, int nchunks);   // slots of a fast sweep over nchunks pool chunks
+int fic_launch_lsq_stat(const FicBuffers& b, const FicLsq& q, const FicGeom& g, hipStream_t s);
+int fic_launch_sweep_lsq_generic(const FicBuffers& b, const FicLsq& q, const FicGeom& g, int r_begin, int r_count, hipStream_t s);
+int fic_launch_sweep_lsq_fast(const FicBuffers& b, const FicLsq& q, const FicGeom& g, int tile0, int ntiles, int chunk_len, int nchunks,
+                              hipStream_t s, unsigned long long* stats = nullptr);   // stats u64 [8]: "sweep_stats" counters or NULL
+int fic_launch_finalize_lsq(const FicBuffers& b, const FicOutputs& out, const FicLsq& q, int nslots, const FicGeom& g, int r_begin,
+                            int r_count, hipStream_t s);
 int fic_launch_decode_iteration_rgb(int32_t* scaled, int32_t* image, const int32_t* qrows5, FicDecodeState* state,
                                     uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s,
                                     const int32_t* iso = nullptr);   // iso [N_r]: an n_iso = 8 codebook of a context, NULL: identity

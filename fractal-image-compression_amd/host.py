@@ -112,7 +112,17 @@ class Encoder:
 
     # ---- compute ---------------------------------------------------------------------------
     def set_option(self, name, value):
+        """fic_ctx_set_option.  "search" also takes "reference" / "lsq" (least squares)."""
+        if name == "search":
+            value = capi.search_id(value)
         capi.check(capi.lib().fic_ctx_set_option(self._h, name.encode(), int(value)))
+
+    def lsq_error(self):
+        """int64 [planes, N_r]: E of the winners of the last encode under set_option("search", "lsq") -- 10^4 times the squared
+        error of the quantised map (fic_ctx_get_lsq_error_host)."""
+        E = np.zeros((self.planes, self.n_ranges), np.int64)
+        capi.check(capi.lib().fic_ctx_get_lsq_error_host(self._h, capi.ptr(E, C.c_int64)))
+        return E
 
     def encode(self, range_begin=0, range_count=-1, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle / torch stream, None = default)."""
@@ -251,10 +261,14 @@ def encode_rgb_per_channel(rgb, B, wK=None, n_iso=1, device=0, sweep=0):
     return {k: v.reshape((n, 3) + v.shape[1:]) for k, v in r.items()}
 
 
-def encode_gray(gray, B, wK=None, n_iso=1, device=0, sweep=0, chunks=0, q_shape=0):
-    """One grey image (uint8 [H,W]) -> result dict with [N_r] arrays (plane axis dropped)."""
+def encode_gray(gray, B, wK=None, n_iso=1, device=0, sweep=0, chunks=0, q_shape=0, search="reference"):
+    """One grey image (uint8 [H,W]) -> result dict with [N_r] arrays (plane axis dropped).  search="lsq": the least-squares
+    search (sweep 0 / 1 / 2), with the winners' errors as "E" (int64 [N_r])."""
     g = np.ascontiguousarray(gray, np.uint8)
     with Encoder(g.shape[1], g.shape[0], B, wK, n_iso, 1, device) as enc:
+        lsq = capi.search_id(search)
+        if lsq:
+            enc.set_option("search", lsq)
         if sweep:
             enc.set_option("sweep", sweep)
         if chunks:
@@ -265,6 +279,8 @@ def encode_gray(gray, B, wK=None, n_iso=1, device=0, sweep=0, chunks=0, q_shape=
         enc.encode()
         r = enc.results()
         out = {k: v[0] for k, v in r.items()}
+        if lsq:
+            out["E"] = enc.lsq_error()[0]
         out["wK"] = enc.wK
         return out
 

@@ -441,9 +441,45 @@ FIC_API int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int
  *                 values widen the prune threshold (more pairs evaluated exactly, same codebooks); positive values narrow it
  *                 below what the derivation in fic_q.hip allows and give WRONG codebooks (the tests show that they are caught).
  *                 Like "q_noflag", not for production use.  fic_rgb_ctx_set_option takes it too (matrix-core RGB sweep).
+ *   "search"      0 (default) the reference's criterion (getErrorVarianceCovariance), 1 the least-squares search described at
+ *                 fic_encode_gray_lsq_u8 below.  Under "search" = 1, "sweep" takes 0 (auto: k_sweep_lsq_generic for windows,
+ *                 k_sweep_lsq_fast for full search), 1 (generic) or 2 (fast, full search only); any other value is
+ *                 FIC_E_ARGUMENT, whichever of the two options is set last.  "chunks", range spans, batched planes,
+ *                 "time_sweep" and fic_ctx_last_kernel work as with "search" = 0, and so do fic_ctx_collage_host and
+ *                 fic_ctx_decode_host / fic_ctx_decode_zoom_host: a and b are the decoder's own values then.
  *   "chunks"      domain-pool chunks per range tile for the fast kernel (0 = auto)
  *   "time_sweep"  1: bracket every sweep launch with hipEvents on its stream */
 FIC_API int fic_ctx_set_option(fic_ctx* ctx, const char* name, int value);
+
+/* ---- least-squares domain search (an extension) ------------------------------------------------------
+ * The reference picks the domain block by rem^2 (1 - r^2) (getErrorVarianceCovariance, FractalCompression.java:655-687), clamps
+ * a afterwards and truncates (int)(a*100), (int) b in writeData.  This search minimises the squared error of the QUANTISED map
+ * the decoder will paint, in exact integers -- no float decides anything.  Same pool, same window, same 8 isometries, same
+ * streams and decoders; only the choice and the coefficients differ.  For range block r and candidate d = pool block g read
+ * through isometry k (n = B*B):
+ *   S_r = sum r, S_rr = sum r^2, S_d = sum d, S_dd = sum d^2, S_rd = sum r d_k;   C = n S_rd - S_r S_d,  V = n S_dd - S_d^2
+ *   qa = 0 if V == 0, else clamp(floor((200 C + V) / (2 V)), -100, 100)      (100 C / V to nearest, then the clamp; floor is
+ *                                                                             the mathematical one, also for negatives)
+ *   qb = floor((2 (100 S_r - qa S_d) + 100 n) / (200 n))                     (mean_r - qa mean_d / 100 to nearest, not clamped)
+ *   E  = sum (100 r - qa d - 100 qb)^2 = 10^4 S_rr + qa^2 S_dd + 10^4 n qb^2 - 200 qa S_rd - 2 10^4 qb S_r + 200 qa qb S_d
+ * (int64, >= 0: 10^4 times the squared error of the quantised map before the decoder's truncation and pixel clamp).  The winner
+ * is the smallest E; candidates in the order c = idx_local * n_iso + k, strict '<' (the first candidate wins a tie).  Outputs:
+ *   idx_local, iso   the winner;   qrows = {idx_local, qa, qb} as they are (no (int)(a*100) step)
+ *   a = (float) qa / 100f, b = (float) qb   (what decodeGreyScale makes of the row, :373);   err = (float)((double) E / 1e4)
+ *   E [planes][N_r]  fic_ctx_get_lsq_error_host after an encode with "search" = 1 (FIC_E_STATE otherwise)
+ * The one-shot entries take the arguments of fic_encode_gray_u8 / _argb plus E [N_r], which may be NULL, and run through the same
+ * cached contexts; a context goes back to the cache in the reference's mode.  The quadtree entries have the signature of
+ * fic_encode_gray_quadtree_u8 / _argb: the per-level codebooks come from this search, everything after them (leaf SSE, split,
+ * leaf table, tag-2 stream, decoder) is unchanged. */
+FIC_API int fic_ctx_get_lsq_error_host(fic_ctx* ctx, int64_t* E);
+FIC_API int fic_encode_gray_lsq_u8(const uint8_t* gray, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
+                                   float* a, float* b, int32_t* iso, int32_t* qrows, int64_t* E);
+FIC_API int fic_encode_gray_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
+                                     float* a, float* b, int32_t* iso, int32_t* qrows, int64_t* E);
+FIC_API int fic_encode_gray_quadtree_lsq_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                            int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+FIC_API int fic_encode_gray_quadtree_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                              float threshold, int device, int32_t* leaves, int64_t capacity, int* n_leaves);
 /* Sum of sweep-kernel durations (ms) and launch count since the last reset ("time_sweep" = 1).
  * Synchronises the events.  reset != 0 clears the accumulators afterwards. */
 FIC_API int fic_ctx_sweep_time(fic_ctx* ctx, double* total_ms, int* launches, int reset);
@@ -451,12 +487,14 @@ FIC_API int fic_ctx_sweep_time(fic_ctx* ctx, double* total_ms, int* launches, in
  * (32 range copies x 32 domain blocks each), out[1] tiles that had flagged pairs, out[2] pairs evaluated exactly,
  * out[3] waves; of a sample of the waves: out[4] shader-clock cycles and out[5] 100 MHz ticks they were alive (summed),
  * out[6] their number (out[4] / out[5] / 10 = the clock in GHz the chip held under this kernel); out[7] reserved.
+ * Under "search" = 1 the fast sweep k_sweep_lsq_fast counts instead: out[0] (wave, pool block) visits, out[1] visits that ran
+ * the exact epilogue (some lane had a pair the prune could not skip), out[2] pairs evaluated exactly, out[3] waves.
  * Synchronises the context's stream. */
 FIC_API int fic_ctx_sweep_stats(fic_ctx* ctx, uint64_t* out8, int reset);
 /* Geometry actually in use: out[0..9] = Rw, Rh, N_r, Dw, Dh, N_d, NR, tiles, chunks, sweep kind. */
 FIC_API int fic_ctx_info(fic_ctx* ctx, int* out10);
 /* Name of the sweep kernel the context's last encode launched (as rocprofv3 prints it, without the argument list), e.g.
- * "k_sweep_q<4, 2, false>" (one pool chunk), "k_sweep_q16<4, true>" (several) or "k_sweep_qs<4, 2>" / "k_sweep_q16s<4>" (several short
+ * "k_sweep_lsq_fast" / "k_sweep_lsq_generic" under "search" = 1, "k_sweep_q<4, 2, false>" (one pool chunk), "k_sweep_q16<4, true>" (several) or "k_sweep_qs<4, 2>" / "k_sweep_q16s<4>" (several short
  * ones: theta is shared between the chunks in the fast path) -- so that a caller can match its timing with a profile.  A small launch
  * of the default sweep (one image up to about 512x512 at B = 8) runs as two kernels instead of five -- k_prep_q8 (scale + pool +
  * range prep) and the sweep, whose last workgroup per range-column group also does k_finalize's work -- and the name then

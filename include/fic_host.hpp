@@ -145,6 +145,24 @@ public:
         return collage;
     }
 
+    // The one-shot least-squares search (an extension, fic_encode_gray_lsq_argb in fic.h): the rows {idx_local, qa, qb} of every
+    // range block into `qrows` [N_r * 3], ready for writeData, the winning isometries into `iso` [N_r] and the winners' errors
+    // E -- 10^4 times the squared error of the quantised map -- into `E` [N_r]; `iso` and `E` may be null.
+    static void encodeGrayScaleLsq(const RasterImage& input, std::vector<int32_t>& qrows, std::vector<int32_t>* iso = nullptr,
+                                   std::vector<int64_t>* E = nullptr)
+    {
+        int Rw = 0, Rh = 0;
+        check(fic_geometry(input.width, input.height, blockgroesse, &Rw, &Rh, nullptr, nullptr));
+        const int nr = Rw * Rh;
+        std::vector<int32_t> idx(nr);
+        std::vector<float> a(nr), b(nr);
+        qrows.resize((size_t)nr * 3);
+        if (iso) iso->resize(nr);
+        if (E) E->resize(nr);
+        check(fic_encode_gray_lsq_argb(input.argb.data(), input.width, input.height, blockgroesse, widthKernel, isometries, device,
+                                       idx.data(), a.data(), b.data(), iso ? iso->data() : nullptr, qrows.data(), E ? E->data() : nullptr));
+    }
+
     // FractalCompression.java:230-246 (grey branch): big-endian header + rows.
     static void writeData(std::ostream& out, const std::vector<int32_t>& qrows, int width, int height)
     {
