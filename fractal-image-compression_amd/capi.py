@@ -154,6 +154,7 @@ def lib():
         "fic_encode_gray_quadtree_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_encode_gray_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
+        "fic_debug_live_memory": (C.c_int, [C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -299,6 +300,17 @@ def encode_gray_multi(gray, B, wK, n_iso=1, n_gpus=1, width=None, height=None):
 def release_cache():
     lib().fic_release_cache.restype = None
     lib().fic_release_cache()
+
+
+LIVE_MEMORY_FIELDS = ("device_bytes", "device_allocations", "pinned_bytes", "pinned_allocations")
+
+
+def live_memory():
+    """What the library holds right now, process-wide (fic_debug_live_memory): a dict of LIVE_MEMORY_FIELDS, all 0 once every
+    context is closed and release_cache() has run."""
+    v = (C.c_int64 * 4)()
+    check(lib().fic_debug_live_memory(v))
+    return dict(zip(LIVE_MEMORY_FIELDS, [int(x) for x in v]))
 
 
 def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):

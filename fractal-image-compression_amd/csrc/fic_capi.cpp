@@ -15,27 +15,55 @@ int check_device(int device)
     return FIC_OK;
 }
 
+bool create_device_ok(int device)
+{
+    int ndev = fic_device_count();
+    if (ndev <= 0) { fail(FIC_E_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); return false; }
+    if (device < 0 || device >= ndev) { fail(FIC_E_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1); return false; }
+    if (hipSetDevice(device) != hipSuccess) { fail(FIC_E_HIP, "hipSetDevice(%d) failed", device); return false; }
+    return true;
+}
+
+int sweep_stats_option(DevMem& mem, unsigned long long*& stats, int on, hipStream_t last_stream)
+{
+    if (on && !stats) {
+        int rc = mem.ensure_zeroed(stats, 8, nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
+    } else if (!on && stats) {
+        HIP_TRY(hipStreamSynchronize(last_stream));
+        mem.release(stats);
+    }
+    return FIC_OK;
+}
+
+int sweep_stats_read(const char* who, unsigned long long* stats, int device, hipStream_t last_stream, uint64_t* out8, int reset)
+{
+    if (!stats) return fail(FIC_E_STATE, "%s: set the option \"sweep_stats\" first", who);
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(last_stream));
+    HIP_TRY(hipMemcpy(out8, stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reset) {
+        HIP_TRY(hipMemset(stats, 0, 8 * sizeof(uint64_t)));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return FIC_OK;
+}
+
+IdleCache<fic_ctx, 16> g_idle_grey;
+
 }  // namespace ficd
 
 using namespace ficd;
 
+fic_ctx::~fic_ctx()
+{
+    (void)hipSetDevice(device);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+}
 
 namespace {
-
-int ctx_free_all(fic_ctx* c)
-{
-    (void)hipSetDevice(c->device);
-    for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    c->ev.clear();
-    if (c->own_stream) { (void)hipStreamDestroy(c->own_stream); c->own_stream = nullptr; }
-    void* ptrs[] = {c->gray_own, c->argb_stage, c->collage, c->decoded, c->dec_state, c->dec_sq, c->mfma_poolB, c->mfma_rngA, c->mfma_sw, c->mfma_rconst, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, c->q_fin, c->q_stats, c->d4_rng, c->d4_pool, c->lsq.pool, c->lsq.rng, c->lsq.slotE, c->lsq.slotC, c->lsq.E, c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var,
-                    c->b.pool_s64, c->b.rng_pix, c->b.rng_st, c->b.key, c->o.idx_local, c->o.idx_global, c->o.iso,
-                    c->o.a, c->o.b, c->o.err, c->o.qrows, c->o.records};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->host_rec) { (void)hipHostFree(c->host_rec); c->host_rec = nullptr; }
-    return FIC_OK;
-}
 
 int flush_events(fic_ctx* c)
 {
@@ -51,44 +79,6 @@ int flush_events(fic_ctx* c)
     c->ev.clear();
     return FIC_OK;
 }
-
-// Idle single-plane contexts of the one-shot entry points, most recently used last.
-std::mutex g_cache_mu;
-std::vector<fic_ctx*> g_cache;
-constexpr size_t kCacheSlots = 16;   // the multi-device entry parks one context per device
-
-}  // namespace
-
-fic_ctx* ficd::cache_take(int device, int w, int h, int B, int wK, int n_iso)
-{
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    for (size_t i = g_cache.size(); i-- > 0;) {
-        fic_ctx* c = g_cache[i];
-        const FicGeom& g = c->g;
-        if (c->device == device && g.W == w && g.H == h && g.B == B && g.wK == wK && g.n_iso == n_iso && g.planes == 1) {
-            g_cache.erase(g_cache.begin() + (long)i);
-            return c;
-        }
-    }
-    return nullptr;
-}
-
-
-void ficd::cache_give(fic_ctx* c)
-{
-    fic_ctx* evict = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        g_cache.push_back(c);
-        if (g_cache.size() > kCacheSlots) {
-            evict = g_cache.front();
-            g_cache.erase(g_cache.begin());
-        }
-    }
-    if (evict) fic_ctx_destroy(evict);
-}
-
-namespace {
 
 // ---- sweep orchestration helpers (used by fic_ctx_encode) ------------------------------------------------------
 
@@ -162,8 +152,9 @@ int d4_prep(fic_ctx* c, hipStream_t s)
 {
     const FicGeom& g = c->g;
     const size_t NW = (size_t)fic_d4_words(g.B), P = (size_t)g.planes;
-    if (!c->d4_rng) HIP_TRY(hipMalloc((void**)&c->d4_rng, P * g.tiles * NW * 64 * 4));
-    if (!c->d4_pool) HIP_TRY(hipMalloc((void**)&c->d4_pool, P * g.Nd_pad * NW * 4));
+    int rc = c->mem.ensure(c->d4_rng, P * g.tiles * NW * 64);
+    if (rc == FIC_OK) rc = c->mem.ensure(c->d4_pool, P * g.Nd_pad * NW);
+    if (rc) return rc;
     if (fic_launch_d4_prep(c->b, c->d4_rng, c->d4_pool, g, s)) return fail(FIC_E_HIP, "k_range_d4 / k_pool_d4 launch failed");
     return FIC_OK;
 }
@@ -216,20 +207,20 @@ int matrix_core_prep(fic_ctx* c, int kind, hipStream_t s)
     const size_t P = (size_t)g.planes;
     if ((c->mfma_poolB || c->mfma_rngA || c->mfma_sw || c->mfma_rconst) && c->mfma_bf16 != (int)m.bf16) {     // operand type changed ("sweep" 3 <-> 4): new fragment stores
         HIP_TRY(hipStreamSynchronize(s));
-        void* old[] = {c->mfma_poolB, c->mfma_rngA, c->mfma_sw, c->mfma_rconst};
-        for (void* p : old) if (p) (void)hipFree(p);
-        c->mfma_poolB = c->mfma_rngA = c->mfma_sw = nullptr;
-        c->mfma_rconst = nullptr;
+        c->mem.release(c->mfma_poolB);
+        c->mem.release(c->mfma_rngA);
+        c->mem.release(c->mfma_sw);
+        c->mem.release(c->mfma_rconst);
     }
     {
-        // every store is guarded on its own pointer: a failed hipMalloc leaves the others usable and is retried next time
+        // every store is ensured on its own pointer: a failed allocation leaves the others usable and is retried next time
         c->mfma_bf16 = (int)m.bf16;
         const size_t rtiles = m.iso8 ? (size_t)m.ngroups8 * (m.G8 / 4) : (size_t)m.nctiles_alloc;   // 32-row/column range tiles
-        if (!c->mfma_poolB) HIP_TRY(hipMalloc(&c->mfma_poolB, P * m.ndtiles_alloc * m.steps * 64 * 16));
-        if (!c->mfma_rngA) HIP_TRY(hipMalloc(&c->mfma_rngA, P * rtiles * m.steps * 64 * 16));
-        if (!c->mfma_sw) HIP_TRY(hipMalloc(&c->mfma_sw, P * m.ndtiles_alloc * 32 * 8));
-        if (!m.bf16 && !c->mfma_rconst)
-            HIP_TRY(hipMalloc((void**)&c->mfma_rconst, m.iso8 ? P * rtiles * 16 * sizeof(int) : P * rtiles * 32 * 16));
+        int rc = c->mem.ensure(c->mfma_poolB, P * m.ndtiles_alloc * m.steps * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->mfma_rngA, P * rtiles * m.steps * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->mfma_sw, P * m.ndtiles_alloc * 32 * 8);
+        if (rc == FIC_OK && !m.bf16) rc = c->mem.ensure(c->mfma_rconst, m.iso8 ? P * rtiles * 16 : P * rtiles * 32 * 16 / sizeof(int));
+        if (rc) return rc;
     }
     if (m.bf16) {
         const int rtiles = m.iso8 ? m.ngroups8 * (m.G8 / 4) : m.nctiles_alloc;
@@ -317,16 +308,16 @@ int q_prep(fic_ctx* c, int tile0, int tile1, hipStream_t s)
     const FicGeom& g = c->g;
     const QShape q = q_shape(g);
     const size_t P = (size_t)g.planes, NK = (size_t)g.n / 16;
-    if (!c->q_pool) HIP_TRY(hipMalloc(&c->q_pool, P * q.ndtiles_alloc * NK * 64 * 16));
-    if (!c->q_flat) HIP_TRY(hipMalloc(&c->q_flat, P * q.ndtiles_alloc * sizeof(uint32_t)));
-    if (!c->q_rng) {                                   // zeroed once: column tiles past the last range group stay zero fragments
-        HIP_TRY(hipMalloc(&c->q_rng, P * q.nct_alloc * NK * 64 * 16));
-        HIP_TRY(hipMemsetAsync(c->q_rng, 0, P * q.nct_alloc * NK * 64 * 16, s));
-    }
-    if (!c->q_rngC) HIP_TRY(hipMalloc(&c->q_rngC, P * g.Nr_pad * fic_q_cols_per_range(g.B, g.n_iso) * g.n));
-    if (!c->q_E) HIP_TRY(hipMalloc(&c->q_E, P * g.Nr_pad * sizeof(float)));
+    DevMem& m = c->mem;
+    int rc = m.ensure(c->q_pool, P * q.ndtiles_alloc * NK * 64 * 16);
+    if (rc == FIC_OK) rc = m.ensure(c->q_flat, P * q.ndtiles_alloc * sizeof(uint32_t));
+    // zeroed once: column tiles past the last range group stay zero fragments
+    if (rc == FIC_OK) rc = m.ensure_zeroed(c->q_rng, P * q.nct_alloc * NK * 64 * 16, s);
+    if (rc == FIC_OK) rc = m.ensure(c->q_rngC, P * g.Nr_pad * fic_q_cols_per_range(g.B, g.n_iso) * g.n);
+    if (rc == FIC_OK) rc = m.ensure(c->q_E, P * g.Nr_pad * sizeof(float));
     // (+ the padded column tiles behind the last plane: the sweep's fast path reads theta_g of every column it owns)
-    if (!c->q_thg) HIP_TRY(hipMalloc(&c->q_thg, (P * g.Nr_pad + (size_t)2 * q.CT * 32 + 64) * sizeof(uint32_t)));
+    if (rc == FIC_OK) rc = m.ensure(c->q_thg, (P * g.Nr_pad + (size_t)2 * q.CT * 32 + 64) * sizeof(uint32_t));
+    if (rc) return rc;
     const int tsz = 64 * g.NR;
     const int grp0 = tile0 * tsz / 64, grp1 = tile1 * tsz / 64;      // 64-range groups covering the span
     if (fic_launch_q_prep(c->b, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, g, q.ndtiles_alloc, q.nct_alloc, grp0, grp1 - grp0, s))
@@ -368,10 +359,9 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
     int tiles_per_chunk = (q.ndtiles + nchunks - 1) / nchunks;
     tiles_per_chunk = (tiles_per_chunk + q.unroll - 1) / q.unroll * q.unroll;     // whole iterations of the unrolled sweep loop
     nchunks = (q.ndtiles + tiles_per_chunk - 1) / tiles_per_chunk;
-    if (fused_fin && !c->q_fin) {                      // one counter per (plane, column group); the sweep leaves them at zero
-        const size_t nfin = (size_t)g.planes * (q.nct_alloc / q.CT + 1);
-        HIP_TRY(hipMalloc((void**)&c->q_fin, nfin * sizeof(unsigned int)));
-        HIP_TRY(hipMemsetAsync(c->q_fin, 0, nfin * sizeof(unsigned int), s));
+    if (fused_fin) {                                   // one counter per (plane, column group); the sweep leaves them at zero
+        const int rc = c->mem.ensure_zeroed(c->q_fin, (size_t)g.planes * (q.nct_alloc / q.CT + 1), s);
+        if (rc) return rc;
     }
     if (fic_launch_sweep_q(c->b, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, g, ct_begin, ct_end, q.ndtiles, q.ndtiles_alloc,
                            q.nct_alloc, tiles_per_chunk, nchunks, s, c->q_stats, c->opt_noflag, fused_fin ? &c->o : nullptr, c->q_fin,
@@ -407,33 +397,28 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
         nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
         nslots = fic_lsq_slots(g, nchunks);
     }
-    if (!c->lsq.pool) {
-        HIP_TRY(hipMalloc(&c->lsq.pool, P * g.Nd_pad * 16));
-        HIP_TRY(hipMemsetAsync(c->lsq.pool, 0, P * g.Nd_pad * 16, s));    // the tail the prefetch over-reads
-    }
-    if (!c->lsq.rng) HIP_TRY(hipMalloc(&c->lsq.rng, P * g.Nr_pad * 8));
-    if (!c->lsq.E) HIP_TRY(hipMalloc(&c->lsq.E, P * g.Nr * 8));
+    int rc = c->mem.ensure_zeroed(c->lsq.pool, P * g.Nd_pad * 16, s);      // the tail the prefetch over-reads
+    if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.rng, P * g.Nr_pad * 8);
+    if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.E, P * g.Nr * 8);
+    if (rc) return rc;
     if (c->lsq_slots < (size_t)nslots) {
         HIP_TRY(hipStreamSynchronize(c->last_stream));
-        if (c->lsq.slotE) (void)hipFree(c->lsq.slotE);
-        if (c->lsq.slotC) (void)hipFree(c->lsq.slotC);
-        c->lsq.slotE = nullptr;
-        c->lsq.slotC = nullptr;
+        c->mem.release(c->lsq.slotE);
+        c->mem.release(c->lsq.slotC);
         c->lsq_slots = 0;
-        HIP_TRY(hipMalloc(&c->lsq.slotE, P * nslots * g.Nr_pad * 8));
-        HIP_TRY(hipMalloc((void**)&c->lsq.slotC, P * nslots * g.Nr_pad * 4));
+        rc = c->mem.ensure(c->lsq.slotE, P * nslots * g.Nr_pad * 8);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.slotC, P * nslots * g.Nr_pad);
+        if (rc) return rc;
         c->lsq_slots = (size_t)nslots;
     }
     if (fic_launch_scale(c->b.gray, c->b.scaled, g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
     if (fic_launch_pool(c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var, c->b.pool_s64, g, s))
         return fail(FIC_E_HIP, "k_pool launch failed");
-    if (!c->b.rng_pix) {
-        int rca = dev_alloc(&c->b.rng_pix, P * g.Nr_pad * g.n_iso * g.DW);
-        if (rca) return rca;
-    }
+    rc = c->mem.ensure(c->b.rng_pix, P * g.Nr_pad * g.n_iso * g.DW);
+    if (rc) return rc;
     if (fic_launch_range(c->b.gray, c->b.rng_pix, c->b.rng_st, g, s, 1)) return fail(FIC_E_HIP, "k_range launch failed");
     if (fic_launch_lsq_stat(c->b, c->lsq, g, s)) return fail(FIC_E_HIP, "k_lsq_stat launch failed");
-    int rc = time_begin(c, s);
+    rc = time_begin(c, s);
     if (rc) return rc;
     if (kind == 1) {
         if (fic_launch_sweep_lsq_generic(c->b, c->lsq, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_sweep_lsq_generic launch failed");
@@ -495,33 +480,32 @@ fic_ctx* fic_ctx_create(int device, int w, int h, int B, int wK, int n_iso, int 
 {
     FicGeom g;
     if (make_geometry(w, h, B, wK, n_iso, planes, &g)) return nullptr;
-    int ndev = fic_device_count();
-    if (ndev <= 0) { fail(FIC_E_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); return nullptr; }
-    if (device < 0 || device >= ndev) { fail(FIC_E_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { fail(FIC_E_HIP, "hipSetDevice(%d) failed", device); return nullptr; }
+    if (!create_device_ok(device)) return nullptr;
     fic_ctx* c = new fic_ctx();
     c->device = device;
+    c->mem.set_device(device);
     c->g = g;
     memset(&c->b, 0, sizeof(c->b));
     memset(&c->o, 0, sizeof(c->o));
     const size_t P = (size_t)planes;
+    DevMem& m = c->mem;
     int rc = FIC_OK;
     auto A = [&](int r) { if (rc == FIC_OK) rc = r; };
-    A(dev_alloc(&c->b.scaled, P * g.Ws * g.Hs));
-    A(dev_alloc(&c->b.pool_pix, P * g.Nd_pad * g.n));
-    A(dev_alloc(&c->b.pool_st, P * g.Nd_pad));
-    A(dev_alloc(&c->b.pool_var, P * g.Nd_pad));
-    A(dev_alloc(&c->b.pool_s64, P * g.Nd_pad));
-    A(dev_alloc(&c->b.rng_st, P * g.Nr_pad));
-    A(dev_alloc(&c->b.key, P * g.Nr_pad));
-    A(dev_alloc(&c->o.idx_local, P * g.Nr));
-    A(dev_alloc(&c->o.idx_global, P * g.Nr));
-    A(dev_alloc(&c->o.iso, P * g.Nr));
-    A(dev_alloc(&c->o.a, P * g.Nr));
-    A(dev_alloc(&c->o.b, P * g.Nr));
-    A(dev_alloc(&c->o.err, P * g.Nr));
-    A(dev_alloc(&c->o.qrows, P * g.Nr * 3));
-    A(dev_alloc(&c->o.records, P * g.Nr * 6));
+    A(m.alloc(c->b.scaled, P * g.Ws * g.Hs));
+    A(m.alloc(c->b.pool_pix, P * g.Nd_pad * g.n));
+    A(m.alloc(c->b.pool_st, P * g.Nd_pad));
+    A(m.alloc(c->b.pool_var, P * g.Nd_pad));
+    A(m.alloc(c->b.pool_s64, P * g.Nd_pad));
+    A(m.alloc(c->b.rng_st, P * g.Nr_pad));
+    A(m.alloc(c->b.key, P * g.Nr_pad));
+    A(m.alloc(c->o.idx_local, P * g.Nr));
+    A(m.alloc(c->o.idx_global, P * g.Nr));
+    A(m.alloc(c->o.iso, P * g.Nr));
+    A(m.alloc(c->o.a, P * g.Nr));
+    A(m.alloc(c->o.b, P * g.Nr));
+    A(m.alloc(c->o.err, P * g.Nr));
+    A(m.alloc(c->o.qrows, P * g.Nr * 3));
+    A(m.alloc(c->o.records, P * g.Nr * 6));
     if (rc == FIC_OK) {
         // zero the pool once: the FIC_POOL_PAD tail blocks stay zero forever (prefetch over-read)
         hipError_t e = hipMemset(c->b.pool_pix, 0, P * g.Nd_pad * g.n);
@@ -535,7 +519,6 @@ fic_ctx* fic_ctx_create(int device, int w, int h, int B, int wK, int n_iso, int 
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "hipMemset: %s", hipGetErrorString(e));
     }
     if (rc != FIC_OK) {
-        ctx_free_all(c);
         delete c;
         return nullptr;
     }
@@ -547,7 +530,6 @@ void fic_ctx_destroy(fic_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    ctx_free_all(c);
     delete c;
 }
 
@@ -557,7 +539,7 @@ int fic_ctx_set_gray_host(fic_ctx* c, const uint8_t* gray)
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     size_t bytes = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (!c->gray_own) { int rc = dev_alloc(&c->gray_own, bytes); if (rc) return rc; }
+    if (int rc = c->mem.ensure(c->gray_own, bytes)) return rc;
     HIP_TRY(hipStreamSynchronize(c->last_stream));   // a previous encode on a non-blocking stream may still read gray_own
     HIP_TRY(hipMemcpy(c->gray_own, gray, bytes, hipMemcpyHostToDevice));
     c->b.gray = c->gray_own;
@@ -571,8 +553,8 @@ int fic_ctx_set_argb_host(fic_ctx* c, const int32_t* argb)
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (!c->gray_own) { int rc = dev_alloc(&c->gray_own, npix); if (rc) return rc; }
-    if (!c->argb_stage) { int rc = dev_alloc(&c->argb_stage, npix); if (rc) return rc; }
+    if (int rc = c->mem.ensure(c->gray_own, npix)) return rc;
+    if (int rc = c->mem.ensure(c->argb_stage, npix)) return rc;
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipMemcpy(c->argb_stage, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
     if (fic_launch_argb_to_gray(c->argb_stage, c->gray_own, npix, nullptr)) return fail(FIC_E_HIP, "k_argb_to_gray launch failed");
@@ -654,8 +636,8 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
             return fail(FIC_E_HIP, "k_pool launch failed");
         // the lane-transposed store of range blocks + isometry copies: only these sweeps read it (134 MB at 4096x4096 with
         // 8 isometries), so it is allocated on their first use, not with the context
-        if (kind != 5 && !c->b.rng_pix) {
-            int rca = dev_alloc(&c->b.rng_pix, (size_t)g.planes * g.Nr_pad * g.n_iso * g.DW);
+        if (kind != 5) {
+            const int rca = c->mem.ensure(c->b.rng_pix, (size_t)g.planes * g.Nr_pad * g.n_iso * g.DW);
             if (rca) return rca;
         }
         // k_sweep_d4 reads its own slot store and the finaliser reads the image: no isometry copies to build then
@@ -721,7 +703,7 @@ int fic_ctx_get_results_host(fic_ctx* c, int32_t* idx_local, float* a, float* b,
         if (qrows) HIP_TRY(hipMemcpy(qrows, c->o.qrows, n * 12, hipMemcpyDeviceToHost));
     } else if (idx_local || a || b || iso || qrows) {
         std::lock_guard<std::mutex> lk(c->mu);
-        if (!c->host_rec) HIP_TRY(hipHostMalloc((void**)&c->host_rec, n * 6 * sizeof(int32_t), hipHostMallocDefault));
+        if (int rc = c->mem.ensure(c->host_rec, n * 6, kMemPinned)) return rc;
         HIP_TRY(hipMemcpy(c->host_rec, c->o.records, n * 6 * sizeof(int32_t), hipMemcpyDeviceToHost));
         const int32_t* r = c->host_rec;
         for (size_t i = 0; i < n; i++, r += 6) {
@@ -765,7 +747,7 @@ int fic_ctx_collage_host(fic_ctx* c, int32_t* argb_out)
     if (!c->encoded_any) return fail(FIC_E_STATE, "fic_ctx_collage_host: nothing encoded yet");
     HIP_TRY(hipSetDevice(c->device));
     size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (!c->collage) { int rc = dev_alloc(&c->collage, npix); if (rc) return rc; }
+    if (int rc = c->mem.ensure(c->collage, npix)) return rc;
     if (fic_launch_collage(c->b, c->o, c->collage, c->g, c->last_stream)) return fail(FIC_E_HIP, "k_collage launch failed");
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipMemcpy(argb_out, c->collage, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -801,15 +783,7 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
         c->opt_time = value ? 1 : 0;
     } else if (!strcmp(name, "sweep_stats")) {
         HIP_TRY(hipSetDevice(c->device));
-        if (value && !c->q_stats) {
-            HIP_TRY(hipMalloc((void**)&c->q_stats, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipMemset(c->q_stats, 0, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
-        } else if (!value && c->q_stats) {
-            HIP_TRY(hipStreamSynchronize(c->last_stream));
-            (void)hipFree(c->q_stats);
-            c->q_stats = nullptr;
-        }
+        return sweep_stats_option(c->mem, c->q_stats, value, c->last_stream);
     } else {
         return fail(FIC_E_ARGUMENT, "unknown option '%s'", name);
     }
@@ -833,15 +807,7 @@ int fic_ctx_sweep_stats(fic_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_ctx_sweep_stats: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->q_stats) return fail(FIC_E_STATE, "fic_ctx_sweep_stats: set the option \"sweep_stats\" first");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out8, c->q_stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) {
-        HIP_TRY(hipMemset(c->q_stats, 0, 8 * sizeof(uint64_t)));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-    }
-    return FIC_OK;
+    return sweep_stats_read("fic_ctx_sweep_stats", c->q_stats, c->device, c->last_stream, out8, reset);
 }
 
 int fic_ctx_info(fic_ctx* c, int* out10)
@@ -895,15 +861,14 @@ int fic_debug_sqrt_f64(int device, uint32_t first, uint32_t count, double* out)
     if (!out || count == 0) return fail(FIC_E_ARGUMENT, "fic_debug_sqrt_f64: bad argument");
     int rc = check_device(device);
     if (rc) return rc;
+    DevMem scratch(device);
     double* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, (size_t)count * sizeof(double)));
-    if (fic_launch_sqrt_probe(d, first, count, nullptr)) rc = fail(FIC_E_HIP, "k_sqrt_probe launch failed");
-    if (rc == FIC_OK) {
-        hipError_t e = hipMemcpy(out, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(FIC_E_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return rc;
+    rc = scratch.alloc(d, count);
+    if (rc) return rc;
+    if (fic_launch_sqrt_probe(d, first, count, nullptr)) return fail(FIC_E_HIP, "k_sqrt_probe launch failed");
+    const hipError_t e = hipMemcpy(out, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "hipMemcpy: %s", hipGetErrorString(e));
+    return FIC_OK;
 }
 
 int fic_ctx_debug_pool_host(fic_ctx* c, uint8_t* pix, uint32_t* sum, uint32_t* var, uint8_t* scaled)
@@ -935,20 +900,10 @@ int fic_ctx_debug_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int
 {
     if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: null argument");
     if (!c->encoded_any || !c->q_pool) return fail(FIC_E_STATE, "fic_ctx_debug_q_host: no encode through the default sweep (\"sweep\" = 6) yet");
-    const FicGeom& g = c->g;
-    const QShape q = q_shape(g);
-    const size_t P = (size_t)g.planes, NK = (size_t)g.n / 16;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    switch (which) {                                   // the stores exactly as q_prep allocates them
-    case 0: src = c->q_pool; bytes = P * q.ndtiles_alloc * NK * 64 * 16; break;
-    case 1: src = c->q_flat; bytes = P * q.ndtiles_alloc * sizeof(uint32_t); break;
-    case 2: src = c->q_rng; bytes = P * q.nct_alloc * NK * 64 * 16; break;
-    case 3: src = c->q_E; bytes = P * g.Nr_pad * sizeof(float); break;
-    case 4: src = c->b.rng_st; bytes = P * g.Nr_pad * sizeof(FicRngStat); break;
-    case 5: src = c->q_rngC; bytes = P * g.Nr_pad * fic_q_cols_per_range(g.B, g.n_iso) * g.n; break;
-    default: return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: which must be 0..5");
-    }
+    if (which < 0 || which > 5) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: which must be 0..5");
+    const void* const stores[6] = {c->q_pool, c->q_flat, c->q_rng, c->q_E, c->b.rng_st, c->q_rngC};
+    const void* src = stores[which];
+    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
     *size = (int64_t)bytes;
     if (!out) return FIC_OK;
     if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_q_host: %zu bytes needed", bytes);
@@ -965,15 +920,15 @@ int ficd::encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h,
 {
     if ((!gray && !argb) || !idx_local || !a || !b) return fail(FIC_E_ARGUMENT, "fic_encode_gray: null argument");
     // The GUI calls encode once per slider move with the same geometry (CTL:125-145): keep the last few
-    // working sets instead of paying ~18 hipMalloc/hipFree per call.
-    fic_ctx* c = cache_take(device, w, h, B, wK, n_iso);
+    // working sets instead of paying ~18 device allocations and frees per call.
+    fic_ctx* c = g_idle_grey.take(device, w, h, B, wK, n_iso);
     if (!c) c = fic_ctx_create(device, w, h, B, wK, n_iso, 1);
     if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_ctx_create recorded why
     int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
     if (rc == FIC_OK) rc = fic_ctx_encode(c, 0, -1, nullptr);
     if (rc == FIC_OK) rc = fic_ctx_get_results_host(c, idx_local, a, b, iso, qrows, nullptr, nullptr);
     ErrKeep keep;
-    if (rc == FIC_OK) cache_give(c);
+    if (rc == FIC_OK) g_idle_grey.give(c);
     else fic_ctx_destroy(c);
     return rc;
 }
@@ -982,13 +937,8 @@ extern "C" {
 
 void fic_release_cache(void)
 {
-    std::vector<fic_ctx*> drop;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        drop.swap(g_cache);
-    }
-    for (fic_ctx* c : drop) fic_ctx_destroy(c);
-    release_rgb_cache();
+    g_idle_grey.drain();
+    g_idle_rgb.drain();
     release_comms();
     release_decoder_arenas();
 }

@@ -9,7 +9,7 @@ using namespace ficd;
 // ---- decoder (decodeGreyScale FC:356-421) ------------------------------------------------------
 namespace {
 // Device arenas of the decode jobs (struct Arena, fic_internal.h), kept between calls (the GUI decodes after every
-// encode, CTL:178-179): one allocation per (device, size class) instead of four hipMalloc/hipFree per call.
+// encode, CTL:178-179): one allocation per (device, size class) instead of four allocations and frees per call.
 // fic_release_cache() frees them.
 std::mutex g_arena_mu;
 std::vector<Arena> g_arenas;
@@ -28,8 +28,13 @@ int arena_take(int device, size_t bytes, Arena* out)
     }
     out->device = device;
     out->bytes = bytes;
-    HIP_TRY(hipMalloc((void**)&out->base, bytes));
-    return FIC_OK;
+    return mem_alloc(kMemDevice, (void**)&out->base, bytes);
+}
+// an arena is its own (pointer, bytes) record: it goes back to the counted pair directly
+void arena_free(const Arena& a)
+{
+    (void)hipSetDevice(a.device);
+    mem_free(kMemDevice, a.base, a.bytes);
 }
 void arena_give(const Arena& a)
 {
@@ -41,8 +46,7 @@ void arena_give(const Arena& a)
         evict = g_arenas.front();
         g_arenas.erase(g_arenas.begin());
     }
-    (void)hipSetDevice(evict.device);
-    (void)hipFree(evict.base);
+    arena_free(evict);
 }
 
 }  // namespace
@@ -54,7 +58,7 @@ void ficd::release_decoder_arenas()
         std::lock_guard<std::mutex> lk(g_arena_mu);
         drop.swap(g_arenas);
     }
-    for (const Arena& a : drop) { (void)hipSetDevice(a.device); (void)hipFree(a.base); }
+    for (const Arena& a : drop) arena_free(a);
 }
 
 static thread_local int g_last_sum_fallbacks = 0;
@@ -215,9 +219,9 @@ int fic_ctx_decode_zoom_host(fic_ctx* c, int zoom, uint8_t* gray_out, float* avg
         HIP_TRY(hipSetDevice(c->device));
         const FicGeom& g = c->g;
         const size_t P = (size_t)g.planes, npix = (size_t)g.W * g.H;
-        if (!c->decoded) { int rc = dev_alloc(&c->decoded, P * npix); if (rc) return rc; }
-        if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, P); if (rc) return rc; }
-        if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(P, npix)); if (rc) return rc; }
+        if (int rc = c->mem.ensure(c->decoded, P * npix)) return rc;
+        if (int rc = c->mem.ensure(c->dec_state, P)) return rc;
+        if (int rc = c->mem.ensure(c->dec_sq, fic_decode_sq_words(P, npix))) return rc;
         J.borrow(kDecodeGrey, g, c->last_stream, c->b.scaled, c->decoded, c->dec_state, c->dec_sq);
     }
     HIP_TRY(hipStreamSynchronize(c->last_stream));
@@ -248,26 +252,23 @@ int fic_debug_float_sum(int device, float carry, const uint32_t* vals, int count
     if (!vals || !out || count < 0) return fail(FIC_E_ARGUMENT, "fic_debug_float_sum: bad argument");
     int rc = check_device(device);
     if (rc) return rc;
+    DevMem scratch(device);
     uint32_t* d = nullptr;
     float* r = nullptr;
     uint32_t* maps = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, (size_t)(count + 4) * 4));
-    hipError_t e = hipMalloc((void**)&r, 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&maps, (fic_float_sum_map_words((size_t)count) + 4) * 4);
-    if (e == hipSuccess) e = hipMemcpy(d, vals, (size_t)count * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
-    if (rc == FIC_OK && fic_launch_float_sum_probe(carry, d, count, maps, r, nullptr)) rc = fail(FIC_E_HIP, "k_float_sum_probe launch failed");
-    if (rc == FIC_OK) {
-        float two[2] = {0.0f, 0.0f};
-        e = hipMemcpy(two, r, 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
-        out[0] = two[0];
-        g_last_sum_fallbacks = (int)two[1];
-    }
-    (void)hipFree(d);
-    if (r) (void)hipFree(r);
-    if (maps) (void)hipFree(maps);
-    return rc;
+    rc = scratch.alloc(d, (size_t)count + 4);
+    if (rc == FIC_OK) rc = scratch.alloc(r, 2);
+    if (rc == FIC_OK) rc = scratch.alloc(maps, fic_float_sum_map_words((size_t)count) + 4);
+    if (rc) return rc;
+    hipError_t e = hipMemcpy(d, vals, (size_t)count * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
+    if (fic_launch_float_sum_probe(carry, d, count, maps, r, nullptr)) return fail(FIC_E_HIP, "k_float_sum_probe launch failed");
+    float two[2] = {0.0f, 0.0f};
+    e = hipMemcpy(two, r, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_float_sum: %s", hipGetErrorString(e));
+    out[0] = two[0];
+    g_last_sum_fallbacks = (int)two[1];
+    return FIC_OK;
 }
 
 // Test hook: segments of the last fic_debug_float_sum on this thread that went through the sequential-order path.

@@ -11,7 +11,7 @@ int lsq_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, i
                 float* a, float* b, int32_t* iso, int32_t* qrows, int64_t* E)
 {
     if ((!gray && !argb) || !idx_local || !a || !b) return fail(FIC_E_ARGUMENT, "fic_encode_gray_lsq: null argument");
-    fic_ctx* c = cache_take(device, w, h, B, wK, n_iso);
+    fic_ctx* c = g_idle_grey.take(device, w, h, B, wK, n_iso);
     if (!c) c = fic_ctx_create(device, w, h, B, wK, n_iso, 1);
     if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_ctx_create recorded why
     int rc = fic_ctx_set_option(c, "search", 1);
@@ -21,7 +21,7 @@ int lsq_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, i
     if (rc == FIC_OK && E) rc = fic_ctx_get_lsq_error_host(c, E);
     ErrKeep keep;
     // the cached contexts serve the reference entries too: never parked in least-squares mode
-    if (rc == FIC_OK && fic_ctx_set_option(c, "search", 0) == FIC_OK) cache_give(c);
+    if (rc == FIC_OK && fic_ctx_set_option(c, "search", 0) == FIC_OK) g_idle_grey.give(c);
     else fic_ctx_destroy(c);
     return rc;
 }

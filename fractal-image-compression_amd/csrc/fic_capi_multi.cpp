@@ -139,13 +139,19 @@ int gather_rccl(const std::vector<fic_ctx*>& ctx, const std::vector<int>& begin,
 // pinned host staging of the grey image for the per-device uploads (grown on demand, freed by fic_release_cache)
 uint8_t* g_stage = nullptr;
 size_t g_stage_cap = 0;
+void stage_drop()
+{
+    mem_free(kMemPinnedPortable, g_stage, g_stage_cap);
+    g_stage = nullptr;
+    g_stage_cap = 0;
+}
 int stage_reserve(size_t bytes)
 {
     if (bytes <= g_stage_cap) return FIC_OK;
-    if (g_stage) { (void)hipHostFree(g_stage); g_stage = nullptr; g_stage_cap = 0; }
-    HIP_TRY(hipHostMalloc((void**)&g_stage, bytes, hipHostMallocPortable));
-    g_stage_cap = bytes;
-    return FIC_OK;
+    stage_drop();
+    const int rc = mem_alloc(kMemPinnedPortable, (void**)&g_stage, bytes);
+    if (rc == FIC_OK) g_stage_cap = bytes;
+    return rc;
 }
 
 // the same gather as plain device copies: logical shards that share a physical device (FIC_FAKE_DEVICES, a test knob --
@@ -199,7 +205,7 @@ int encode_multi(const uint8_t* gray, const int32_t* argb, int w, int h, int B, 
     auto drop = [&](bool keep) {
         ErrKeep keep_err;
         for (fic_ctx* c : ctx)
-            if (c) { if (keep) cache_give(c); else fic_ctx_destroy(c); }
+            if (c) { if (keep) g_idle_grey.give(c); else fic_ctx_destroy(c); }
     };
     // The image goes to every device (each builds its own pool replica: cheaper than shipping the 16x-expanded pool).  ONE
     // pinned staging copy of the grey bytes (the R channel of ARGB input, FC:596/977), then one hipMemcpyAsync per device on
@@ -212,13 +218,13 @@ int encode_multi(const uint8_t* gray, const int32_t* argb, int w, int h, int B, 
     }
     for (int i = 0; i < n_gpus && rc == FIC_OK; i++) {
         const int dev = i % ndev;
-        ctx[i] = cache_take(dev, w, h, B, wK, n_iso);
+        ctx[i] = g_idle_grey.take(dev, w, h, B, wK, n_iso);
         if (!ctx[i]) ctx[i] = fic_ctx_create(dev, w, h, B, wK, n_iso, 1);
         if (!ctx[i]) { rc = g_err_code ? g_err_code : FIC_E_HIP; break; }
         fic_ctx* c = ctx[i];
         hipError_t e = hipSetDevice(dev);
         if (e == hipSuccess && !c->own_stream) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-        if (e == hipSuccess && !c->gray_own) e = hipMalloc((void**)&c->gray_own, npix);
+        if (e == hipSuccess && c->mem.ensure(c->gray_own, npix)) { rc = fail(FIC_E_HIP, "image upload to device %d: %s", dev, g_mem_why); break; }
         if (e == hipSuccess && c->last_stream != c->own_stream) e = hipStreamSynchronize(c->last_stream);   // a parked context last used elsewhere
         if (e == hipSuccess) e = hipMemcpyAsync(c->gray_own, g_stage, npix, hipMemcpyHostToDevice, c->own_stream);
         if (e != hipSuccess) { rc = fail(FIC_E_HIP, "image upload to device %d: %s", dev, hipGetErrorString(e)); break; }
@@ -289,13 +295,15 @@ int fic_debug_rccl_selftest(int n_signed)
     for (int i = 0; i < n; i++) devs[i] = i;
     int rc = rccl_comms(devs);
     if (rc) return rc;
+    std::vector<DevMem> own(n);          // one owner per device: the buffers go when the call returns, after the streams below
     std::vector<int32_t*> buf(n, nullptr);
     std::vector<hipStream_t> st(n, nullptr);
     const size_t cnt = 6 * 1000;
     hipError_t e = hipSuccess;
-    for (int i = 0; i < n && e == hipSuccess; i++) {
+    for (int i = 0; i < n && e == hipSuccess && rc == FIC_OK; i++) {
+        own[i].set_device(i);
         e = hipSetDevice(i);
-        if (e == hipSuccess) e = hipMalloc((void**)&buf[i], cnt * n * 4);
+        if (e == hipSuccess && own[i].alloc(buf[i], cnt * n)) { rc = fail(FIC_E_HIP, "rccl selftest setup: %s", g_mem_why); break; }
         if (e == hipSuccess) e = hipMemset(buf[i], i + 1, cnt * n * 4);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);       // the fill is only enqueued; the sends run on non-blocking streams
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking);
@@ -340,7 +348,6 @@ int fic_debug_rccl_selftest(int n_signed)
         for (int i = 0; i < n; i++) {
             (void)hipSetDevice(i);
             if (st[i]) { (void)hipStreamSynchronize(st[i]); (void)hipStreamDestroy(st[i]); }
-            if (buf[i]) (void)hipFree(buf[i]);
         }
     }
     return rc;
@@ -369,5 +376,5 @@ void ficd::release_comms()
 {
     std::lock_guard<std::mutex> lk(g_multi_mu);
     if (g_rccl.lib) rccl_drop_comms();
-    if (g_stage) { (void)hipHostFree(g_stage); g_stage = nullptr; g_stage_cap = 0; }
+    stage_drop();
 }

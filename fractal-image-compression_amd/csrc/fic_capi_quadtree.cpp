@@ -24,7 +24,7 @@ struct QtGreyHost : QtGrey {
     static constexpr const DecodeKind& kDecode = kDecodeGrey;
     static Ctx* take(int device, const FicGeom& g)
     {
-        Ctx* c = cache_take(device, g.W, g.H, g.B, g.wK, g.n_iso);
+        Ctx* c = g_idle_grey.take(device, g.W, g.H, g.B, g.wK, g.n_iso);
         return c ? c : fic_ctx_create(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
     }
     static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int search)   // exactly the one-shot encode of this level
@@ -38,7 +38,7 @@ struct QtGreyHost : QtGrey {
         (void)fic_ctx_set_option(c, "search", 0);
         return rc;
     }
-    static void give(Ctx* c, bool ok) { ok ? cache_give(c) : fic_ctx_destroy(c); }
+    static void give(Ctx* c, bool ok) { ok ? g_idle_grey.give(c) : fic_ctx_destroy(c); }
     // every level reads the top context's scaled copy, made here: the original, 2:1 scaled (FC:970-1007)
     static int prepare(Ctx* top) { return fic_launch_scale(top->b.gray, top->b.scaled, top->g, nullptr); }
     static QtViews<Px> views(const Ctx* c, const Ctx* top) { return {c->b.gray, top->b.scaled, c->o.qrows, c->g.n_iso > 1 ? c->o.iso : nullptr}; }
@@ -52,7 +52,7 @@ struct QtRgbHost : QtRgb {
     static constexpr const DecodeKind& kDecode = kDecodeRgb;
     static Ctx* take(int device, const FicGeom& g)
     {
-        Ctx* c = rgb_cache_take(device, g.W, g.H, g.B, g.wK);
+        Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, 1);
         return c ? c : fic_rgb_ctx_create(device, g.W, g.H, g.B, g.wK, 1);
     }
     static int encode(Ctx* c, const uint8_t*, const int32_t* argb, int = 0)   // exactly the one-shot RGB encode of this level
@@ -60,14 +60,10 @@ struct QtRgbHost : QtRgb {
         const int rc = fic_rgb_ctx_set_argb_host(c, argb);
         return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
     }
-    static void give(Ctx* c, bool ok) { ok ? rgb_cache_give(c) : fic_rgb_ctx_destroy(c); }
+    static void give(Ctx* c, bool ok) { ok ? g_idle_rgb.give(c) : fic_rgb_ctx_destroy(c); }
     static int prepare(Ctx*) { return 0; }
-    static QtViews<Px> views(const Ctx* c, const Ctx*)   // every level reads its own scaleImageRGB copy, made by its encode
-    {
-        QtViews<Px> v{};
-        rgb_ctx_views(c, &v.image, &v.scaled, &v.qrows);
-        return v;
-    }
+    // every level reads its own scaleImageRGB copy, made by its encode (image 0 of the context)
+    static QtViews<Px> views(const Ctx* c, const Ctx*) { return {c->argb, c->scaled, c->qrows, nullptr}; }
     static int scale(const Px* image, Px* scaled, const FicGeom& g) { return fic_launch_scale_rgb(image, scaled, g, nullptr); }
 };
 
@@ -80,18 +76,13 @@ struct QtRgbIsoHost : QtRgbIso {
     static constexpr const DecodeKind& kDecode = kDecodeRgb;
     static Ctx* take(int device, const FicGeom& g)
     {
-        Ctx* c = rgb_cache_take(device, g.W, g.H, g.B, g.wK, g.n_iso);
+        Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, g.n_iso);
         return c ? c : fic_rgb_ctx_create_iso(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
     }
     static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int = 0) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's
     static void give(Ctx* c, bool ok) { QtRgbHost::give(c, ok); }
     static int prepare(Ctx*) { return 0; }
-    static QtViews<Px> views(const Ctx* c, const Ctx*)
-    {
-        QtViews<Px> v{};
-        rgb_ctx_views(c, &v.image, &v.scaled, &v.qrows, &v.iso);
-        return v;
-    }
+    static QtViews<Px> views(const Ctx* c, const Ctx*) { return {c->argb, c->scaled, c->qrows, c->iso}; }   // iso NULL on n_iso = 1: the identity
     static int scale(const Px* image, Px* scaled, const FicGeom& g) { return fic_launch_scale_rgb(image, scaled, g, nullptr); }
 };
 
@@ -128,6 +119,7 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     if (rc) return rc;
 
     typename Fmt::Ctx* c[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    DevMem mem(device);              // the scratch of this call: freed on every way out
     char* scratch = nullptr;
     for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
         c[l] = Fmt::take(device, L.g[l]);
@@ -144,7 +136,7 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     const int n1 = L.nl == 3 ? L.g[1].Nr : 0, nkeys = top.Nr + n1;
     const size_t o_keys = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4), o_sel = o_keys + (budget ? align256((size_t)nkeys * 4) : 0),
                  o_stats = o_sel + (budget ? align256(FIC_QT_SELECT_WORDS * 4) : 0), total = o_stats + (budget ? 256 : 0);
-    if (rc == FIC_OK) rc = dev_alloc(&scratch, total);
+    if (rc == FIC_OK) rc = mem.alloc(scratch, total);
     if (rc == FIC_OK && Fmt::prepare(c[0])) rc = fail(FIC_E_HIP, "k_scale launch failed");
     const uint32_t* sse[kQtMaxLevels];
     const int32_t* qrows[kQtMaxLevels];
@@ -203,7 +195,6 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s SSE: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
     ErrKeep keep;
-    if (scratch) (void)hipFree(scratch);
     for (int l = 0; l < L.nl; l++)
         if (c[l]) Fmt::give(c[l], rc == FIC_OK);
     return rc;
@@ -297,19 +288,17 @@ int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int64_t ran
     if (n < 1 || n >= 0x7FFFFFFFll || rank < 0) return fail(FIC_E_ARGUMENT, "fic_debug_qt_select: n = %lld, rank = %lld", (long long)n, (long long)rank);
     int rc = check_device(device);
     if (rc) return rc;
+    DevMem mem(device);
     char* scratch = nullptr;
     const size_t o_sel = align256((size_t)n * 4);
-    rc = dev_alloc(&scratch, o_sel + FIC_QT_SELECT_WORDS * 4);
+    rc = mem.alloc(scratch, o_sel + FIC_QT_SELECT_WORDS * 4);
     if (rc) return rc;
     uint32_t res[4] = {0, 0, 0, 0};
     hipError_t e = hipMemcpy(scratch, keys, (size_t)n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && fic_launch_qt_select((const uint32_t*)scratch, (uint32_t)n, (uint32_t)(rank < n ? rank : n), (uint32_t*)(scratch + o_sel), nullptr))
-        rc = fail(FIC_E_HIP, "fic_debug_qt_select: launch failed");
-    if (rc == FIC_OK && e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 4, sizeof(res), hipMemcpyDeviceToHost);
-    if (rc == FIC_OK && e != hipSuccess) rc = fail(FIC_E_HIP, "fic_debug_qt_select: %s", hipGetErrorString(e));
-    ErrKeep keep;
-    (void)hipFree(scratch);
-    if (rc) return rc;
+        return fail(FIC_E_HIP, "fic_debug_qt_select: launch failed");
+    if (e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 4, sizeof(res), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_qt_select: %s", hipGetErrorString(e));
     *key_out = res[0];
     memcpy(threshold_out, &res[1], sizeof(float));
     *above_out = res[2];

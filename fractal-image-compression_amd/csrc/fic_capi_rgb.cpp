@@ -4,50 +4,15 @@
 
 using namespace ficd;
 
+IdleCache<fic_rgb_ctx, 4> ficd::g_idle_rgb;
+
 extern "C" {
 
 // ---- joint-RGB encode (encodeRGB FC:171-219) -----------------------------------------------------
-// A context owns the device working set of `planes` colour images of one geometry (config-5 style batches; the one-shot
-// entry keeps a few single-image contexts).  The kernels take the image from their grid: a batch is one launch per stage on the
-// caller's stream (only the matrix-core full search runs image by image).  The covariance sums stay sequential f32 in the reference's order (FC:781-792: they exceed 2^24).
-struct fic_rgb_ctx {
-    int device = 0;
-    FicGeom g;
-    int32_t* argb_own = nullptr;     // context-owned input copy
-    const int32_t* argb = nullptr;   // input in use (own copy or the caller's device pointer)
-    int32_t* scaled = nullptr;       // per plane: [H/2][W/2]
-    uint16_t* pool_sum = nullptr;    // [N_d][n]
-    float* pool_cf = nullptr;        // [N_d][n] (full search at B = 4 / 8)
-    FicRgbDomStat* pool_st = nullptr;
-    int16_t* rng_t = nullptr;
-    FicRgbRngStat* rng_st = nullptr;
-    unsigned long long* key = nullptr;
-    int32_t *idx_local = nullptr, *idx_global = nullptr, *qrows = nullptr, *collage = nullptr;
-    float *a = nullptr, *bR = nullptr, *bG = nullptr, *bB = nullptr;
-    int32_t* iso = nullptr;          // winning isometries [planes][N_r] (n_iso = 8 contexts only; g.n_iso says which)
-    int32_t* dec_image = nullptr;    // decoder: image, scaled image, state, per-pixel squared changes (one plane at a time)
-    int32_t* dec_scaled = nullptr;
-    FicDecodeState* dec_state = nullptr;
-    uint32_t* dec_sq = nullptr;
-    FicRgbQ q;                       // matrix-core full search (allocated on first use; one image at a time, stream-ordered)
-    int opt_sweep = 0;               // 0 auto, 1 VALU sweeps, 2 matrix-core full search
-    int opt_chunks = 0;              // pool chunks of the matrix-core sweep (0 = automatic)
-    int last_sweep = 0;              // what the last encode ran: 1 / 2
-    bool have_input = false, encoded_any = false, have_collage = false;
-    hipStream_t last_stream = nullptr;
-    std::mutex mu;
-};
-
+// A context (fic_rgb_ctx, fic_internal.h) owns the device working set of `planes` colour images of one geometry (config-5 style
+// batches; the one-shot entry keeps a few single-image contexts).  The covariance sums stay sequential f32 in the reference's
+// order (FC:781-792: they exceed 2^24).
 namespace {
-void rgb_free_all(fic_rgb_ctx* c)
-{
-    (void)hipSetDevice(c->device);
-    void* ptrs[] = {c->argb_own, c->scaled, c->pool_sum, c->pool_cf, c->pool_st, c->rng_t, c->rng_st, c->key, c->idx_local,
-                    c->idx_global, c->qrows, c->collage, c->a, c->bR, c->bG, c->bB, c->iso, c->dec_image, c->dec_scaled, c->dec_state, c->dec_sq,
-                    c->q.poolQ, c->q.dflat, c->q.rngQ, c->q.qst, c->q.rngE, c->q.theta_g, c->q.amax, c->q.stats};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-}
 // buffers of plane p as the per-image kernels expect them
 void rgb_plane(const fic_rgb_ctx* c, int p, FicRgbBuffers* b, FicRgbOutputs* o)
 {
@@ -100,35 +65,24 @@ int rgb_q_setup(fic_rgb_ctx* c)
 {
     const FicGeom& g = c->g;
     FicRgbQ& q = c->q;
-    if (q.poolQ) return FIC_OK;
-    unsigned long long* const stats = q.stats;           // option "sweep_stats": set before the first matrix-core encode too
+    if (q.amax) return FIC_OK;                           // the last one ensured: every store is there
     const int unroll = fic_q_unroll(g.B, 1), CT = fic_q_ct(g.B);
     const size_t NK = (size_t)g.n / 16;
     q.ndtiles = (g.Nd + 31) / 32;
     q.ndtiles_alloc = q.ndtiles + 2 * unroll;
     const int nct = (int)(((long long)g.Nr * g.n_iso + 31) / 32);       // n_iso = 8: 8 columns per range block
     q.nct_alloc = ((nct + CT - 1) / CT * CT + CT + 1) & ~1;
-    int rc = FIC_OK;
-    auto A = [&](hipError_t e) { if (rc == FIC_OK && e != hipSuccess) rc = fail(FIC_E_HIP, "RGB matrix-core buffers: %s", hipGetErrorString(e)); };
-    A(hipMalloc(&q.poolQ, (size_t)q.ndtiles_alloc * NK * 64 * 16));
-    A(hipMalloc(&q.dflat, (size_t)q.ndtiles_alloc * sizeof(uint32_t)));
-    A(hipMalloc(&q.rngQ, (size_t)q.nct_alloc * NK * 64 * 16));
-    A(hipMalloc(&q.qst, (size_t)g.Nr * sizeof(FicRngStat)));
-    A(hipMalloc(&q.rngE, (size_t)g.Nr * sizeof(float)));
-    A(hipMalloc(&q.theta_g, (size_t)q.nct_alloc * 32 * sizeof(uint32_t)));     // per column incl. the padded column tiles (the sweep's fast path reads them)
-    A(hipMalloc(&q.amax, 256));
-    if (rc != FIC_OK) {
-        void* ptrs[] = {q.poolQ, q.dflat, q.rngQ, q.qst, q.rngE, q.theta_g, q.amax};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        q = FicRgbQ();
-        q.stats = stats;
-    }
-    return rc;
+    // every store is ensured on its own pointer: a failed allocation leaves the earlier ones with the owner and is retried next time
+    DevMem& m = c->mem;
+    int rc = m.ensure(q.poolQ, (size_t)q.ndtiles_alloc * NK * 64 * 16);
+    if (rc == FIC_OK) rc = m.ensure(q.dflat, (size_t)q.ndtiles_alloc * sizeof(uint32_t));
+    if (rc == FIC_OK) rc = m.ensure(q.rngQ, (size_t)q.nct_alloc * NK * 64 * 16);
+    if (rc == FIC_OK) rc = m.ensure(q.qst, (size_t)g.Nr * sizeof(FicRngStat));
+    if (rc == FIC_OK) rc = m.ensure(q.rngE, (size_t)g.Nr * sizeof(float));
+    if (rc == FIC_OK) rc = m.ensure(q.theta_g, (size_t)q.nct_alloc * 32 * sizeof(uint32_t));     // per column incl. the padded column tiles (the sweep's fast path reads them)
+    if (rc == FIC_OK) rc = m.ensure(q.amax, sizeof(uint32_t));              // one word: the largest domain-operand norm
+    return rc ? fail(FIC_E_HIP, "RGB matrix-core buffers: %s", g_mem_why) : FIC_OK;
 }
-// idle single-image contexts of the one-shot RGB entry, most recently used last
-std::mutex g_rgb_mu;
-std::vector<fic_rgb_ctx*> g_rgb_cache;
 }  // namespace
 
 fic_rgb_ctx* fic_rgb_ctx_create(int device, int w, int h, int B, int wK, int planes)
@@ -147,33 +101,31 @@ fic_rgb_ctx* fic_rgb_ctx_create_iso(int device, int w, int h, int B, int wK, int
         return nullptr;
     }
     g.n_iso = n_iso;                 // the other fields are those of the 1-isometry geometry (the grey sweeps' tiling is not used here)
-    int ndev = fic_device_count();
-    if (ndev <= 0) { fail(FIC_E_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); return nullptr; }
-    if (device < 0 || device >= ndev) { fail(FIC_E_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { fail(FIC_E_HIP, "hipSetDevice(%d) failed", device); return nullptr; }
+    if (!create_device_ok(device)) return nullptr;
     fic_rgb_ctx* c = new fic_rgb_ctx();
     c->device = device;
+    c->mem.set_device(device);
     c->g = g;
     const size_t P = (size_t)planes, npix = (size_t)w * h, nr = (size_t)g.Nr, nd = (size_t)g.Nd, n = (size_t)g.n;
+    DevMem& m = c->mem;
     int rc = FIC_OK;
     auto A = [&](int r) { if (rc == FIC_OK) rc = r; };
-    A(dev_alloc(&c->scaled, P * g.Ws * g.Hs));
-    A(dev_alloc(&c->pool_sum, P * nd * n));
-    A(dev_alloc(&c->pool_st, P * nd));
-    A(dev_alloc(&c->rng_t, P * nr * n));
-    A(dev_alloc(&c->rng_st, P * nr));
-    A(dev_alloc(&c->key, P * nr));
-    A(dev_alloc(&c->idx_local, P * nr));
-    A(dev_alloc(&c->idx_global, P * nr));
-    A(dev_alloc(&c->a, P * nr));
-    A(dev_alloc(&c->bR, P * nr));
-    A(dev_alloc(&c->bG, P * nr));
-    A(dev_alloc(&c->bB, P * nr));
-    A(dev_alloc(&c->qrows, P * nr * 5));
-    A(dev_alloc(&c->collage, P * npix));
-    if (n_iso == 8) A(dev_alloc(&c->iso, P * nr));
+    A(m.alloc(c->scaled, P * g.Ws * g.Hs));
+    A(m.alloc(c->pool_sum, P * nd * n));
+    A(m.alloc(c->pool_st, P * nd));
+    A(m.alloc(c->rng_t, P * nr * n));
+    A(m.alloc(c->rng_st, P * nr));
+    A(m.alloc(c->key, P * nr));
+    A(m.alloc(c->idx_local, P * nr));
+    A(m.alloc(c->idx_global, P * nr));
+    A(m.alloc(c->a, P * nr));
+    A(m.alloc(c->bR, P * nr));
+    A(m.alloc(c->bG, P * nr));
+    A(m.alloc(c->bB, P * nr));
+    A(m.alloc(c->qrows, P * nr * 5));
+    A(m.alloc(c->collage, P * npix));
+    if (n_iso == 8) A(m.alloc(c->iso, P * nr));
     if (rc != FIC_OK) {
-        rgb_free_all(c);
         delete c;
         return nullptr;
     }
@@ -185,7 +137,6 @@ void fic_rgb_ctx_destroy(fic_rgb_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    rgb_free_all(c);
     delete c;
 }
 
@@ -195,7 +146,7 @@ int fic_rgb_ctx_set_argb_host(fic_rgb_ctx* c, const int32_t* argb)
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     const size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (!c->argb_own) { int rc = dev_alloc(&c->argb_own, npix); if (rc) return rc; }
+    if (int rc = c->mem.ensure(c->argb_own, npix)) return rc;
     HIP_TRY(hipStreamSynchronize(c->last_stream));     // a previous encode may still read the copy
     HIP_TRY(hipMemcpy(c->argb_own, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
     c->argb = c->argb_own;
@@ -230,8 +181,8 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
     const bool use_q = g.full && g.Nd < (1 << 24) && (want == 2 || (want == 0 && ((double)g.n_iso * g.Nr * g.Nd >= 3e7 || g.B == 16)));
     if (use_q && rgb_q_setup(c)) return FIC_E_HIP;
     if (use_q) rgb_q_chunks(c);
-    if (!use_q && g.full && g.B <= 8 && !c->pool_cf) {      // the VALU full-search sweep's f32 pool copy (k_sweep_rgb_fast), on first use
-        const int rc = dev_alloc(&c->pool_cf, (size_t)g.planes * g.Nd * g.n);
+    if (!use_q && g.full && g.B <= 8) {                     // the VALU full-search sweep's f32 pool copy (k_sweep_rgb_fast), on first use
+        const int rc = c->mem.ensure(c->pool_cf, (size_t)g.planes * g.Nd * g.n);
         if (rc != FIC_OK) return rc;
     }
     c->last_sweep = use_q ? 2 : 1;
@@ -268,16 +219,7 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
     }
     if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
         HIP_TRY(hipSetDevice(c->device));
-        if (value && !c->q.stats) {
-            HIP_TRY(hipMalloc((void**)&c->q.stats, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipMemset(c->q.stats, 0, 8 * sizeof(unsigned long long)));
-            HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
-        } else if (!value && c->q.stats) {
-            HIP_TRY(hipStreamSynchronize(c->last_stream));
-            (void)hipFree(c->q.stats);
-            c->q.stats = nullptr;
-        }
-        return FIC_OK;
+        return sweep_stats_option(c->mem, c->q.stats, value, c->last_stream);
     }
     return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: unknown option '%s'", name);
 }
@@ -288,20 +230,11 @@ int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capac
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->encoded_any || c->last_sweep != 2 || !c->q.poolQ)
         return fail(FIC_E_STATE, "fic_rgb_ctx_debug_q_host: no encode through the matrix-core sweep (\"sweep\" = 2) yet");
-    const FicGeom& g = c->g;
+    if (which < 0 || which > 5) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_q_host: which must be 0..5");
     const FicRgbQ& q = c->q;
-    const size_t NK = (size_t)g.n / 16;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    switch (which) {                                   // the stores exactly as rgb_q_setup allocates them (last plane encoded)
-    case 0: src = q.poolQ; bytes = (size_t)q.ndtiles_alloc * NK * 64 * 16; break;
-    case 1: src = q.dflat; bytes = (size_t)q.ndtiles_alloc * sizeof(uint32_t); break;
-    case 2: src = q.rngQ; bytes = (size_t)q.nct_alloc * NK * 64 * 16; break;
-    case 3: src = q.rngE; bytes = (size_t)g.Nr * sizeof(float); break;
-    case 4: src = q.qst; bytes = (size_t)g.Nr * sizeof(FicRngStat); break;
-    case 5: src = q.amax; bytes = sizeof(uint32_t); break;
-    default: return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_q_host: which must be 0..5");
-    }
+    const void* const stores[6] = {q.poolQ, q.dflat, q.rngQ, q.rngE, q.qst, q.amax};
+    const void* src = stores[which];
+    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them (last plane encoded)
     *size = (int64_t)bytes;
     if (!out) return FIC_OK;
     if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_rgb_ctx_debug_q_host: %zu bytes needed", bytes);
@@ -321,15 +254,7 @@ int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_stats: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->q.stats) return fail(FIC_E_STATE, "fic_rgb_ctx_sweep_stats: set the option \"sweep_stats\" first");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out8, c->q.stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) {
-        HIP_TRY(hipMemset(c->q.stats, 0, 8 * sizeof(uint64_t)));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-    }
-    return FIC_OK;
+    return sweep_stats_read("fic_rgb_ctx_sweep_stats", c->q.stats, c->device, c->last_stream, out8, reset);
 }
 
 int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
@@ -412,10 +337,10 @@ int fic_rgb_ctx_decode_zoom_host(fic_rgb_ctx* c, int zoom, int32_t* argb_out, fl
     const size_t npix = (size_t)g1.W * g1.H;
     DecodeJob J;
     if (zoom == 1) {
-        if (!c->dec_image) { int rc = dev_alloc(&c->dec_image, npix); if (rc) return rc; }
-        if (!c->dec_scaled) { int rc = dev_alloc(&c->dec_scaled, (size_t)g.Ws * g.Hs); if (rc) return rc; }
-        if (!c->dec_state) { int rc = dev_alloc(&c->dec_state, 1); if (rc) return rc; }
-        if (!c->dec_sq) { int rc = dev_alloc(&c->dec_sq, fic_decode_sq_words(1, npix)); if (rc) return rc; }
+        if (int rc = c->mem.ensure(c->dec_image, npix)) return rc;
+        if (int rc = c->mem.ensure(c->dec_scaled, (size_t)g.Ws * g.Hs)) return rc;
+        if (int rc = c->mem.ensure(c->dec_state, 1)) return rc;
+        if (int rc = c->mem.ensure(c->dec_sq, fic_decode_sq_words(1, npix))) return rc;
         J.borrow(kDecodeRgb, g1, c->last_stream, c->dec_scaled, c->dec_image, c->dec_state, c->dec_sq);
     } else {
         const int rc = J.open("fic_rgb_ctx_decode_zoom_host", c->device, kDecodeRgb, g1, c->last_stream);
@@ -441,41 +366,6 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
 
 }  // extern "C"
 
-fic_rgb_ctx* ficd::rgb_cache_take(int device, int w, int h, int B, int wK, int n_iso)
-{
-    std::lock_guard<std::mutex> lk(g_rgb_mu);
-    for (size_t i = g_rgb_cache.size(); i-- > 0;) {
-        fic_rgb_ctx* c = g_rgb_cache[i];
-        const FicGeom& g = c->g;
-        if (c->device == device && g.W == w && g.H == h && g.B == B && g.wK == wK && g.n_iso == n_iso && g.planes == 1) {
-            g_rgb_cache.erase(g_rgb_cache.begin() + (long)i);
-            return c;
-        }
-    }
-    return nullptr;
-}
-void ficd::rgb_cache_give(fic_rgb_ctx* c)
-{
-    fic_rgb_ctx* evict = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_rgb_mu);
-        g_rgb_cache.push_back(c);
-        if (g_rgb_cache.size() > 4) {
-            evict = g_rgb_cache.front();
-            g_rgb_cache.erase(g_rgb_cache.begin());
-        }
-    }
-    if (evict) fic_rgb_ctx_destroy(evict);
-}
-
-void ficd::rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5, const int32_t** iso)
-{
-    if (iso) *iso = c->iso;
-    if (argb) *argb = c->argb;
-    if (scaled) *scaled = c->scaled;
-    if (qrows5) *qrows5 = c->qrows;
-}
-
 extern "C" {
 
 int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK, int device, int32_t* idx_local, float* a,
@@ -491,7 +381,7 @@ int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, in
     if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_iso_argb: null argument");
     if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso);
     // the GUI re-encodes the same image on every slider move (CTL:125-145): keep the last few working sets
-    fic_rgb_ctx* c = rgb_cache_take(device, w, h, B, wK, n_iso);
+    fic_rgb_ctx* c = g_idle_rgb.take(device, w, h, B, wK, n_iso);
     if (!c) c = fic_rgb_ctx_create_iso(device, w, h, B, wK, n_iso, 1);
     if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_rgb_ctx_create recorded why
     int rc = fic_rgb_ctx_set_argb_host(c, argb);
@@ -499,19 +389,9 @@ int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, in
     if (rc == FIC_OK) rc = fic_rgb_ctx_get_results_host(c, idx_local, a, bR, bG, bB, qrows5, collage_argb);
     if (rc == FIC_OK && iso) rc = fic_rgb_ctx_get_iso_host(c, iso);
     ErrKeep keep;
-    if (rc == FIC_OK) rgb_cache_give(c);
+    if (rc == FIC_OK) g_idle_rgb.give(c);
     else fic_rgb_ctx_destroy(c);
     return rc;
 }
 
 }  // extern "C"
-
-void ficd::release_rgb_cache()
-{
-    std::vector<fic_rgb_ctx*> drop;
-    {
-        std::lock_guard<std::mutex> lk(g_rgb_mu);
-        drop.swap(g_rgb_cache);
-    }
-    for (fic_rgb_ctx* c : drop) fic_rgb_ctx_destroy(c);
-}

@@ -1,6 +1,8 @@
-// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the context type, small
-// device-memory helpers, the decode job and the caches' release hooks; error reporting, geometry validation and the stream
-// formats come with fic_stream.h.  Not part of the public interface.
+// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the two context types, the
+// idle-context caches of the one-shot entries, the "sweep_stats" counter block, the decode job and the release hooks; error
+// reporting, geometry validation and the stream formats come with fic_stream.h, the ownership of device memory with
+// fic_devmem.h (the HIP runtime's allocation calls are made in fic_devmem.cpp and nowhere else).  Not part of the public
+// interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -17,6 +19,7 @@
 #include "fic_device.h"
 #include "fic_launch.h"
 #include "fic_stream.h"
+#include "fic_devmem.h"
 
 namespace ficd {
 
@@ -33,30 +36,21 @@ struct ErrKeep {
     ~ErrKeep() { g_err = msg; g_err_code = code; }
 };
 
-template <typename T>
-int dev_alloc(T** p, size_t count)
-{
-    HIP_TRY(hipMalloc((void**)p, count * sizeof(T)));
-    return FIC_OK;
-}
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Makes `device` current, or refuses it with FIC_E_NO_DEVICE (fic_capi.cpp)
 int check_device(int device);
+// The device check of the two *_create entries: records why and returns false, or makes `device` current (fic_capi.cpp)
+bool create_device_ok(int device);
 
-// idle single-plane grey contexts of the one-shot / multi-device entries (fic_capi.cpp)
-fic_ctx* cache_take(int device, int w, int h, int B, int wK, int n_iso);
-void cache_give(fic_ctx* c);
 int encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device,
                    int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows);
 
-// idle single-image joint-RGB contexts of the one-shot RGB entry (fic_capi_rgb.cpp), and the device buffers of image 0 of a
-// context: the input in use [H][W], its scaleImageRGB copy [H/2][W/2], the quantised rows [N_r][5] of the last encode and
-// its winning isometries [N_r] (NULL on an n_iso = 1 context: the identity)
-fic_rgb_ctx* rgb_cache_take(int device, int w, int h, int B, int wK, int n_iso = 1);
-void rgb_cache_give(fic_rgb_ctx* c);
-void rgb_ctx_views(const fic_rgb_ctx* c, const int32_t** argb, const int32_t** scaled, const int32_t** qrows5,
-                   const int32_t** iso = nullptr);
+// The "sweep_stats" counter block of either context (fic_capi.cpp): 8 u64 device counters of k_sweep_q, held by the context's
+// owner.  The option switches it on (zeroed) or off; the read entry copies it out and may reset it.
+int sweep_stats_option(DevMem& mem, unsigned long long*& stats, int on, hipStream_t last_stream);
+int sweep_stats_read(const char* who, unsigned long long* stats, int device, hipStream_t last_stream, uint64_t* out8, int reset);
+
 
 // device arena of a decode (fic_capi_decode.cpp): one allocation kept between calls, taken and given back by a DecodeJob
 struct Arena {
@@ -103,9 +97,8 @@ struct DecodeJob {
             const std::function<int(int)>& iteration);
 };
 
-// what fic_release_cache() frees besides the grey contexts
+// what fic_release_cache() frees besides the idle contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp
-void release_rgb_cache();          // fic_capi_rgb.cpp
 void release_comms();              // fic_capi_multi.cpp
 
 }  // namespace ficd
@@ -114,6 +107,7 @@ void release_comms();              // fic_capi_multi.cpp
 struct fic_ctx {
     int device = 0;
     FicGeom g;
+    ficd::DevMem mem;                // owns every device and pinned pointer below; b, o and lsq view what it holds
     FicBuffers b;
     FicOutputs o;
     uint8_t* gray_own = nullptr;     // context-owned input copy
@@ -151,4 +145,91 @@ struct fic_ctx {
     double acc_ms = 0.0;
     int acc_n = 0;
     std::mutex mu;
+    ~fic_ctx();                      // events and the own stream (fic_capi.cpp); the memory goes with `mem`
 };
+
+// Device-resident working set of `planes` colour images of one geometry (fic_rgb_ctx_* of include/fic.h, fic_capi_rgb.cpp).
+// The kernels take the image from their grid: a batch is one launch per stage on the caller's stream (only the matrix-core
+// full search runs image by image).
+struct fic_rgb_ctx {
+    int device = 0;
+    FicGeom g;
+    ficd::DevMem mem;                // owns every device pointer below; q views what it holds
+    int32_t* argb_own = nullptr;     // context-owned input copy
+    const int32_t* argb = nullptr;   // input in use (own copy or the caller's device pointer)
+    int32_t* scaled = nullptr;       // per plane: [H/2][W/2]
+    uint16_t* pool_sum = nullptr;    // [N_d][n]
+    float* pool_cf = nullptr;        // [N_d][n] (full search at B = 4 / 8)
+    FicRgbDomStat* pool_st = nullptr;
+    int16_t* rng_t = nullptr;
+    FicRgbRngStat* rng_st = nullptr;
+    unsigned long long* key = nullptr;
+    int32_t *idx_local = nullptr, *idx_global = nullptr, *qrows = nullptr, *collage = nullptr;
+    float *a = nullptr, *bR = nullptr, *bG = nullptr, *bB = nullptr;
+    int32_t* iso = nullptr;          // winning isometries [planes][N_r] (n_iso = 8 contexts only; g.n_iso says which)
+    int32_t* dec_image = nullptr;    // decoder: image, scaled image, state, per-pixel squared changes (one plane at a time)
+    int32_t* dec_scaled = nullptr;
+    FicDecodeState* dec_state = nullptr;
+    uint32_t* dec_sq = nullptr;
+    FicRgbQ q;                       // matrix-core full search (allocated on first use; one image at a time, stream-ordered)
+    int opt_sweep = 0;               // 0 auto, 1 VALU sweeps, 2 matrix-core full search
+    int opt_chunks = 0;              // pool chunks of the matrix-core sweep (0 = automatic)
+    int last_sweep = 0;              // what the last encode ran: 1 / 2
+    bool have_input = false, encoded_any = false, have_collage = false;
+    hipStream_t last_stream = nullptr;
+    std::mutex mu;
+};
+
+namespace ficd {
+
+// Idle single-image contexts of the one-shot entries, most recently used last; the oldest is destroyed when a give() finds
+// every slot taken.  The grey cache has 16 slots (the multi-device entry parks one context per device), the joint-RGB one 4.
+inline void destroy_ctx(fic_ctx* c) { fic_ctx_destroy(c); }
+inline void destroy_ctx(fic_rgb_ctx* c) { fic_rgb_ctx_destroy(c); }
+template <typename Ctx, size_t kSlots>
+class IdleCache {
+public:
+    Ctx* take(int device, int w, int h, int B, int wK, int n_iso)
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        for (size_t i = idle_.size(); i-- > 0;) {
+            Ctx* c = idle_[i];
+            const FicGeom& g = c->g;
+            if (c->device == device && g.W == w && g.H == h && g.B == B && g.wK == wK && g.n_iso == n_iso && g.planes == 1) {
+                idle_.erase(idle_.begin() + (long)i);
+                return c;
+            }
+        }
+        return nullptr;
+    }
+    void give(Ctx* c)
+    {
+        Ctx* evict = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            idle_.push_back(c);
+            if (idle_.size() > kSlots) {
+                evict = idle_.front();
+                idle_.erase(idle_.begin());
+            }
+        }
+        if (evict) destroy_ctx(evict);
+    }
+    void drain()
+    {
+        std::vector<Ctx*> drop;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            drop.swap(idle_);
+        }
+        for (Ctx* c : drop) destroy_ctx(c);
+    }
+
+private:
+    std::mutex mu_;
+    std::vector<Ctx*> idle_;
+};
+extern IdleCache<fic_ctx, 16> g_idle_grey;       // fic_capi.cpp
+extern IdleCache<fic_rgb_ctx, 4> g_idle_rgb;     // fic_capi_rgb.cpp
+
+}  // namespace ficd

@@ -540,6 +540,11 @@ FIC_API int fic_ctx_debug_q_host(fic_ctx* ctx, int which, void* out, int64_t cap
  * columns per range block, column 8 j + k the copy c_k of range j with c_k[src_k(i)] = greyR[i]; the other stores are unchanged. */
 FIC_API int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 
+/* Test hook: what the library holds right now, process-wide, through contexts, the one-shot caches, the decoders' arenas and
+ * any call in flight: out4 = {device bytes, device allocations, pinned host bytes, pinned host allocations}.  All four are 0
+ * once every context is destroyed and fic_release_cache() has run.  Needs no device. */
+FIC_API int fic_debug_live_memory(int64_t out4[4]);
+
 #ifdef __cplusplus
 }
 #endif
