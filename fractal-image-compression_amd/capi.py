@@ -153,6 +153,10 @@ def lib():
         "fic_encode_gray_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p, C.POINTER(C.c_int64)]),
         "fic_encode_gray_quadtree_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_encode_gray_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_rgb_ctx_get_lsq_error_host": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "fic_encode_rgb_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.POINTER(C.c_int64)]),
+        "fic_encode_rgb_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
+        "fic_encode_rgb_quadtree_iso_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
         "fic_debug_live_memory": (C.c_int, [C.POINTER(C.c_int64)]),
     }
@@ -336,10 +340,12 @@ def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):
     return out[:cap], np.float32(avg.value), it.value, w, h
 
 
-def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1):
+def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1, search="reference"):
     """encodeRGB (FC:171-219) on the GPU.  argb: int32 [h*w].  Returns a dict of [N_r] arrays
     (idx_local, a, bR, bG, bB, iso, qrows [N_r,5]) and, when asked, the collage (int32 [h*w]).  n_iso = 8: the search also
-    tries the 8 isometries of the domain block (fic_encode_rgb_iso_argb; `iso` is all 0 with n_iso = 1, the reference path)."""
+    tries the 8 isometries of the domain block (fic_encode_rgb_iso_argb; `iso` is all 0 with n_iso = 1, the reference path).
+    search="lsq": the least-squares search (fic_encode_rgb_lsq_argb), with the winners' errors as "E" (int64 [N_r])."""
+    lsq = search_id(search)
     Rw, Rh, Dw, Dh = geometry(w, h, B)
     nr = Rw * Rh
     argb = np.ascontiguousarray(argb, np.int32).reshape(-1)
@@ -349,10 +355,14 @@ def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1):
          "bG": np.zeros(nr, np.float32), "bB": np.zeros(nr, np.float32), "iso": np.zeros(nr, np.int32),
          "qrows": np.zeros((nr, 5), np.int32)}
     col = np.zeros(w * h, np.int32) if want_collage else None
-    check(lib().fic_encode_rgb_iso_argb(ptr(argb, C.c_int32), w, h, B, wK, n_iso, device, ptr(r["idx_local"], C.c_int32),
-                                        ptr(r["a"], C.c_float), ptr(r["bR"], C.c_float), ptr(r["bG"], C.c_float),
-                                        ptr(r["bB"], C.c_float), ptr(r["iso"], C.c_int32), ptr(r["qrows"], C.c_int32),
-                                        ptr(col, C.c_int32)))
+    args = (ptr(argb, C.c_int32), w, h, B, wK, n_iso, device, ptr(r["idx_local"], C.c_int32), ptr(r["a"], C.c_float),
+            ptr(r["bR"], C.c_float), ptr(r["bG"], C.c_float), ptr(r["bB"], C.c_float), ptr(r["iso"], C.c_int32),
+            ptr(r["qrows"], C.c_int32), ptr(col, C.c_int32))
+    if lsq:
+        r["E"] = np.zeros(nr, np.int64)
+        check(lib().fic_encode_rgb_lsq_argb(*args, ptr(r["E"], C.c_int64)))
+    else:
+        check(lib().fic_encode_rgb_iso_argb(*args))
     if want_collage:
         r["collage"] = col
     return r
@@ -413,8 +423,18 @@ class RgbEncoder:
         check(lib().fic_rgb_ctx_sync(self._h))
 
     def set_option(self, name, value):
-        """"sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search."""
+        """"sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search.  "search": 0 / "reference" or 1 / "lsq" (least
+        squares; "sweep" then means 0 auto, 1 generic, 2 fast)."""
+        if name == "search":
+            value = search_id(value)
         check(lib().fic_rgb_ctx_set_option(self._h, name.encode(), int(value)))
+
+    def lsq_error(self):
+        """int64 [planes, N_r]: E of the winners of the last encode under set_option("search", "lsq") -- 10^6 times the squared
+        error of the quantised map over the three channels (fic_rgb_ctx_get_lsq_error_host)."""
+        E = np.zeros((self.planes, self.n_ranges), np.int64)
+        check(lib().fic_rgb_ctx_get_lsq_error_host(self._h, ptr(E, C.c_int64)))
+        return E
 
     def last_sweep(self):
         return check(lib().fic_rgb_ctx_last_sweep(self._h))
@@ -576,16 +596,17 @@ def _argb_image(argb, w, h):
     return a
 
 
-def encode_rgb_quadtree(argb, w, h, B_max, B_min, wK=0, threshold=float("inf"), device=0):
+def encode_rgb_quadtree(argb, w, h, B_max, B_min, wK=0, threshold=float("inf"), device=0, search="reference"):
     """Joint-RGB quadtree encode of the int32 ARGB pixels `argb` ([h*w] or [h, w]; fic_encode_rgb_quadtree_argb).  wK = 0:
     full search at every level.  Returns the leaf table int32 [n_leaves, 8] with the columns QT_RGB_LEAF_FIELDS (q1..q4: the
-    level's encode_rgb qrows row), in stream order."""
+    level's encode_rgb qrows row), in stream order.  search="lsq": the per-level codebooks come from the least-squares search
+    (fic_encode_rgb_quadtree_lsq_argb)."""
+    fn = lib().fic_encode_rgb_quadtree_lsq_argb if search_id(search) else lib().fic_encode_rgb_quadtree_argb
     a = _argb_image(argb, w, h)
     cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
     out = np.zeros((max(cap, 1), 8), np.int32)
     n = C.c_int()
-    check(lib().fic_encode_rgb_quadtree_argb(ptr(a, C.c_int32), w, h, B_max, B_min, wK, float(threshold), device,
-                                             ptr(out, C.c_int32), out.shape[0], C.byref(n)))
+    check(fn(ptr(a, C.c_int32), w, h, B_max, B_min, wK, float(threshold), device, ptr(out, C.c_int32), out.shape[0], C.byref(n)))
     return out[:n.value].copy()
 
 
@@ -675,15 +696,16 @@ def decode_rgb_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
 QT_RGB_ISO_LEAF_FIELDS = QT_RGB_LEAF_FIELDS + ("iso",)
 
 
-def encode_rgb_quadtree_iso(argb, w, h, B_max, B_min, wK=0, n_iso=8, threshold=float("inf"), device=0):
+def encode_rgb_quadtree_iso(argb, w, h, B_max, B_min, wK=0, n_iso=8, threshold=float("inf"), device=0, search="reference"):
     """Joint-RGB quadtree encode with n_iso = 1 or 8 isometries (fic_encode_rgb_quadtree_iso_argb): the leaf table int32
-    [n_leaves, 9] with the columns QT_RGB_ISO_LEAF_FIELDS, in stream order.  n_iso = 1: encode_rgb_quadtree's rows and iso = 0."""
+    [n_leaves, 9] with the columns QT_RGB_ISO_LEAF_FIELDS, in stream order.  n_iso = 1: encode_rgb_quadtree's rows and iso = 0.
+    search="lsq": the per-level codebooks come from the least-squares search (fic_encode_rgb_quadtree_iso_lsq_argb)."""
+    fn = lib().fic_encode_rgb_quadtree_iso_lsq_argb if search_id(search) else lib().fic_encode_rgb_quadtree_iso_argb
     a = _argb_image(argb, w, h)
     cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
     out = np.zeros((max(cap, 1), 9), np.int32)
     n = C.c_int()
-    check(lib().fic_encode_rgb_quadtree_iso_argb(ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso, float(threshold), device,
-                                                 ptr(out, C.c_int32), out.shape[0], C.byref(n)))
+    check(fn(ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso, float(threshold), device, ptr(out, C.c_int32), out.shape[0], C.byref(n)))
     return out[:n.value].copy()
 
 

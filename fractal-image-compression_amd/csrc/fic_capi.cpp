@@ -441,9 +441,9 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
 extern "C" {
 
 #ifdef FIC_BUILD_XCHECK
-const char* fic_version(void) { return "fic-hip 0.4 (gfx950, +xcheck sweeps)"; }
+const char* fic_version(void) { return "fic-hip 0.5 (gfx950, +xcheck sweeps)"; }
 #else
-const char* fic_version(void) { return "fic-hip 0.4 (gfx950)"; }
+const char* fic_version(void) { return "fic-hip 0.5 (gfx950)"; }
 #endif
 
 int fic_device_count(void)

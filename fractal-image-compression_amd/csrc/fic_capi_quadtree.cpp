@@ -55,10 +55,16 @@ struct QtRgbHost : QtRgb {
         Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, 1);
         return c ? c : fic_rgb_ctx_create(device, g.W, g.H, g.B, g.wK, 1);
     }
-    static int encode(Ctx* c, const uint8_t*, const int32_t* argb, int = 0)   // exactly the one-shot RGB encode of this level
+    static int encode(Ctx* c, const uint8_t*, const int32_t* argb, int search = 0)   // exactly the one-shot RGB encode of this level
     {
-        const int rc = fic_rgb_ctx_set_argb_host(c, argb);
-        return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
+        int rc = fic_rgb_ctx_set_argb_host(c, argb);
+        if (rc || !search) return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
+        // least squares: the cached context goes back in the reference's mode whatever happens
+        rc = fic_rgb_ctx_set_option(c, "search", search);
+        if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c, 0, nullptr);
+        ErrKeep keep;
+        (void)fic_rgb_ctx_set_option(c, "search", 0);
+        return rc;
     }
     static void give(Ctx* c, bool ok) { ok ? g_idle_rgb.give(c) : fic_rgb_ctx_destroy(c); }
     static int prepare(Ctx*) { return 0; }
@@ -79,7 +85,7 @@ struct QtRgbIsoHost : QtRgbIso {
         Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, g.n_iso);
         return c ? c : fic_rgb_ctx_create_iso(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
     }
-    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int = 0) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int search = 0) { return QtRgbHost::encode(c, gray, argb, search); }   // = fic_encode_rgb_iso_argb's / _lsq_argb's
     static void give(Ctx* c, bool ok) { QtRgbHost::give(c, ok); }
     static int prepare(Ctx*) { return 0; }
     static QtViews<Px> views(const Ctx* c, const Ctx*) { return {c->argb, c->scaled, c->qrows, c->iso}; }   // iso NULL on n_iso = 1: the identity
@@ -96,8 +102,8 @@ struct QtBudget {
 
 // The encode behind fic_encode_*_quadtree_* and the SSE test hooks: every level through the one-shot contexts, then the
 // per-level SSE, the split and the compaction on the device.  leaves / sse_out may be NULL.  budget: NULL, or the threshold
-// comes from the budget's select instead of the argument.  search: the criterion of the per-level codebooks (grey only: 0 the
-// reference's, 1 least squares); everything after them is the same code.
+// comes from the budget's select instead of the argument.  search: the criterion of the per-level codebooks (0 the
+// reference's, 1 least squares: DESIGN.md 4.19 grey, 4.20 colour); everything after them is the same code.
 template <typename Fmt>
 int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
               int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity,
@@ -331,6 +337,13 @@ int fic_encode_rgb_quadtree_argb(const int32_t* argb, int w, int h, int B_max, i
     return qt_encode<QtRgbHost>(nullptr, argb, w, h, B_max, B_min, wK, 1, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
 }
 
+int fic_encode_rgb_quadtree_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold, int device,
+                                     int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_lsq_argb: null argument");
+    return qt_encode<QtRgbHost>(nullptr, argb, w, h, B_max, B_min, wK, 1, threshold, device, leaves, capacity, n_leaves, nullptr, 0, nullptr, 1);
+}
+
 int fic_encode_rgb_quadtree_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int64_t max_leaves, int device,
                                         int32_t* leaves, int64_t capacity, int* n_leaves, float* threshold_out, uint64_t* stats4)
 {
@@ -364,6 +377,13 @@ int fic_encode_rgb_quadtree_iso_argb(const int32_t* argb, int w, int h, int B_ma
 {
     if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_iso_argb: null argument");
     return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0);
+}
+
+int fic_encode_rgb_quadtree_iso_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
+                                         int device, int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!argb || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_quadtree_iso_lsq_argb: null argument");
+    return qt_encode<QtRgbIsoHost>(nullptr, argb, w, h, B_max, B_min, wK, n_iso, threshold, device, leaves, capacity, n_leaves, nullptr, 0, nullptr, 1);
 }
 
 int fic_encode_rgb_quadtree_iso_budget_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int64_t max_leaves,

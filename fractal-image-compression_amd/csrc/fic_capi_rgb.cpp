@@ -170,7 +170,9 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
     if (!c->have_input) return fail(FIC_E_STATE, "fic_rgb_ctx_encode: no input image set");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
+    const hipStream_t prev = c->last_stream;
     c->last_stream = s;
+    if (c->opt_search == 1) return rgb_lsq_encode(c, with_collage, s, prev);      // least squares
     const FicGeom& g = c->g;
     // Full search: the matrix-core sweep where it pays (its prep costs ~50 us; the VALU sweep does ~1e11 pairs/s), or where
     // the VALU full-search kernel does not exist (B = 16).  FIC_RGB_SWEEP=1|2 / option "sweep" override.
@@ -186,6 +188,7 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
         if (rc != FIC_OK) return rc;
     }
     c->last_sweep = use_q ? 2 : 1;
+    c->last_search = 0;
     {
         FicRgbBuffers b;                                  // image 0 of the batch: the kernels take the image from their grid
         FicRgbOutputs o;
@@ -205,6 +208,12 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
     if (!strcmp(name, "sweep")) {
         if (value < 0 || value > 2) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: sweep must be 0 (auto), 1 (VALU) or 2 (matrix cores)");
         c->opt_sweep = value;
+        return FIC_OK;
+    }
+    if (!strcmp(name, "search")) {                     // 0: the reference's criterion, 1: least squares; "sweep" then
+        if (value < 0 || value > 1)                    // means 0 (auto), 1 (generic), 2 (fast): the same three values either way
+            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: search must be 0 (the reference's criterion) or 1 (least squares)");
+        c->opt_search = value;
         return FIC_OK;
     }
     if (!strcmp(name, "chunks")) {
@@ -263,7 +272,12 @@ int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
     const FicGeom& g = c->g;
     const int NK = g.n / 16;
     char buf[96];
-    if (c->last_sweep == 2) {
+    if (c->last_search == 1) {
+        int NC = 1;
+        fic_lsq_rgb_variant(g.B, g.n_iso, &NC);
+        if (c->last_lsq_kind == 2) snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_fast<%d, %d>", 3 * g.DW, NC);
+        else snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_generic");
+    } else if (c->last_sweep == 2) {
         const int kind = fic_q_multi_kind(c->q.nchunks, c->q.tiles_per_chunk);      // what fic_launch_rgbq instantiates
         const int mode = g.n_iso == 8 ? 4 : 3;
         if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, %d>", NK, mode);

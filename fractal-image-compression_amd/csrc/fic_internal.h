@@ -21,6 +21,8 @@
 #include "fic_stream.h"
 #include "fic_devmem.h"
 
+struct fic_rgb_ctx;
+
 namespace ficd {
 
 #define HIP_TRY(expr)                                                                              \
@@ -96,6 +98,10 @@ struct DecodeJob {
     int run(const char* who, const float* avg_in, float* avg_out, int* iters_out, int* seq_out, void* host_out,
             const std::function<int(int)>& iteration);
 };
+
+// The encode of a colour context under "search" = 1 (fic_capi_rgb_lsq.cpp); the caller holds the context's lock, has made its
+// device current and recorded the stream; `prev` is the stream of the context's encode before this one
+int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev);
 
 // what fic_release_cache() frees besides the idle contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp
@@ -175,6 +181,10 @@ struct fic_rgb_ctx {
     int opt_sweep = 0;               // 0 auto, 1 VALU sweeps, 2 matrix-core full search
     int opt_chunks = 0;              // pool chunks of the matrix-core sweep (0 = automatic)
     int last_sweep = 0;              // what the last encode ran: 1 / 2
+    FicLsqRgb lsq;                   // least-squares search ("search" = 1): byte stores, sums, per-chunk slots, the winners' E (on first use)
+    size_t lsq_slots = 0;            // slots per plane the slot stores have room for
+    int opt_search = 0, last_search = 0;
+    int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast
     bool have_input = false, encoded_any = false, have_collage = false;
     hipStream_t last_stream = nullptr;
     std::mutex mu;

@@ -190,6 +190,35 @@ int fic_launch_sweep_lsq_fast(const FicBuffers& b, const FicLsq& q, const FicGeo
                               hipStream_t s, unsigned long long* stats = nullptr);   // stats u64 [8]: "sweep_stats" counters or NULL
 int fic_launch_finalize_lsq(const FicBuffers& b, const FicOutputs& out, const FicLsq& q, int nslots, const FicGeom& g, int r_begin,
                             int r_count, hipStream_t s);
+// least-squares domain search of the joint-RGB path (fic_lsq_rgb.hip, option "search" = 1 of a colour context).
+// Its stores (Nr_pad = N_r rounded up to whole tiles of 64 range blocks):
+//   pool3   : u8    [planes][Nd_pad][3][n]               pool blocks, planar R, G, B (tail zeroed)
+//   pool_st : u32x8 [planes][Nd_pad]                     {S_d R, G, B, S_dd, V, bits of (float) sqrt((double) V), 0, 0}
+//   rng3    : u32   [planes][tiles][n_iso][3 DW][64]     lane-transposed isometry copies of the range blocks, planar
+//   rng_st  : u32x4 [planes][Nr_pad]                     {S_r R, G, B, S_rr}
+//   slotE   : i64   [planes][nslots][Nr_pad]             smallest E of one (pool chunk, isometry group) of the sweep, and in
+//   slotC   : u32   [planes][nslots][Nr_pad]             its candidate c = wloc * n_iso + k     (the generic sweep: one slot)
+//   E       : i64   [planes][Nr]                         the winner's E (fic_rgb_ctx_get_lsq_error_host)
+struct FicLsqRgb {
+    void* pool3 = nullptr;
+    void* pool_st = nullptr;
+    void* rng3 = nullptr;
+    void* rng_st = nullptr;
+    void* slotE = nullptr;
+    uint32_t* slotC = nullptr;
+    void* E = nullptr;
+    int Nr_pad = 0;
+};
+int fic_lsq_rgb_variant(int B, int n_iso, int* NC);     // 0 and the isometries per workgroup of k_sweep_lsq_rgb_fast, or -1: none
+int fic_lsq_rgb_slots(const FicGeom& g, int nchunks);   // slots of a fast sweep over nchunks pool chunks
+int fic_launch_lsq_rgb_prep(const int32_t* argb, const int32_t* scaled, const FicLsqRgb& q, const FicGeom& g, hipStream_t s);
+int fic_launch_sweep_lsq_rgb_generic(const FicLsqRgb& q, const FicGeom& g, hipStream_t s);
+int fic_launch_sweep_lsq_rgb_fast(const FicLsqRgb& q, const FicGeom& g, int chunk_len, int nchunks, hipStream_t s,
+                                  unsigned long long* stats = nullptr);   // stats u64 [8]: "sweep_stats" counters or NULL
+int fic_launch_finalize_lsq_rgb(const FicRgbOutputs& out, const FicLsqRgb& q, int nslots, const FicGeom& g, hipStream_t s);
+// stages of fic_launch_rgb_encode on their own, over g.planes images: scaleImageRGB and the collage of the rows in `out`
+int fic_launch_scale_rgb_planes(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s);
+int fic_launch_rgb_collage(const int32_t* scaled, const FicRgbOutputs& out, int32_t* collage, const FicGeom& g, hipStream_t s);
 int fic_launch_decode_iteration_rgb(int32_t* scaled, int32_t* image, const int32_t* qrows5, FicDecodeState* state,
                                     uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s,
                                     const int32_t* iso = nullptr);   // iso [N_r]: an n_iso = 8 codebook of a context, NULL: identity

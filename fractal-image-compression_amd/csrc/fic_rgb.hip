@@ -514,6 +514,21 @@ int fic_launch_rgb_encode(const FicRgbBuffers& b, const FicRgbOutputs& out, int3
     return 0;
 }
 
+// the first and the last stage of fic_launch_rgb_encode on their own (the least-squares search, fic_lsq_rgb.hip, runs between them)
+int fic_launch_scale_rgb_planes(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scale_rgb, dim3((g.Ws + 255) / 256, g.Hs, (unsigned)g.planes), dim3(256), 0, s, argb, scaled, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+int fic_launch_rgb_collage(const int32_t* scaled, const FicRgbOutputs& out, int32_t* collage, const FicGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_collage_rgb, dim3((g.W + 255) / 256, g.H, (unsigned)g.planes), dim3(256), 0, s, scaled, out, collage, g);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
 // scaleImageRGB (FC:901-962) of one image
 int fic_launch_scale_rgb(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s)
 {

@@ -480,6 +480,38 @@ FIC_API int fic_encode_gray_quadtree_lsq_u8(const uint8_t* gray, int w, int h, i
                                             int device, int32_t* leaves, int64_t capacity, int* n_leaves);
 FIC_API int fic_encode_gray_quadtree_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
                                               float threshold, int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+/* ---- least-squares domain search, joint RGB (an extension) --------------------------------------------
+ * The reference's colour criterion (getErrorVarianceCovarianceRGB, FractalCompression.java:760-808) works on the sum of the
+ * three channels, divides by varianceR + varianceG + mittelWertB, never sets the domain variance and clamps a after the winner
+ * is chosen.  This search minimises, in exact integers, the squared error over the three channels of the QUANTISED map -- one
+ * a, three b, as in the reference's row.  Same pool (createCodebuchRGB), window, isometries, streams and decoders.  Per channel
+ * ch in {R, G, B}: S_r, S_rr, S_d, S_dd, S_rd = sum r d_k (n = B*B);
+ *   C = sum_ch (n S_rd - S_r S_d),   V = sum_ch (n S_dd - S_d^2)
+ *   qa = 0 if V == 0, else clamp(floor((2000 C + V) / (2 V)), -1000, 1000)          (1000 C / V to nearest, then the clamp)
+ *   t_R, t_G = floor((2 (1000 S_r - qa S_d) + 10 n) / (20 n))                       (100 (mean_r - a mean_d) to nearest)
+ *   t_B      = floor((2 (1000 S_r - qa S_d) + 1000 n) / (2000 n))                   (the stream's bB is an integer)
+ *   u = {10 t_R, 10 t_G, 1000 t_B};   E = sum_ch sum_i (1000 r - qa d - u_ch)^2     (int64, >= 0, < 2^50)
+ * The winner is the smallest E; candidates in the order c = idx_local * n_iso + k, strict '<'.  Outputs: idx_local, iso;
+ * qrows5 = {idx_local, 1000 qa, 1000 t_R, 1000 t_G, t_B}, which every writer and decoder of colour rows takes unchanged;
+ * a, bR, bG, bB what decodeRGB makes of that row ((float) q1 / 1e6f, (float) q2 / 1e5f, (float) q3 / 1e5f, (float) q4), so the
+ * collage and the context's decode need no change; E [planes][N_r] through fic_rgb_ctx_get_lsq_error_host (FIC_E_STATE unless
+ * the last encode was a least-squares one).
+ * fic_rgb_ctx_set_option(ctx, "search", 0 | 1) switches a colour context.  Under "search" = 1, "sweep" means 0 (auto:
+ * k_sweep_lsq_rgb_fast for full search at B <= 8, else k_sweep_lsq_rgb_generic), 1 (generic) or 2 (fast; an encode of any other
+ * geometry returns FIC_E_ARGUMENT); FIC_RGB_SWEEP does not apply.  "chunks" (pool chunks of the fast sweep, 0 = auto), batched
+ * planes, fic_rgb_ctx_last_kernel, the collage and fic_rgb_ctx_decode_host / _zoom_host work as before; "sweep_stats" counts as
+ * under the grey search (fic_ctx_sweep_stats).  fic_encode_rgb_lsq_argb takes the arguments of fic_encode_rgb_iso_argb plus
+ * E [N_r] (may be NULL) and runs over the same cached contexts, which go back to the cache in the reference's mode.  The two
+ * quadtree entries have the signatures of fic_encode_rgb_quadtree_argb (tag 3) and fic_encode_rgb_quadtree_iso_argb (tag 6):
+ * the per-level codebooks come from this search, everything after them is unchanged. */
+FIC_API int fic_rgb_ctx_get_lsq_error_host(fic_rgb_ctx* ctx, int64_t* E);
+FIC_API int fic_encode_rgb_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
+                                    float* a, float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb,
+                                    int64_t* E);
+FIC_API int fic_encode_rgb_quadtree_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, float threshold,
+                                             int device, int32_t* leaves, int64_t capacity, int* n_leaves);
+FIC_API int fic_encode_rgb_quadtree_iso_lsq_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso,
+                                                 float threshold, int device, int32_t* leaves, int64_t capacity, int* n_leaves);
 /* Sum of sweep-kernel durations (ms) and launch count since the last reset ("time_sweep" = 1).
  * Synchronises the events.  reset != 0 clears the accumulators afterwards. */
 FIC_API int fic_ctx_sweep_time(fic_ctx* ctx, double* total_ms, int* launches, int reset);

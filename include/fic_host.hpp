@@ -163,6 +163,26 @@ public:
                                        idx.data(), a.data(), b.data(), iso ? iso->data() : nullptr, qrows.data(), E ? E->data() : nullptr));
     }
 
+    // The one-shot least-squares search of a colour image (an extension, fic_encode_rgb_lsq_argb in fic.h; `isometries` is 1 or
+    // 8): the rows {idx_local, 1000 qa, 1000 t_R, 1000 t_G, t_B} of every range block into `qrows5` [N_r * 5], ready for
+    // fic_write_run_rgb / fic_write_run_rgb_iso, the winning isometries into `iso` [N_r] and the winners' errors E -- 10^6 times
+    // the squared error of the quantised map over the three channels -- into `E` [N_r]; `iso` and `E` may be null.
+    static void encodeRGBLsq(const RasterImage& input, std::vector<int32_t>& qrows5, std::vector<int32_t>* iso = nullptr,
+                             std::vector<int64_t>* E = nullptr)
+    {
+        int Rw = 0, Rh = 0;
+        check(fic_geometry(input.width, input.height, blockgroesse, &Rw, &Rh, nullptr, nullptr));
+        const int nr = Rw * Rh;
+        std::vector<int32_t> idx(nr);
+        std::vector<float> a(nr), bR(nr), bG(nr), bB(nr);
+        qrows5.resize((size_t)nr * 5);
+        if (iso) iso->resize(nr);
+        if (E) E->resize(nr);
+        check(fic_encode_rgb_lsq_argb(input.argb.data(), input.width, input.height, blockgroesse, widthKernel, isometries, device,
+                                      idx.data(), a.data(), bR.data(), bG.data(), bB.data(), iso ? iso->data() : nullptr, qrows5.data(),
+                                      nullptr, E ? E->data() : nullptr));
+    }
+
     // FractalCompression.java:230-246 (grey branch): big-endian header + rows.
     static void writeData(std::ostream& out, const std::vector<int32_t>& qrows, int width, int height)
     {
