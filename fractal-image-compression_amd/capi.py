@@ -424,7 +424,8 @@ class RgbEncoder:
 
     def set_option(self, name, value):
         """"sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search.  "search": 0 / "reference" or 1 / "lsq" (least
-        squares; "sweep" then means 0 auto, 1 generic, 2 fast)."""
+        squares; "sweep" then means 0 auto, 1 generic, 2 fast).  "lsq_tau_widen": 0 (off) or 8..24 --
+        diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value)."""
         if name == "search":
             value = search_id(value)
         check(lib().fic_rgb_ctx_set_option(self._h, name.encode(), int(value)))

@@ -422,7 +422,7 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     if (rc) return rc;
     if (kind == 1) {
         if (fic_launch_sweep_lsq_generic(c->b, c->lsq, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_sweep_lsq_generic launch failed");
-    } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats)) {
+    } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_fast launch failed");
     }
     rc = time_end(c, s);
@@ -777,6 +777,9 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
     } else if (!strcmp(name, "q_eshift")) {            // diagnostic: k_sweep_q's E_r times 2^-value (> 0: below the derivation, WRONG codebooks)
         if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "q_eshift must be in -12..4");
         c->g.q_eshift = value;
+    } else if (!strcmp(name, "lsq_tau_widen")) {       // diagnostic: k_sweep_lsq_fast's tau times 1 + 2^-value (> 0: above the derivation, WRONG codebooks)
+        if (value != 0 && (value < 8 || value > 24)) return fail(FIC_E_ARGUMENT, "lsq_tau_widen must be 0 (off) or in 8..24");
+        c->opt_lsq_widen = value;
     } else if (!strcmp(name, "q_noflag")) {            // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
         c->opt_noflag = value ? 1 : 0;
     } else if (!strcmp(name, "time_sweep")) {

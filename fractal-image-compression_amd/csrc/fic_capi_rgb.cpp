@@ -226,6 +226,12 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         c->g.q_eshift = value;
         return FIC_OK;
     }
+    if (!strcmp(name, "lsq_tau_widen")) {              // diagnostic: k_sweep_lsq_rgb_fast's tau times 1 + 2^-value (> 0: WRONG codebooks)
+        if (value != 0 && (value < 8 || value > 24))
+            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_tau_widen must be 0 (off) or in 8..24");
+        c->opt_lsq_widen = value;
+        return FIC_OK;
+    }
     if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
         HIP_TRY(hipSetDevice(c->device));
         return sweep_stats_option(c->mem, c->q.stats, value, c->last_stream);

@@ -57,7 +57,7 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     if (fic_launch_lsq_rgb_prep(c->argb, c->scaled, q, g, s)) return fail(FIC_E_HIP, "k_lsq_rgb_prep launch failed");
     if (kind == 1) {
         if (fic_launch_sweep_lsq_rgb_generic(q, g, s)) return fail(FIC_E_HIP, "k_sweep_lsq_rgb_generic launch failed");
-    } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->q.stats)) {
+    } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->q.stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_rgb_fast launch failed");
     }
     if (fic_launch_finalize_lsq_rgb(o, q, nslots, g, s)) return fail(FIC_E_HIP, "k_finalize_lsq_rgb launch failed");

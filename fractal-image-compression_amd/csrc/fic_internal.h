@@ -141,6 +141,7 @@ struct fic_ctx {
     FicLsq lsq{};                    // least-squares search ("search" = 1): statistics, per-chunk slots, the winners' E (on first use)
     size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
+    int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
     bool have_input = false;
     bool encoded_any = false;
     hipStream_t last_stream = nullptr;
@@ -184,6 +185,7 @@ struct fic_rgb_ctx {
     FicLsqRgb lsq;                   // least-squares search ("search" = 1): byte stores, sums, per-chunk slots, the winners' E (on first use)
     size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
+    int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
     int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast
     bool have_input = false, encoded_any = false, have_collage = false;
     hipStream_t last_stream = nullptr;

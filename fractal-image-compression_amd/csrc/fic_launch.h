@@ -170,6 +170,11 @@ int fic_launch_sweep_q(const FicBuffers& b, const void* poolQ, const void* dflat
                        void* theta_g, const FicGeom& g, int ct_begin, int ct_end, int ndtiles, int ndtiles_alloc,
                        int nct_alloc, int tiles_per_chunk, int nchunks, hipStream_t s, unsigned long long* stats = nullptr, int dbg_noflag = 0,
                        const FicOutputs* fin_out = nullptr, unsigned int* fin_count = nullptr, int r_begin = 0, int r_count = 0);
+// The prune of the two fast sweeps skips a pair when |C'| <= (int) fl(tau * s32'); tau carries the safety factor 1 - 2^-18 that
+// the derivation in fic_lsq.hip needs.  Option "lsq_tau_widen" = k in 8..24 multiplies tau by 1 + 2^-k after it: diagnostic,
+// > 0 gives WRONG codebooks (the bound tests use it to show that their inputs catch a bound that is too wide); 0: times 1.
+#define FIC_LSQ_TAU_SAFETY 0.99999618530273437500f
+inline float fic_lsq_tau_widen(int k) { return k > 0 ? 1.0f + (float)(1.0 / (double)(1ll << k)) : 1.0f; }
 // least-squares domain search (fic_lsq.hip, option "search" = 1).  Its stores, beside FicBuffers:
 //   pool  : u32x4 [planes][Nd_pad]          {S_d, S_dd, V = n S_dd - S_d^2, bits of (float) sqrt((double) V)}
 //   rng   : u32x2 [planes][Nr_pad]          {S_r, S_rr}
@@ -187,7 +192,8 @@ int fic_lsq_slots(const FicGeom& g, int nchunks);   // slots of a fast sweep ove
 int fic_launch_lsq_stat(const FicBuffers& b, const FicLsq& q, const FicGeom& g, hipStream_t s);
 int fic_launch_sweep_lsq_generic(const FicBuffers& b, const FicLsq& q, const FicGeom& g, int r_begin, int r_count, hipStream_t s);
 int fic_launch_sweep_lsq_fast(const FicBuffers& b, const FicLsq& q, const FicGeom& g, int tile0, int ntiles, int chunk_len, int nchunks,
-                              hipStream_t s, unsigned long long* stats = nullptr);   // stats u64 [8]: "sweep_stats" counters or NULL
+                              hipStream_t s, unsigned long long* stats = nullptr,    // stats u64 [8]: "sweep_stats" counters or NULL
+                              int tau_widen = 0);                                     // option "lsq_tau_widen"
 int fic_launch_finalize_lsq(const FicBuffers& b, const FicOutputs& out, const FicLsq& q, int nslots, const FicGeom& g, int r_begin,
                             int r_count, hipStream_t s);
 // least-squares domain search of the joint-RGB path (fic_lsq_rgb.hip, option "search" = 1 of a colour context).
@@ -214,7 +220,8 @@ int fic_lsq_rgb_slots(const FicGeom& g, int nchunks);   // slots of a fast sweep
 int fic_launch_lsq_rgb_prep(const int32_t* argb, const int32_t* scaled, const FicLsqRgb& q, const FicGeom& g, hipStream_t s);
 int fic_launch_sweep_lsq_rgb_generic(const FicLsqRgb& q, const FicGeom& g, hipStream_t s);
 int fic_launch_sweep_lsq_rgb_fast(const FicLsqRgb& q, const FicGeom& g, int chunk_len, int nchunks, hipStream_t s,
-                                  unsigned long long* stats = nullptr);   // stats u64 [8]: "sweep_stats" counters or NULL
+                                  unsigned long long* stats = nullptr,    // stats u64 [8]: "sweep_stats" counters or NULL
+                                  int tau_widen = 0);                      // option "lsq_tau_widen"
 int fic_launch_finalize_lsq_rgb(const FicRgbOutputs& out, const FicLsqRgb& q, int nslots, const FicGeom& g, hipStream_t s);
 // stages of fic_launch_rgb_encode on their own, over g.planes images: scaleImageRGB and the collage of the rows in `out`
 int fic_launch_scale_rgb_planes(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s);

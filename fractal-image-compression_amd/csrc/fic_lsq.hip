@@ -178,6 +178,8 @@ __global__ __launch_bounds__(256) void k_sweep_lsq_generic(const uint32_t* __res
 // li <= sqrt(T V') (1 - 2^-18) (1 + 2^-21) < sqrt(T V'), and C' is an integer compared exactly (tau * s32' < 2^30.1: the
 // conversion to int truncates a non-negative float, never rounds up).  tau = -1 stands for T < 0 and "nothing evaluated yet":
 // li = -1 flags every pair, so the first block of a chunk is always evaluated.  Only flagged pairs run the 64-bit epilogue.
+// The factor 1 - 2^-18 is the kernel argument tau_safety; tau_widen is 1, or 1 + 2^-k under the diagnostic option
+// "lsq_tau_widen" = k, which puts li ABOVE the derivation (wrong codebooks) so that tests can show their inputs notice.
 //
 // Chunks and isometry groups do not share a key: E needs up to 42 bits beside a 25-bit candidate.  Every (chunk, group)
 // writes its lane minimum to a slot of its own; k_finalize_lsq takes the lexicographic (E, candidate) minimum over the slots,
@@ -196,6 +198,8 @@ struct LsqSweepArgs {
     int planes;
     unsigned long long* stats; // NULL, or counters ("sweep_stats"): {(wave, pool block) visits, visits that ran the exact epilogue,
                                //  pairs evaluated exactly, waves}
+    float tau_safety;          // the safety factor of tau, 1 - 2^-18 (FIC_LSQ_TAU_SAFETY)
+    float tau_widen;           // 1, or 1 + 2^-k under the option "lsq_tau_widen" = k: diagnostic, > 0 gives WRONG codebooks
 };
 
 template <int DW, int NR, int NC>
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(256) void k_sweep_lsq_fast(LsqSweepArgs A)
             best_E[rs] = f.E;
             best_cand[rs] = (uint32_t)d * (uint32_t)A.n_iso + (uint32_t)(kbase + k);
             const long long Ti = 10000ll * (long long)R[rs] - (f.E << A.lgn);        // 10^4 T, exact
-            tau[rs] = Ti < 0 ? -1.0f : __fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.01f), 0.99999618530273437500f);
+            tau[rs] = Ti < 0 ? -1.0f : __fmul_rn(__fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.01f), A.tau_safety), A.tau_widen);
         }
     };
     auto end_domain = [&](int d, const u32x4& s) {     // s = {S_d, S_dd, V, bits of s32}
@@ -468,10 +472,12 @@ int fic_launch_sweep_lsq_generic(const FicBuffers& b, const FicLsq& q, const Fic
 
 // The instantiations are k_sweep_fast's (fic_fast_variant, fic_device.h).
 int fic_launch_sweep_lsq_fast(const FicBuffers& b, const FicLsq& q, const FicGeom& g, int tile0, int ntiles, int chunk_len, int nchunks,
-                              hipStream_t s, unsigned long long* stats)
+                              hipStream_t s, unsigned long long* stats, int tau_widen)
 {
     LsqSweepArgs A;
     A.stats = stats;
+    A.tau_safety = FIC_LSQ_TAU_SAFETY;
+    A.tau_widen = fic_lsq_tau_widen(tau_widen);
     A.pool_pix = (const uint32_t*)b.pool_pix;
     A.lsq_pool = (const u32x4*)q.pool;
     A.rng_pix = b.rng_pix;

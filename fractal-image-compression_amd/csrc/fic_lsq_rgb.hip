@@ -181,6 +181,7 @@ __global__ __launch_bounds__(256) void k_sweep_lsq_rgb_generic(const uint32_t* _
 // int without overflow (truncation of a non-negative float never rounds up).  Neither holds at B = 16 (|C| reaches 3.2e9,
 // V needs the unsigned 32 bits): B = 16 runs through the generic kernel.  tau = -1 stands for T < 0 and "nothing evaluated
 // yet": li = -1 flags every pair.  Only flagged pairs run the 64-bit epilogue.
+// tau_safety and tau_widen (option "lsq_tau_widen": diagnostic, > 0 gives WRONG codebooks) are k_sweep_lsq_fast's.
 //
 // Every (pool chunk, isometry group) writes its lane minimum to a slot of its own; k_finalize_lsq_rgb takes the lexicographic
 // (E, candidate) minimum over the slots, which does not depend on how the pool was cut.
@@ -197,6 +198,8 @@ struct LsqRgbSweepArgs {
     int chunk_len, nchunks;    // pool chunk length, number of chunks (none of them empty)
     unsigned long long* stats; // NULL, or counters ("sweep_stats"): {(wave, pool block) visits, visits that ran the exact epilogue,
                                //  pairs evaluated exactly, waves}
+    float tau_safety;          // the safety factor of tau, 1 - 2^-18 (FIC_LSQ_TAU_SAFETY)
+    float tau_widen;           // 1, or 1 + 2^-k under the option "lsq_tau_widen" = k: diagnostic, > 0 gives WRONG codebooks
 };
 
 template <int DW3, int NC>
@@ -277,7 +280,7 @@ __global__ __launch_bounds__(256) void k_sweep_lsq_rgb_fast(LsqRgbSweepArgs A)
                         best_E = f.E;
                         best_cand = (uint32_t)d * (uint32_t)A.n_iso + (uint32_t)(kbase + k);
                         const long long Ti = 1000000ll * (long long)R - (f.E << A.lgn);          // 10^6 T, exact
-                        tau = Ti < 0 ? -1.0f : __fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.001f), 0.99999618530273437500f);
+                        tau = Ti < 0 ? -1.0f : __fmul_rn(__fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.001f), A.tau_safety), A.tau_widen);
                     }
                 }
             }
@@ -390,7 +393,7 @@ int fic_launch_sweep_lsq_rgb_generic(const FicLsqRgb& q, const FicGeom& g, hipSt
 }
 
 int fic_launch_sweep_lsq_rgb_fast(const FicLsqRgb& q, const FicGeom& g, int chunk_len, int nchunks, hipStream_t s,
-                                  unsigned long long* stats)
+                                  unsigned long long* stats, int tau_widen)
 {
     int NC;
     if (fic_lsq_rgb_variant(g.B, g.n_iso, &NC) || !g.full) return -1;
@@ -407,6 +410,8 @@ int fic_launch_sweep_lsq_rgb_fast(const FicLsqRgb& q, const FicGeom& g, int chun
     A.Nd = g.Nd; A.Nd_pad = g.Nd_pad; A.Nr = g.Nr; A.Nr_pad = q.Nr_pad; A.n_iso = g.n_iso; A.lgn = g.lgn;
     A.ntiles = q.Nr_pad / 64; A.chunk_len = chunk_len; A.nchunks = nchunks;
     A.stats = stats;
+    A.tau_safety = FIC_LSQ_TAU_SAFETY;
+    A.tau_widen = fic_lsq_tau_widen(tau_widen);
     dim3 grid((unsigned)((A.ntiles + 3) / 4), (unsigned)nslots, (unsigned)g.planes);
     dim3 block(256);
     if (g.B == 4 && g.n_iso == 1) hipLaunchKernelGGL((k_sweep_lsq_rgb_fast<12, 1>), grid, block, 0, s, A);

@@ -112,7 +112,8 @@ class Encoder:
 
     # ---- compute ---------------------------------------------------------------------------
     def set_option(self, name, value):
-        """fic_ctx_set_option.  "search" also takes "reference" / "lsq" (least squares)."""
+        """fic_ctx_set_option.  "search" also takes "reference" / "lsq" (least squares).  "lsq_tau_widen": 0
+        (off) or 8..24 -- diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value)."""
         if name == "search":
             value = capi.search_id(value)
         capi.check(capi.lib().fic_ctx_set_option(self._h, name.encode(), int(value)))

@@ -447,6 +447,10 @@ FIC_API int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int
  *                 FIC_E_ARGUMENT, whichever of the two options is set last.  "chunks", range spans, batched planes,
  *                 "time_sweep" and fic_ctx_last_kernel work as with "search" = 0, and so do fic_ctx_collage_host and
  *                 fic_ctx_decode_host / fic_ctx_decode_zoom_host: a and b are the decoder's own values then.
+ *   "lsq_tau_widen"  diagnostic, 0 (off, the default) or 8..24: k_sweep_lsq_fast multiplies the tau of its prune bound by
+ *                 1 + 2^-value after the safety factor, above what the derivation in fic_lsq.hip allows: > 0 gives WRONG
+ *                 codebooks (the tests show that they are caught).  Not for production use; the contexts behind the one-shot
+ *                 entries never carry it.  fic_rgb_ctx_set_option takes it too (k_sweep_lsq_rgb_fast).
  *   "chunks"      domain-pool chunks per range tile for the fast kernel (0 = auto)
  *   "time_sweep"  1: bracket every sweep launch with hipEvents on its stream */
 FIC_API int fic_ctx_set_option(fic_ctx* ctx, const char* name, int value);

@@ -2,7 +2,8 @@
 // every kernel of the joint-RGB least-squares search calls: on random pairs of blocks its qa, t and E against the definition in
 // plain 64-bit integers (mathematical floor) and E against the direct sum over the pixels.  The cases cover V == 0, clamped qa
 // on both sides, negative numerators that are no multiple of the divisor (floor against truncation) and negative t in every
-// channel.  Built by tests/test_rgb_lsq_model.py with the host compiler and its sanitizers; never runs on a GPU.
+// channel, and blocks of 0 and 255 only ("halves"), where at n = 256 V passes 2^31 and C passes 2^31 on either side: the values
+// the 64-bit C and the unsigned 32-bit V of the B = 16 route exist for.  Built by tests/test_rgb_lsq_model.py with the host compiler and its sanitizers; never runs on a GPU.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,15 +29,24 @@ static uint32_t rnd()
 int main()
 {
     long long failures = 0, pairs = 0, n_v0 = 0, n_hi = 0, n_lo = 0, n_negnum = 0, n_negt[3] = {0, 0, 0};
+    long long n_bigv = 0, n_bigc = 0, n_negbigc = 0;
     static uint8_t r[3][256], d[3][256];
     for (int lgn = 4; lgn <= 8; lgn += 2) {
         const int n = 1 << lgn;
-        for (int it = 0; it < 6000; it++) {
-            const int kind = it % 6;
+        for (int it = 0; it < 7200; it++) {
+            const int kind = it < 6000 ? it % 6 : 6;
+            // halves: d is 0 or 255 per pixel, the same in the three channels in every other case; r is d with one pixel in 16
+            // flipped, 255 - d with such flips (inverted: a quarter of the cases), independent of d, or d itself
+            const int equal = it & 1, mode = (it >> 1) & 3;
             for (int ch = 0; ch < 3; ch++) {
                 const uint8_t flat = (uint8_t)rnd();
                 for (int i = 0; i < n; i++) {
                     uint8_t dv = (uint8_t)rnd(), rv = (uint8_t)rnd();
+                    if (kind == 6) {
+                        dv = (equal && ch > 0) ? d[0][i] : ((rnd() & 1) ? 255 : 0);
+                        const bool flip = mode < 2 && rnd() % 16 == 0;
+                        rv = mode == 2 ? ((rnd() & 1) ? 255 : 0) : (uint8_t)((mode == 1) != flip ? 255 - dv : dv);
+                    }
                     if (kind == 1) dv = flat;                                              // flat domain: V == 0 when all three are
                     if (kind == 2) { dv = (uint8_t)(100 + rnd() % 4); rv = (rnd() & 1) ? 255 : 0; }          // low contrast: clamps
                     if (kind == 3) rv = (uint8_t)(255 - dv / 2);                           // negative slope
@@ -58,6 +68,9 @@ int main()
                 C += n * srd - sr * sd;
                 V += n * sdd - sd * sd;
             }
+            if (V >= (1ll << 31)) n_bigv++;
+            if (C >= (1ll << 31)) n_bigc++;
+            if (C <= -(1ll << 31)) n_negbigc++;
             const LsqRgbFit f = lsq_fit_rgb(lgn, S_r, S_rr, S_d, S_dd, S_rd, C, (uint32_t)V);
             // the definition
             long long qa = 0;
@@ -87,9 +100,11 @@ int main()
             }
         }
     }
-    printf("pairs %lld: V == 0 %lld, qa = 1000 %lld, qa = -1000 %lld, negative numerators off the grid %lld, negative t %lld %lld %lld\n", pairs,
-           n_v0, n_hi, n_lo, n_negnum, n_negt[0], n_negt[1], n_negt[2]);
-    if (n_v0 < 100 || n_hi < 100 || n_lo < 100 || n_negnum < 100 || n_negt[0] < 100 || n_negt[1] < 100 || n_negt[2] < 100) {
+    printf("pairs %lld: V == 0 %lld, qa = 1000 %lld, qa = -1000 %lld, negative numerators off the grid %lld, negative t %lld %lld %lld, "
+           "V >= 2^31 %lld, C >= 2^31 %lld, C <= -2^31 %lld\n", pairs, n_v0, n_hi, n_lo, n_negnum, n_negt[0], n_negt[1], n_negt[2], n_bigv,
+           n_bigc, n_negbigc);
+    if (n_v0 < 100 || n_hi < 100 || n_lo < 100 || n_negnum < 100 || n_negt[0] < 100 || n_negt[1] < 100 || n_negt[2] < 100 || n_bigv < 100 ||
+        n_bigc < 100 || n_negbigc < 100) {
         printf("a case is not covered\n");
         failures++;
     }

@@ -65,8 +65,9 @@ def test_closed_form_equals_direct_sum():
 
 
 def test_kernel_fit_against_plain_int64_host_program(tmp_path):
-    """lsq_fit_rgb (csrc/fic_lsq_rgb_fit.h), the fit every kernel of the search calls, as a stand-alone host program: 18 000
-    pairs against the definition in plain 64-bit integers and the direct sum, built with AddressSanitizer and
+    """lsq_fit_rgb (csrc/fic_lsq_rgb_fit.h), the fit every kernel of the search calls, as a stand-alone host program: 21 600
+    pairs -- among them blocks of 0 and 255 whose V and |C| pass 2^31 at B = 16 -- against the definition in plain 64-bit
+    integers and the direct sum, built with AddressSanitizer and
     UndefinedBehaviorSanitizer where the host compiler has them; without them otherwise, and the test prints which of the two
     ran, so a pass on a machine without the runtimes is not read as a sanitizer pass.  Nothing of the program is loaded
     into this process, and it never runs on a GPU."""
