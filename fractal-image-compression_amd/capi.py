@@ -193,6 +193,20 @@ def ptr(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
+def aligned_tensor(t, align):
+    """`t` itself where its address is a multiple of `align` bytes (the alignment contract of fic_ctx_set_gray_device /
+    fic_rgb_ctx_set_argb_device), else a clone of it in a fresh allocation -- torch's are aligned to 256 bytes and more.  The
+    clone is finished when this returns: the encode may run on any stream."""
+    if t.data_ptr() % align == 0:
+        return t
+    import torch
+    c = t.clone(memory_format=torch.contiguous_format)
+    torch.cuda.current_stream(t.device).synchronize()
+    if c.data_ptr() % align != 0:
+        raise FicError(-3, f"could not obtain a device allocation aligned to {align} bytes")
+    return c
+
+
 def geometry(w, h, B):
     v = [C.c_int() for _ in range(4)]
     check(lib().fic_geometry(w, h, B, *[C.byref(x) for x in v]))
@@ -401,13 +415,15 @@ class RgbEncoder:
             pass
 
     def set_argb(self, argb):
-        """int32 [planes, H*W] numpy array (copied) or a torch CUDA int32 tensor of that many elements (used in place)."""
+        """int32 [planes, H*W] numpy array (copied) or a torch CUDA int32 tensor of that many elements (used in place and read
+        at encode time; one at an address that is no multiple of 4 is cloned here instead, as Encoder.set_gray does)."""
         n = self.planes * self.width * self.height
         if hasattr(argb, "data_ptr"):
             if not argb.is_cuda or argb.element_size() != 4 or not argb.is_contiguous() or argb.numel() != n:
                 raise FicError(-3, "device input must be a contiguous int32 CUDA tensor [planes,H,W]")
-            self._keep = argb
+            argb = aligned_tensor(argb, 4)
             check(lib().fic_rgb_ctx_set_argb_device(self._h, C.c_void_p(argb.data_ptr())))
+            self._keep = argb
         else:
             a = np.ascontiguousarray(argb, np.int32)
             if a.size != n:

@@ -82,6 +82,19 @@ int flush_events(fic_ctx* c)
 
 // ---- sweep orchestration helpers (used by fic_ctx_encode) ------------------------------------------------------
 
+// Stream rule of the handle API (include/fic.h): an encode on stream `s` takes over the context.  On the stream of the encode
+// before it this is one pointer comparison; on another one the host waits for the earlier encode first, since stream order no
+// longer keeps the two apart.  (The multi-device entry sets last_stream itself, after its own wait: fic_capi_multi.cpp.)
+int order_after_last_encode(fic_ctx* c, hipStream_t s)
+{
+    if (s != c->last_stream) {
+        if (c->stream_used) HIP_TRY(hipStreamSynchronize(c->last_stream));
+        c->last_stream = s;
+    }
+    c->stream_used = true;
+    return FIC_OK;
+}
+
 // "time_sweep": bracket the sweep launch with events on its stream; durations are read later by flush_events.
 int time_begin(fic_ctx* c, hipStream_t s)
 {
@@ -567,6 +580,10 @@ int fic_ctx_set_argb_host(fic_ctx* c, const int32_t* argb)
 int fic_ctx_set_gray_device(fic_ctx* c, const void* dev_gray)
 {
     if (!c || !dev_gray) return fail(FIC_E_ARGUMENT, "fic_ctx_set_gray_device: null argument");
+    // the range preps read the caller's bytes in words of up to 8 bytes (k_prep_q8 / k_range_q8: uint2 rows at B = 8); plane
+    // and row offsets keep the base's alignment (W, H multiples of B >= 4; W a multiple of 8 wherever the 8-byte load runs)
+    if ((uintptr_t)dev_gray % 8 != 0)
+        return fail(FIC_E_ARGUMENT, "fic_ctx_set_gray_device: alignment: address %p is not a multiple of 8 bytes (the input in force stays)", dev_gray);
     std::lock_guard<std::mutex> lk(c->mu);
     c->b.gray = (uint8_t*)dev_gray;
     c->have_input = true;
@@ -584,7 +601,8 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
         return fail(FIC_E_ARGUMENT, "fic_ctx_encode: range span [%d,%d) outside 0..%d", range_begin, range_begin + range_count, g.Nr);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
-    c->last_stream = s;
+    // another stream than the last encode's: scratch stores, keys and outputs are shared, so the new work starts after the old
+    if (int rc = order_after_last_encode(c, s)) return rc;
     if (range_count == 0) return FIC_OK;
     if (c->opt_search == 1) return lsq_encode(c, range_begin, range_count, s);
 
@@ -680,6 +698,7 @@ int fic_ctx_sync(fic_ctx* c)
     if (!c) return fail(FIC_E_ARGUMENT, "fic_ctx_sync: null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
+    c->stream_used = false;                            // nothing pending: the caller may destroy that stream, the next encode waits for nothing
     return FIC_OK;
 }
 

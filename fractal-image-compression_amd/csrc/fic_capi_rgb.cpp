@@ -157,6 +157,8 @@ int fic_rgb_ctx_set_argb_host(fic_rgb_ctx* c, const int32_t* argb)
 int fic_rgb_ctx_set_argb_device(fic_rgb_ctx* c, const void* dev_argb)
 {
     if (!c || !dev_argb) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_argb_device: null argument");
+    if ((uintptr_t)dev_argb % 4 != 0)                  // every kernel loads the pixels as int32_t, none wider
+        return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_argb_device: alignment: address %p is not a multiple of 4 bytes (the input in force stays)", dev_argb);
     std::lock_guard<std::mutex> lk(c->mu);
     c->argb = (const int32_t*)dev_argb;
     c->have_input = true;
@@ -171,8 +173,12 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     const hipStream_t prev = c->last_stream;
+    const bool switched = c->stream_used && s != prev;    // an earlier encode, issued on another stream
     c->last_stream = s;
-    if (c->opt_search == 1) return rgb_lsq_encode(c, with_collage, s, prev);      // least squares
+    c->stream_used = true;
+    if (c->opt_search == 1) return rgb_lsq_encode(c, with_collage, s, prev, switched);      // least squares
+    // scaled image, pool, keys and outputs are shared: the new work starts after the old
+    if (switched) HIP_TRY(hipStreamSynchronize(prev));
     const FicGeom& g = c->g;
     // Full search: the matrix-core sweep where it pays (its prep costs ~50 us; the VALU sweep does ~1e11 pairs/s), or where
     // the VALU full-search kernel does not exist (B = 16).  FIC_RGB_SWEEP=1|2 / option "sweep" override.
@@ -302,6 +308,7 @@ int fic_rgb_ctx_sync(fic_rgb_ctx* c)
     if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sync: null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
+    c->stream_used = false;                            // nothing pending: the caller may destroy that stream, the next encode waits for nothing
     return FIC_OK;
 }
 

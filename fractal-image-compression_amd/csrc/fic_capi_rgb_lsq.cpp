@@ -7,8 +7,10 @@ using namespace ficd;
 
 // scaleImageRGB as for the reference's search, then the planar byte stores and sums, k_sweep_lsq_rgb_generic (windows, B = 16,
 // "sweep" = 1) or k_sweep_lsq_rgb_fast (full search at B <= 8), k_finalize_lsq_rgb and the reference's collage of the rows.
-int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev)
+int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev, bool switched)
 {
+    // the byte stores, sums, slots and outputs are shared with the earlier encode: the new work starts after it
+    if (switched) HIP_TRY(hipStreamSynchronize(prev));
     const FicGeom& g = c->g;
     int NC = 1;
     const bool fast_ok = g.full && fic_lsq_rgb_variant(g.B, g.n_iso, &NC) == 0;

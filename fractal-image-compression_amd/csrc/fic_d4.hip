@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void k_range_d4(const uint8_t* __restrict__ gra
         for (int y = 0; y < B; y++)
 #pragma unroll
             for (int x4 = 0; x4 < B / 4; x4++) {
-                const uint32_t q = *(const uint32_t*)(blk + (size_t)y * g.W + 4 * x4);   // W, B multiples of 4: aligned
+                const uint32_t q = *(const uint32_t*)(blk + (size_t)y * g.W + 4 * x4);   // W, B multiples of 4, base a multiple of 8 (fic_ctx_set_gray_device): aligned
 #pragma unroll
                 for (int t = 0; t < 4; t++) px[y * B + 4 * x4 + t] = (int)((q >> (8 * t)) & 255u);
             }

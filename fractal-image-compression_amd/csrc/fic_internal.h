@@ -100,8 +100,9 @@ struct DecodeJob {
 };
 
 // The encode of a colour context under "search" = 1 (fic_capi_rgb_lsq.cpp); the caller holds the context's lock, has made its
-// device current and recorded the stream; `prev` is the stream of the context's encode before this one
-int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev);
+// device current and recorded the stream; `prev` is the stream of the context's encode before this one, `switched` says that
+// there was one and that it is another stream than `s`
+int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev, bool switched);
 
 // what fic_release_cache() frees besides the idle contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp
@@ -145,6 +146,7 @@ struct fic_ctx {
     bool have_input = false;
     bool encoded_any = false;
     hipStream_t last_stream = nullptr;
+    bool stream_used = false;        // an encode was issued on last_stream (fic_ctx_encode orders a stream switch after it)
     hipStream_t own_stream = nullptr; // non-blocking stream of the multi-device entry (created on demand)
     int opt_sweep = 0, opt_chunks = 0, opt_time = 0, opt_noflag = 0;
     int last_chunks = 0, last_kind = 0, last_fused = 0, last_tiles_per_chunk = 0;
@@ -189,6 +191,7 @@ struct fic_rgb_ctx {
     int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast
     bool have_input = false, encoded_any = false, have_collage = false;
     hipStream_t last_stream = nullptr;
+    bool stream_used = false;        // an encode was issued on last_stream (fic_rgb_ctx_encode orders a stream switch after it)
     std::mutex mu;
 };
 

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_range_copies(const uint8_t* __restrict_
         if (j < g.Nr) {                                        // tile padding stays zero (never written back)
             const int pos = wd * 4;
             const uint8_t* p = img + (size_t)((j / g.Rw) * B + pos / B) * g.W + (j % g.Rw) * B + pos % B;
-            v = *(const uint32_t*)p;                           // B, W multiples of 4: aligned
+            v = *(const uint32_t*)p;                           // B, W multiples of 4, base a multiple of 8 (fic_ctx_set_gray_device): aligned
         }
         *(uint32_t*)&blk[lane * stride + wd * 4] = v;
     }

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_range_q(const uint8_t* __restrict__ gra
         if (j < g.Nr) {
             const int pos = wd * 4;
             const uint8_t* p = img + (size_t)((j / g.Rw) * B + (pos >> lgB)) * g.W + (j % g.Rw) * B + (pos & (B - 1));
-            v = *(const uint32_t*)p;                           // B, W multiples of 4: aligned
+            v = *(const uint32_t*)p;                           // B, W multiples of 4, base a multiple of 8 (fic_ctx_set_gray_device): aligned
         }
         *(uint32_t*)&blk[l * stride + wd * 4] = v;
     }
@@ -484,7 +484,7 @@ __device__ __forceinline__ void range_q8_body(int grp, int plane, const uint8_t*
         const int l = i >> 3, ry = i & 7;
         const int j = j0 + l;
         uint2 v = make_uint2(0u, 0u);
-        if (j < g.Nr) v = *(const uint2*)(img + (size_t)((j / g.Rw) * B + ry) * g.W + (j % g.Rw) * B);   // W, B multiples of 8: aligned
+        if (j < g.Nr) v = *(const uint2*)(img + (size_t)((j / g.Rw) * B + ry) * g.W + (j % g.Rw) * B);   // W, B multiples of 8 and so is the base (the widest load of the caller's bytes: fic_ctx_set_gray_device refuses any other): aligned
         *(uint2*)&blk[l * STR + ry * B] = v;
     }
     __syncthreads();

@@ -90,14 +90,17 @@ class Encoder:
 
     # ---- input -----------------------------------------------------------------------------
     def set_gray(self, gray):
-        """gray: uint8 [planes,H,W] / [H,W] numpy array, or a torch CUDA uint8 tensor of that shape."""
+        """gray: uint8 [planes,H,W] / [H,W] numpy array (copied), or a torch CUDA uint8 tensor of that shape.  A tensor whose
+        address is a multiple of 8 is used in place and read by every later encode, at encode time; any other one (a view at
+        an odd offset) is cloned here, once, into a fresh allocation: later writes to it are not seen."""
         L = capi.lib()
         n = self.planes * self.height * self.width
         if hasattr(gray, "data_ptr"):                                  # torch tensor, device resident
             if not gray.is_cuda or gray.dtype.itemsize != 1 or not gray.is_contiguous() or gray.numel() != n:
                 raise FicError(-3, "device input must be a contiguous uint8 CUDA tensor [planes,H,W]")
-            self._keep = gray
+            gray = capi.aligned_tensor(gray, 8)
             capi.check(L.fic_ctx_set_gray_device(self._h, C.c_void_p(gray.data_ptr())))
+            self._keep = gray
         else:
             g = np.ascontiguousarray(gray, np.uint8)
             if g.size != n:

@@ -109,7 +109,14 @@ FIC_API void fic_ctx_destroy(fic_ctx* ctx);
 
 /* Input: host bytes [planes][h][w] (copied), host ARGB (copied + R extracted on device), or a
  * device pointer to bytes [planes][h][w] that stays owned by the caller and must remain valid
- * until fic_ctx_sync (no copy; this is the path bench.py times: inputs resident in HBM). */
+ * until fic_ctx_sync (no copy; this is the path bench.py times: inputs resident in HBM).
+ * The device pointer is read by every later fic_ctx_encode, at encode time and on that encode's
+ * stream, not when it is set: what the caller writes there in stream order before an encode is
+ * what gets encoded.  Its address must be a multiple of 8 (the widest load of the caller's bytes;
+ * plane offsets p*w*h and row offsets keep that alignment for every accepted geometry); any other
+ * address is refused with FIC_E_ARGUMENT and the input in force stays.  A later
+ * fic_ctx_set_gray_host / fic_ctx_set_argb_host switches back to the context's own copy and never
+ * writes through the device pointer. */
 FIC_API int fic_ctx_set_gray_host(fic_ctx* ctx, const uint8_t* gray);
 FIC_API int fic_ctx_set_argb_host(fic_ctx* ctx, const int32_t* argb);
 FIC_API int fic_ctx_set_gray_device(fic_ctx* ctx, const void* dev_gray);
@@ -117,7 +124,14 @@ FIC_API int fic_ctx_set_gray_device(fic_ctx* ctx, const void* dev_gray);
 /* Asynchronous encode of range blocks [range_begin, range_begin+range_count) of every plane on
  * `hip_stream` (a hipStream_t, NULL = default stream): pool build + range prep + sweep +
  * finalise.  range_count < 0 means "to the end".  Multi-GPU sharding calls this
- * with a different span per rank; results for other ranges are left untouched. */
+ * with a different span per rank; results for other ranges are left untouched.
+ * Streams: a context's scratch and result arrays are shared by all its encodes.  Encodes issued
+ * on one stream are ordered by it.  An encode issued on ANOTHER stream than the context's last
+ * one starts only after that earlier encode has finished (the call waits for it on the host), so
+ * the last call wins whatever the streams (after fic_ctx_sync nothing is pending, and the next
+ * encode waits for nothing: the old stream may be destroyed by then); fic_ctx_sync, the host getters, collage, decode and
+ * the set_*_host entries wait on the stream of the last encode.  The result and record device
+ * pointers below never change over the life of the context. */
 FIC_API int fic_ctx_encode(fic_ctx* ctx, int range_begin, int range_count, void* hip_stream);
 FIC_API int fic_ctx_sync(fic_ctx* ctx);
 
@@ -150,8 +164,12 @@ FIC_API int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK
                                 float* a, float* bR, float* bG, float* bB, int32_t* qrows5, int32_t* collage_argb);
 /* Handle API of the same path: the device-resident working set of `planes` colour images of one geometry (a batch of
  * config-5 style images, or one image encoded again and again); same kernels, same bits as fic_encode_rgb_argb per image.
- * Input: host ARGB [planes][h][w] (copied) or a device pointer that stays owned by the caller until fic_rgb_ctx_sync.
+ * Input: host ARGB [planes][h][w] (copied) or a device pointer that stays owned by the caller until fic_rgb_ctx_sync.  As
+ * for fic_ctx_set_gray_device the device pointer is read at encode time, on the encode's stream; its address must be a
+ * multiple of 4 (every kernel loads the pixels as int32), else FIC_E_ARGUMENT and the input in force stays.
  * fic_rgb_ctx_encode is asynchronous on hip_stream; with_collage != 0 also builds getBestGeneratedCollageRGB (:308-347).
+ * Streams, as for fic_ctx_encode: an encode issued on another stream than the context's last one starts only after that
+ * earlier encode has finished (the call waits for it on the host); getters, decode and fic_rgb_ctx_sync wait on the last stream.
  * Results: [planes][N_r] arrays ([planes][N_r][5] qrows5, [planes][h][w] collage); any pointer may be NULL.
  * fic_rgb_ctx_decode_host runs decodeRGB (:430-508) from the context's quantised rows: argb_out [planes][h][w],
  * avg_error_out / iterations_out [planes] (may be NULL). */
