@@ -117,6 +117,7 @@ def lib():
         "fic_debug_sqrt_f64": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
         "fic_ctx_debug_pool_host": (C.c_int, [vp, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p]),
         "fic_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "fic_ctx_debug_lsq_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_last_kernel": (C.c_int, [vp, C.c_char_p, C.c_int]),
         "fic_rgb_ctx_sweep_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
@@ -264,6 +265,14 @@ def search_id(search):
     if search in (0, 1):
         return int(search)
     raise FicError(-3, f"search must be 'reference' or 'lsq', not {search!r}")
+
+
+LSQ_ENGINES = {"valu": 0, "mfma": 1}
+
+
+def lsq_engine_id(engine):
+    """"valu" (k_sweep_lsq_fast) / "mfma" (k_sweep_lsq_q), or the option value itself (the library checks it)."""
+    return LSQ_ENGINES[engine] if isinstance(engine, str) and engine in LSQ_ENGINES else engine
 
 
 def encode_gray_oneshot(gray, B, wK, n_iso=1, device=0, search="reference"):

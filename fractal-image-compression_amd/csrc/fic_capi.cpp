@@ -385,8 +385,35 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
     return FIC_OK;
 }
 
+// Pool chunks of the matrix-core least-squares sweep (k_sweep_lsq_q, fic_lsq_q.hip) in domain tiles of 32 blocks.  A chunk's
+// start costs a full first tile (1024 exact pairs per column tile of every wave), so there are two reasons to split, each with
+// its own floor under the chunk length (measured, profiles/lsq_q_timing.txt part 2, DESIGN.md 4.21 "Chunk policy"):
+//  fill:    fewer waves than the chip holds at two per SIMD (2048): split until they exist, down to chunks of 8 domain tiles;
+//  balance: up to four such rounds of waves (8192), but only with chunks of 500 domain tiles or more.
+void lsq_q_chunks(const fic_ctx* c, int ndtiles, int ct_count, int* tiles_per_chunk, int* nchunks)
+{
+    const FicGeom& g = c->g;
+    long long nc = c->opt_chunks;
+    if (nc <= 0) {
+        const long long ctw = fic_lsq_q_ct(g.B) / 4;                               // column tiles per wave
+        const long long base_waves = (ct_count + ctw - 1) / ctw * g.planes;       // wave tasks per chunk
+        long long fill = (2048 + base_waves - 1) / base_waves, bal = (8192 + base_waves - 1) / base_waves;
+        if (fill > ndtiles / 8) fill = ndtiles / 8;
+        if (bal > ndtiles / 500) bal = ndtiles / 500;
+        nc = fill > bal ? fill : bal;
+    }
+    if (nc > ndtiles) nc = ndtiles;
+    if (nc < 1) nc = 1;
+    *tiles_per_chunk = (int)((ndtiles + nc - 1) / nc);
+    const int longest = fic_lsq_q_max_tiles_per_chunk(g.B, g.n_iso);             // (a pool of 2^22 candidates or more: more chunks than asked for)
+    if (*tiles_per_chunk > longest) *tiles_per_chunk = longest;
+    *nchunks = (ndtiles + *tiles_per_chunk - 1) / *tiles_per_chunk;                // no empty chunk: every slot gets written
+}
+
 // Least-squares search ("search" = 1, fic_lsq.hip) of the span: pool build and range prep as for the VALU
 // sweeps, the extra sums, k_sweep_lsq_generic (windows, "sweep" = 1) or k_sweep_lsq_fast (full search), k_finalize_lsq.
+// Under "lsq_engine" = 1 the matrix-core sweep k_sweep_lsq_q (fic_lsq_q.hip; reported as sweep kind 7) runs
+// wherever k_sweep_lsq_fast would.
 int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
 {
     const FicGeom& g = c->g;
@@ -410,6 +437,16 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
         nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
         nslots = fic_lsq_slots(g, nchunks);
     }
+    int ct_begin = 0, ct_end = 0, tiles_per_chunk = 0;
+    if (kind == 2 && c->opt_lsq_engine == 1) {
+        kind = 7;
+        c->lsqq.ndtiles = (g.Nd + 31) / 32;
+        c->lsqq.nct_alloc = (int)(((long long)g.Nr * g.n_iso + 31) / 32);
+        ct_begin = (int)((long long)range_begin * g.n_iso / 32);
+        ct_end = (int)(((long long)(range_begin + range_count) * g.n_iso + 31) / 32);
+        lsq_q_chunks(c, c->lsqq.ndtiles, ct_end - ct_begin, &tiles_per_chunk, &nchunks);
+        nslots = nchunks;
+    }
     int rc = c->mem.ensure_zeroed(c->lsq.pool, P * g.Nd_pad * 16, s);      // the tail the prefetch over-reads
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.rng, P * g.Nr_pad * 8);
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.E, P * g.Nr * 8);
@@ -431,9 +468,21 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     if (rc) return rc;
     if (fic_launch_range(c->b.gray, c->b.rng_pix, c->b.rng_st, g, s, 1)) return fail(FIC_E_HIP, "k_range launch failed");
     if (fic_launch_lsq_stat(c->b, c->lsq, g, s)) return fail(FIC_E_HIP, "k_lsq_stat launch failed");
+    if (kind == 7) {                                   // fragment prep belongs to pool build / range prep: not timed
+        const size_t NK = (size_t)g.n / 16;
+        rc = c->mem.ensure(c->lsqq.poolQ, P * c->lsqq.ndtiles * NK * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngQ, P * c->lsqq.nct_alloc * NK * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngE, P * g.Nr_pad * sizeof(float));
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngR, P * g.Nr_pad * sizeof(uint32_t));
+        if (rc) return rc;
+        if (fic_launch_lsq_q_prep(c->b, c->lsq, c->lsqq, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_q_prep launch failed");
+    }
     rc = time_begin(c, s);
     if (rc) return rc;
-    if (kind == 1) {
+    if (kind == 7) {
+        if (fic_launch_sweep_lsq_q(c->b, c->lsq, c->lsqq, g, ct_begin, ct_end, tiles_per_chunk, nchunks, s, c->q_stats, c->opt_lsq_widen))
+            return fail(FIC_E_HIP, "k_sweep_lsq_q launch failed");
+    } else if (kind == 1) {
         if (fic_launch_sweep_lsq_generic(c->b, c->lsq, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_sweep_lsq_generic launch failed");
     } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_fast launch failed");
@@ -799,6 +848,12 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
     } else if (!strcmp(name, "lsq_tau_widen")) {       // diagnostic: k_sweep_lsq_fast's tau times 1 + 2^-value (> 0: above the derivation, WRONG codebooks)
         if (value != 0 && (value < 8 || value > 24)) return fail(FIC_E_ARGUMENT, "lsq_tau_widen must be 0 (off) or in 8..24");
         c->opt_lsq_widen = value;
+    } else if (!strcmp(name, "lsq_engine")) {          // which sweep runs where k_sweep_lsq_fast would: 0 that one, 1 k_sweep_lsq_q (matrix cores)
+        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "lsq_engine must be 0 (VALU, k_sweep_lsq_fast) or 1 (matrix cores, k_sweep_lsq_q)");
+        c->opt_lsq_engine = value;
+    } else if (!strcmp(name, "lsq_q_eshift")) {        // diagnostic: k_sweep_lsq_q's Er times 2^-value (> 0: below the derivation, WRONG codebooks)
+        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "lsq_q_eshift must be in -12..4");
+        c->opt_lsq_q_eshift = value;
     } else if (!strcmp(name, "q_noflag")) {            // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
         c->opt_noflag = value ? 1 : 0;
     } else if (!strcmp(name, "time_sweep")) {
@@ -853,6 +908,7 @@ int fic_ctx_last_kernel(fic_ctx* c, char* out, int capacity)
     else if (kind == 6 && fic_q_shape16(g)) snprintf(buf, sizeof(buf), "k_sweep_q16<%d, %s>", NK, multi);
     else if (kind == 6 && shorts) snprintf(buf, sizeof(buf), "k_sweep_qs<%d, %d>", NK, g.n_iso == 1 ? 0 : (g.B == 4 ? 1 : 2));
     else if (kind == 6) snprintf(buf, sizeof(buf), "k_sweep_q<%d, %d, %s>", NK, g.n_iso == 1 ? 0 : (g.B == 4 ? 1 : 2), multi);
+    else if (c->last_search == 1 && kind == 7) snprintf(buf, sizeof(buf), "k_sweep_lsq_q<%d, %d>", NK, g.n_iso == 8 ? 3 : 0);
     else if (c->last_search == 1) snprintf(buf, sizeof(buf), kind == 2 ? "k_sweep_lsq_fast" : "k_sweep_lsq_generic");
     else if (kind == 5) snprintf(buf, sizeof(buf), "k_sweep_d4");
     else if (kind == 2) snprintf(buf, sizeof(buf), "k_sweep_fast");
@@ -929,6 +985,24 @@ int fic_ctx_debug_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int
     *size = (int64_t)bytes;
     if (!out) return FIC_OK;
     if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_q_host: %zu bytes needed", bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
+int fic_ctx_debug_lsq_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
+{
+    if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_lsq_q_host: null argument");
+    if (!c->encoded_any || !c->lsqq.poolQ)
+        return fail(FIC_E_STATE, "fic_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
+    if (which < 0 || which > 3) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_lsq_q_host: which must be 0..3");
+    const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
+    const void* src = stores[which];
+    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
+    *size = (int64_t)bytes;
+    if (!out) return FIC_OK;
+    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_lsq_q_host: %zu bytes needed", bytes);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));

@@ -143,6 +143,9 @@ struct fic_ctx {
     size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
     int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
+    FicLsqQ lsqq{};                  // the matrix-core least-squares sweep ("lsq_engine" = 1): fragments, Er, R (on first use)
+    int opt_lsq_engine = 0;          // option "lsq_engine": 0 k_sweep_lsq_fast, 1 k_sweep_lsq_q wherever the former would run
+    int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, k_sweep_lsq_q's Er times 2^-value; > 0 gives WRONG codebooks
     bool have_input = false;
     bool encoded_any = false;
     hipStream_t last_stream = nullptr;

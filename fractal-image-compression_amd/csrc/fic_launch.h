@@ -196,6 +196,27 @@ int fic_launch_sweep_lsq_fast(const FicBuffers& b, const FicLsq& q, const FicGeo
                               int tau_widen = 0);                                     // option "lsq_tau_widen"
 int fic_launch_finalize_lsq(const FicBuffers& b, const FicOutputs& out, const FicLsq& q, int nslots, const FicGeom& g, int r_begin,
                             int r_count, hipStream_t s);
+// The same search on the matrix cores (fic_lsq_q.hip, context option "lsq_engine" = 1): a normalised f16 prune
+// GEMM decides which pairs can be skipped, the others are evaluated as above.  Its stores, beside FicBuffers and FicLsq
+// (NK = n / 16; a fragment is 64 lanes x 8 f16, laid out as fic_q.hip's frag_slot for v_mfma_f32_32x32x16_f16):
+//   poolQ : f16 [planes][ndtiles][NK][64][8]     A fragments, 32 pool blocks per domain tile (rows past N_d and flat blocks: zeros)
+//   rngQ  : f16 [planes][nct_alloc][NK][64][8]   B fragments, 32 columns per column tile, column = range block * n_iso + isometry
+//   rngE  : f32 [planes][Nr_pad]                 the rounding allowance Er of the prune test
+//   rngR  : u32 [planes][Nr_pad]                 R = n S_rr - S_r^2
+struct FicLsqQ {
+    void* poolQ = nullptr;
+    void* rngQ = nullptr;
+    void* rngE = nullptr;
+    void* rngR = nullptr;
+    int ndtiles = 0, nct_alloc = 0;
+};
+int fic_lsq_q_ct(int B);            // column tiles (x32 columns) per workgroup of k_sweep_lsq_q
+int fic_lsq_q_max_tiles_per_chunk(int B, int n_iso);   // longest pool chunk k_sweep_lsq_q takes, in domain tiles
+int fic_launch_lsq_q_prep(const FicBuffers& b, const FicLsq& q, const FicLsqQ& s, const FicGeom& g, int eshift, hipStream_t st);
+// column tiles [ct_begin, ct_end); nchunks pool chunks of tiles_per_chunk domain tiles, none empty; slots per plane = nchunks
+int fic_launch_sweep_lsq_q(const FicBuffers& b, const FicLsq& q, const FicLsqQ& s, const FicGeom& g, int ct_begin, int ct_end,
+                           int tiles_per_chunk, int nchunks, hipStream_t st, unsigned long long* stats = nullptr,
+                           int tau_widen = 0);
 // least-squares domain search of the joint-RGB path (fic_lsq_rgb.hip, option "search" = 1 of a colour context).
 // Its stores (Nr_pad = N_r rounded up to whole tiles of 64 range blocks):
 //   pool3   : u8    [planes][Nd_pad][3][n]               pool blocks, planar R, G, B (tail zeroed)

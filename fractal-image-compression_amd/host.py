@@ -116,9 +116,15 @@ class Encoder:
     # ---- compute ---------------------------------------------------------------------------
     def set_option(self, name, value):
         """fic_ctx_set_option.  "search" also takes "reference" / "lsq" (least squares).  "lsq_tau_widen": 0
-        (off) or 8..24 -- diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value)."""
+        (off) or 8..24 -- diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value).
+        "lsq_engine": 0 / "valu" (k_sweep_lsq_fast) or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_q, DESIGN.md 4.21: the same
+        codebooks); "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times 2^-value)."""
         if name == "search":
             value = capi.search_id(value)
+        if name == "lsq_engine":
+            value = capi.lsq_engine_id(value)
+            if isinstance(value, str):
+                raise FicError(-3, f"lsq_engine must be 'valu', 'mfma', 0 or 1, not {value!r}")
         capi.check(capi.lib().fic_ctx_set_option(self._h, name.encode(), int(value)))
 
     def lsq_error(self):
@@ -234,6 +240,17 @@ class Encoder:
         return {"pix": pix, "sum": s, "var": v, "scaled": sc}
 
     Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "rngC")
+    LSQ_Q_STORES = ("A", "B", "Er", "R")
+
+    def debug_lsq_q(self, which):
+        """Raw bytes (uint8 array) of one store of k_lsq_q_prep after an encode through k_sweep_lsq_q ("lsq_engine" = 1): "A" /
+        "B" the fragments, "Er" the per-range allowance (f32), "R" (u32) (fic_ctx_debug_lsq_q_host; tests/lsqqmodel.py decodes them)."""
+        i = self.LSQ_Q_STORES.index(which)
+        size = C.c_int64()
+        capi.check(capi.lib().fic_ctx_debug_lsq_q_host(self._h, i, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        capi.check(capi.lib().fic_ctx_debug_lsq_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
+        return out
 
     def debug_q(self, which):
         """Raw bytes (uint8 array) of one store of k_sweep_q after an encode through it ("sweep" = 6): "pool" / "rng" the
@@ -265,14 +282,17 @@ def encode_rgb_per_channel(rgb, B, wK=None, n_iso=1, device=0, sweep=0):
     return {k: v.reshape((n, 3) + v.shape[1:]) for k, v in r.items()}
 
 
-def encode_gray(gray, B, wK=None, n_iso=1, device=0, sweep=0, chunks=0, q_shape=0, search="reference"):
+def encode_gray(gray, B, wK=None, n_iso=1, device=0, sweep=0, chunks=0, q_shape=0, search="reference", lsq_engine="valu"):
     """One grey image (uint8 [H,W]) -> result dict with [N_r] arrays (plane axis dropped).  search="lsq": the least-squares
-    search (sweep 0 / 1 / 2), with the winners' errors as "E" (int64 [N_r])."""
+    search (sweep 0 / 1 / 2), with the winners' errors as "E" (int64 [N_r]); lsq_engine="mfma" runs its full
+    search on the matrix cores (k_sweep_lsq_q, DESIGN.md 4.21: the same codebook)."""
     g = np.ascontiguousarray(gray, np.uint8)
     with Encoder(g.shape[1], g.shape[0], B, wK, n_iso, 1, device) as enc:
         lsq = capi.search_id(search)
         if lsq:
             enc.set_option("search", lsq)
+        if capi.lsq_engine_id(lsq_engine):
+            enc.set_option("lsq_engine", lsq_engine)
         if sweep:
             enc.set_option("sweep", sweep)
         if chunks:

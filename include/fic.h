@@ -469,6 +469,17 @@ FIC_API int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int
  *                 1 + 2^-value after the safety factor, above what the derivation in fic_lsq.hip allows: > 0 gives WRONG
  *                 codebooks (the tests show that they are caught).  Not for production use; the contexts behind the one-shot
  *                 entries never carry it.  fic_rgb_ctx_set_option takes it too (k_sweep_lsq_rgb_fast).
+ *   "lsq_engine"  0 (default) or 1; any other value is FIC_E_ARGUMENT and leaves the option as it was.  Under 1, an encode under
+ *                 "search" = 1 that would have launched k_sweep_lsq_fast (full search with "sweep" 0 or 2) launches the
+ *                 matrix-core sweep k_sweep_lsq_q instead: an f16 GEMM decides which pairs can be
+ *                 skipped, every other pair is evaluated by the integer arithmetic of k_sweep_lsq_fast -- the same codebooks,
+ *                 bit for bit.  "sweep" = 1, windowed searches and "search" = 0 are untouched.  "chunks" then counts pool
+ *                 chunks in domain tiles of 32 blocks; range spans, batched planes, "time_sweep", the collage and the decodes
+ *                 work as before.  The one-shot and quadtree entries (and their cached contexts) never use it.
+ *   "lsq_q_eshift"  diagnostic, -12..4 (default 0): k_sweep_lsq_q's per-range rounding allowance Er is stored times 2^-value.
+ *                 Negative values widen the bound (more pairs evaluated exactly, same codebooks); positive values narrow it
+ *                 below what the derivation in fic_lsq_q.hip allows and give WRONG codebooks (the tests show that they are
+ *                 caught).  Not for production use.  "lsq_tau_widen" applies to k_sweep_lsq_q's theta as it does to tau.
  *   "chunks"      domain-pool chunks per range tile for the fast kernel (0 = auto)
  *   "time_sweep"  1: bracket every sweep launch with hipEvents on its stream */
 FIC_API int fic_ctx_set_option(fic_ctx* ctx, const char* name, int value);
@@ -543,12 +554,17 @@ FIC_API int fic_ctx_sweep_time(fic_ctx* ctx, double* total_ms, int* launches, in
  * out[6] their number (out[4] / out[5] / 10 = the clock in GHz the chip held under this kernel); out[7] reserved.
  * Under "search" = 1 the fast sweep k_sweep_lsq_fast counts instead: out[0] (wave, pool block) visits, out[1] visits that ran
  * the exact epilogue (some lane had a pair the prune could not skip), out[2] pairs evaluated exactly, out[3] waves.
+ * Under "lsq_engine" = 1 k_sweep_lsq_q counts with k_sweep_q's meaning: out[0] tile epilogues (32 columns x 32 pool blocks
+ * each), out[1] tiles that had flagged pairs, out[2] pairs evaluated exactly, out[3] waves; out[4..7] stay 0.
  * Synchronises the context's stream. */
 FIC_API int fic_ctx_sweep_stats(fic_ctx* ctx, uint64_t* out8, int reset);
-/* Geometry actually in use: out[0..9] = Rw, Rh, N_r, Dw, Dh, N_d, NR, tiles, chunks, sweep kind. */
+/* Geometry actually in use: out[0..9] = Rw, Rh, N_r, Dw, Dh, N_d, NR, tiles, chunks, sweep kind.  The sweep kind is the value
+ * of "sweep" that ran (1..6; under "search" = 1: 1 generic, 2 fast), or 7: the matrix-core least-squares sweep k_sweep_lsq_q
+ * ("lsq_engine" = 1). */
 FIC_API int fic_ctx_info(fic_ctx* ctx, int* out10);
 /* Name of the sweep kernel the context's last encode launched (as rocprofv3 prints it, without the argument list), e.g.
- * "k_sweep_lsq_fast" / "k_sweep_lsq_generic" under "search" = 1, "k_sweep_q<4, 2, false>" (one pool chunk), "k_sweep_q16<4, true>" (several) or "k_sweep_qs<4, 2>" / "k_sweep_q16s<4>" (several short
+ * "k_sweep_lsq_fast" / "k_sweep_lsq_generic" under "search" = 1 ("lsq_engine" = 1: "k_sweep_lsq_q<NK, CSHIFT>" with NK = n / 16 =
+ * 1, 4, 16 and CSHIFT = 0 (1 isometry) or 3 (8 isometries), e.g. "k_sweep_lsq_q<4, 3>"), "k_sweep_q<4, 2, false>" (one pool chunk), "k_sweep_q16<4, true>" (several) or "k_sweep_qs<4, 2>" / "k_sweep_q16s<4>" (several short
  * ones: theta is shared between the chunks in the fast path) -- so that a caller can match its timing with a profile.  A small launch
  * of the default sweep (one image up to about 512x512 at B = 8) runs as two kernels instead of five -- k_prep_q8 (scale + pool +
  * range prep) and the sweep, whose last workgroup per range-column group also does k_finalize's work -- and the name then
@@ -588,6 +604,12 @@ FIC_API int fic_ctx_debug_pool_host(fic_ctx* ctx, uint8_t* pix, uint32_t* sum, u
  * {rM, rem} i32 pairs [planes][padded N_r], 5 the columns' copies as bytes [planes][padded N_r][columns per range][n].
  * *size = the store's size in bytes; out may be NULL (size only), else capacity must hold it. */
 FIC_API int fic_ctx_debug_q_host(fic_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
+/* Test hook: raw bytes of one store of k_lsq_q_prep after an encode through k_sweep_lsq_q ("search" = 1, "lsq_engine" = 1;
+ * FIC_E_STATE before the first one): which = 0 A fragments [planes][domain tiles][NK][64] x 8 f16 (slot (m, lane): elements
+ * [16 m + 8 (lane >> 5), +8) of pool block 32 tile + (lane & 31)), 1 B fragments [planes][column tiles][NK][64] x 8 f16 (column
+ * = range block * n_iso + isometry), 2 the allowance Er f32 [planes][padded N_r], 3 R = n S_rr - S_r^2 u32 [planes][padded N_r].
+ * *size = the store's size in bytes; out may be NULL (size only), else capacity must hold it. */
+FIC_API int fic_ctx_debug_lsq_q_host(fic_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 /* Test hook, joint RGB: the same for the matrix-core RGB sweep ("sweep" = 2) of the LAST plane encoded: which = 0 A fragments
  * [domain tiles + padding][NK][64] x 8 f16, 1 flat-tile flags, 2 B fragments [column tiles + padding][NK][64] x 8 f16, 3 E_r f32 [N_r],
  * 4 {0, varianzRange} i32 pairs [N_r], 5 Amax (f32 bits, one u32).  On an n_iso = 8 context the B fragments hold 8 adjacent
