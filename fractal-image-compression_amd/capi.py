@@ -120,6 +120,9 @@ def lib():
         "fic_ctx_debug_lsq_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "fic_rgb_ctx_last_kernel": (C.c_int, [vp, C.c_char_p, C.c_int]),
+        "fic_rgb_ctx_debug_lsq_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "fic_rgb_ctx_sweep_time": (C.c_int, [vp, C.POINTER(C.c_double), ip, C.c_int]),
+        "fic_rgb_ctx_last_lsq_chunks": (C.c_int, [vp]),
         "fic_rgb_ctx_sweep_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
         "fic_encode_gray_quadtree_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_encode_gray_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
@@ -363,12 +366,26 @@ def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):
     return out[:cap], np.float32(avg.value), it.value, w, h
 
 
-def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1, search="reference"):
+def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1, search="reference", lsq_engine="valu"):
     """encodeRGB (FC:171-219) on the GPU.  argb: int32 [h*w].  Returns a dict of [N_r] arrays
     (idx_local, a, bR, bG, bB, iso, qrows [N_r,5]) and, when asked, the collage (int32 [h*w]).  n_iso = 8: the search also
     tries the 8 isometries of the domain block (fic_encode_rgb_iso_argb; `iso` is all 0 with n_iso = 1, the reference path).
-    search="lsq": the least-squares search (fic_encode_rgb_lsq_argb), with the winners' errors as "E" (int64 [N_r])."""
+    search="lsq": the least-squares search (fic_encode_rgb_lsq_argb, DESIGN.md 4.20), with the winners' errors as "E" (int64 [N_r]);
+    lsq_engine="mfma" runs its full search on the matrix cores (k_sweep_lsq_rgb_q, DESIGN.md 4.22: the same codebook) through a
+    context of its own -- the one-shot entry and its cached contexts never carry the option."""
     lsq = search_id(search)
+    engine = lsq_engine_id(lsq_engine)
+    if engine not in (0, 1):
+        raise FicError(-3, f"lsq_engine must be 'valu', 'mfma', 0 or 1, not {lsq_engine!r}")
+    if lsq and engine:
+        with RgbEncoder(w, h, B, wK, 1, device, n_iso) as enc:
+            enc.set_option("search", 1)
+            enc.set_option("lsq_engine", 1)
+            enc.set_argb(np.ascontiguousarray(argb, np.int32).reshape(1, -1))
+            enc.encode(with_collage=want_collage)
+            r = {k: v[0] for k, v in enc.results().items()}
+            r["E"] = enc.lsq_error()[0]
+        return r
     Rw, Rh, Dw, Dh = geometry(w, h, B)
     nr = Rw * Rh
     argb = np.ascontiguousarray(argb, np.int32).reshape(-1)
@@ -450,9 +467,16 @@ class RgbEncoder:
     def set_option(self, name, value):
         """"sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search.  "search": 0 / "reference" or 1 / "lsq" (least
         squares; "sweep" then means 0 auto, 1 generic, 2 fast).  "lsq_tau_widen": 0 (off) or 8..24 --
-        diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value)."""
+        diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value).  "lsq_engine": 0 / "valu"
+        or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_rgb_q, DESIGN.md 4.22: the same codebooks, B = 16 included);
+        "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times 2^-value); "time_sweep": 1
+        brackets the least-squares sweep launch with events (sweep_time)."""
         if name == "search":
             value = search_id(value)
+        if name == "lsq_engine":
+            value = lsq_engine_id(value)
+            if isinstance(value, str):                       # other numbers: the library refuses them (FIC_E_ARGUMENT)
+                raise FicError(-3, f"lsq_engine must be 'valu', 'mfma', 0 or 1, not {value!r}")
         check(lib().fic_rgb_ctx_set_option(self._h, name.encode(), int(value)))
 
     def lsq_error(self):
@@ -476,6 +500,29 @@ class RgbEncoder:
         v = (C.c_uint64 * 8)()
         check(lib().fic_rgb_ctx_sweep_stats(self._h, v, 1 if reset else 0))
         return dict(zip(["tiles", "flagged_tiles", "exact_pairs", "waves", "wave_cycles", "wave_ticks", "waves_sampled"], [int(x) for x in v]))
+
+    def sweep_time(self, reset=True):
+        """(total ms, launches) of the least-squares sweep launches since the last reset (set_option("time_sweep", 1))."""
+        ms, n = C.c_double(), C.c_int()
+        check(lib().fic_rgb_ctx_sweep_time(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
+        return ms.value, n.value
+
+    def last_lsq_chunks(self):
+        """Pool chunks of the last least-squares sweep (0: the last encode was none)."""
+        return check(lib().fic_rgb_ctx_last_lsq_chunks(self._h))
+
+    LSQ_Q_STORES = ("A", "B", "Er", "R")
+
+    def debug_lsq_q(self, which):
+        """Raw bytes (uint8 array) of one store of k_lsq_rgb_q_prep after an encode through k_sweep_lsq_rgb_q ("lsq_engine" = 1):
+        "A" / "B" the fragments, "Er" the per-range allowance (f32), "R" (u32) (fic_rgb_ctx_debug_lsq_q_host;
+        tests/rgblsqqmodel.py decodes them)."""
+        i = self.LSQ_Q_STORES.index(which)
+        size = C.c_int64()
+        check(lib().fic_rgb_ctx_debug_lsq_q_host(self._h, i, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        check(lib().fic_rgb_ctx_debug_lsq_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
+        return out
 
     Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "amax")
 

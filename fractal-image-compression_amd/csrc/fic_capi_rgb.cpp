@@ -238,6 +238,21 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         c->opt_lsq_widen = value;
         return FIC_OK;
     }
+    if (!strcmp(name, "lsq_engine")) {                 // which sweep a full least-squares search runs: 0 VALU, 1 k_sweep_lsq_rgb_q (matrix cores)
+        if (value < 0 || value > 1)
+            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_engine must be 0 (VALU sweeps) or 1 (matrix cores, k_sweep_lsq_rgb_q)");
+        c->opt_lsq_engine = value;
+        return FIC_OK;
+    }
+    if (!strcmp(name, "lsq_q_eshift")) {               // diagnostic: k_sweep_lsq_rgb_q's Er times 2^-value (> 0: below the derivation, WRONG codebooks)
+        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_q_eshift must be in -12..4");
+        c->opt_lsq_q_eshift = value;
+        return FIC_OK;
+    }
+    if (!strcmp(name, "time_sweep")) {                 // event pairs around the least-squares sweep launch (fic_rgb_ctx_sweep_time)
+        c->opt_time = value ? 1 : 0;
+        return FIC_OK;
+    }
     if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
         HIP_TRY(hipSetDevice(c->device));
         return sweep_stats_option(c->mem, c->q.stats, value, c->last_stream);
@@ -287,7 +302,8 @@ int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
     if (c->last_search == 1) {
         int NC = 1;
         fic_lsq_rgb_variant(g.B, g.n_iso, &NC);
-        if (c->last_lsq_kind == 2) snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_fast<%d, %d>", 3 * g.DW, NC);
+        if (c->last_lsq_kind == 7) snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_q<%d, %d>", 3 * g.n / 16, g.n_iso == 8 ? 3 : 0);
+        else if (c->last_lsq_kind == 2) snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_fast<%d, %d>", 3 * g.DW, NC);
         else snprintf(buf, sizeof(buf), "k_sweep_lsq_rgb_generic");
     } else if (c->last_sweep == 2) {
         const int kind = fic_q_multi_kind(c->q.nchunks, c->q.tiles_per_chunk);      // what fic_launch_rgbq instantiates

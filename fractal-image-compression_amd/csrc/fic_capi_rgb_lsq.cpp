@@ -2,11 +2,56 @@
 // of a colour context under "search" = 1 (kernels in fic_lsq_rgb.hip), the winners' errors and the one-shot entry over the
 // cached contexts.  The quadtree entries are in fic_capi_quadtree.cpp.  Host-side orchestration only.
 #include "fic_internal.h"
+#include "fic_lsq_rgb_q_chunks.h"
 
 using namespace ficd;
 
+fic_rgb_ctx::~fic_rgb_ctx()
+{
+    if (ev.empty()) return;
+    (void)hipSetDevice(device);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+}
+
+namespace {
+
+// "time_sweep" of a colour context: fic_capi.cpp's scheme.  Pairs of events bracket the sweep launch on its stream and are
+// read later; with the option off no event is created.
+int rgb_flush_events(fic_rgb_ctx* c)
+{
+    for (size_t i = 0; i + 1 < c->ev.size(); i += 2) {
+        HIP_TRY(hipEventSynchronize(c->ev[i + 1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
+        c->acc_ms += ms;
+        c->acc_n += 1;
+        (void)hipEventDestroy(c->ev[i]);
+        (void)hipEventDestroy(c->ev[i + 1]);
+    }
+    c->ev.clear();
+    return FIC_OK;
+}
+int rgb_time_mark(fic_rgb_ctx* c, hipStream_t s, bool begin)
+{
+    if (!c->opt_time) return FIC_OK;
+    if (begin && c->ev.size() >= 256) {                // bound the pending list: fold finished launches into the accumulators
+        int rc = rgb_flush_events(c);
+        if (rc) return rc;
+    }
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    c->ev.push_back(e);
+    HIP_TRY(hipEventRecord(e, s));
+    return FIC_OK;
+}
+
+}  // namespace
+
 // scaleImageRGB as for the reference's search, then the planar byte stores and sums, k_sweep_lsq_rgb_generic (windows, B = 16,
 // "sweep" = 1) or k_sweep_lsq_rgb_fast (full search at B <= 8), k_finalize_lsq_rgb and the reference's collage of the rows.
+// Under "lsq_engine" = 1 a full search with "sweep" 0 or 2 at B = 4 / 8 / 16 runs k_sweep_lsq_rgb_q instead:
+// where the fast sweep would run at B <= 8, and where the automatic choice would take the generic kernel at B = 16 ("sweep" = 2
+// is accepted there only under this option).  "sweep" = 1, windows and "search" = 0 never see the option.
 int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev, bool switched)
 {
     // the byte stores, sums, slots and outputs are shared with the earlier encode: the new work starts after it
@@ -15,6 +60,8 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     int NC = 1;
     const bool fast_ok = g.full && fic_lsq_rgb_variant(g.B, g.n_iso, &NC) == 0;
     int kind = c->opt_sweep;
+    const bool q_ok = c->opt_lsq_engine == 1 && g.full && kind != 1 && (g.B == 4 || g.B == 8 || g.B == 16) && (g.n_iso == 1 || g.n_iso == 8);
+    if (q_ok) kind = 7;
     if (kind == 0) kind = fast_ok ? 2 : 1;
     if (kind == 2 && !fast_ok)
         return fail(FIC_E_ARGUMENT, "least-squares search: the fast sweep (\"sweep\" = 2) needs full search (wK == Dw == Dh) and B <= 8");
@@ -34,6 +81,15 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
         chunk_len = (int)((g.Nd + nc - 1) / nc);
         nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
         nslots = fic_lsq_rgb_slots(g, nchunks);
+    }
+    LsqRgbQPlan plan{};
+    if (kind == 7) {
+        plan = lsq_rgb_q_plan(g.Nd, (long long)g.Nr * g.n_iso, g.B, g.n_iso, g.planes, c->opt_chunks);
+        if (!plan.ok) return fail(FIC_E_GEOMETRY, "least-squares search on the matrix cores: the pool has 2^32 - 1 candidates or more");
+        nchunks = plan.nchunks;
+        nslots = plan.nslots;
+        c->lsqq.ndtiles = plan.ndtiles;
+        c->lsqq.nct = (int)(((long long)g.Nr * g.n_iso + 31) / 32);
     }
     DevMem& m = c->mem;
     int rc = m.ensure_zeroed(q.pool3, P * g.Nd_pad * 3 * g.n, s);
@@ -57,16 +113,34 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     o.qrows = c->qrows; o.iso = c->iso;
     if (fic_launch_scale_rgb_planes(c->argb, c->scaled, g, s)) return fail(FIC_E_HIP, "k_scale_rgb launch failed");
     if (fic_launch_lsq_rgb_prep(c->argb, c->scaled, q, g, s)) return fail(FIC_E_HIP, "k_lsq_rgb_prep launch failed");
-    if (kind == 1) {
+    if (kind == 7) {                                   // fragment prep belongs to the stores: not timed
+        const size_t NK = 3 * (size_t)g.n / 16;
+        FicLsqRgbQ& f = c->lsqq;
+        rc = m.ensure(f.poolQ, P * f.ndtiles * NK * 64 * 16);
+        if (rc == FIC_OK) rc = m.ensure(f.rngQ, P * f.nct * NK * 64 * 16);
+        if (rc == FIC_OK) rc = m.ensure(f.rngE, P * nrp * sizeof(float));
+        if (rc == FIC_OK) rc = m.ensure(f.rngR, P * nrp * sizeof(uint32_t));
+        if (rc) return rc;
+        if (fic_launch_lsq_rgb_q_prep(q, f, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_rgb_q_prep launch failed");
+    }
+    rc = rgb_time_mark(c, s, true);
+    if (rc) return rc;
+    if (kind == 7) {
+        if (fic_launch_sweep_lsq_rgb_q(q, c->lsqq, g, plan.tiles_per_chunk, plan.nchunks, s, c->q.stats, c->opt_lsq_widen))
+            return fail(FIC_E_HIP, "k_sweep_lsq_rgb_q launch failed");
+    } else if (kind == 1) {
         if (fic_launch_sweep_lsq_rgb_generic(q, g, s)) return fail(FIC_E_HIP, "k_sweep_lsq_rgb_generic launch failed");
     } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->q.stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_rgb_fast launch failed");
     }
+    rc = rgb_time_mark(c, s, false);
+    if (rc) return rc;
     if (fic_launch_finalize_lsq_rgb(o, q, nslots, g, s)) return fail(FIC_E_HIP, "k_finalize_lsq_rgb launch failed");
     if (with_collage && fic_launch_rgb_collage(c->scaled, o, c->collage, g, s)) return fail(FIC_E_HIP, "k_collage_rgb launch failed");
     c->last_sweep = 1;                                 // nothing of the matrix-core sweep to look at (fic_rgb_ctx_debug_q_host)
     c->last_search = 1;
     c->last_lsq_kind = kind;
+    c->last_lsq_chunks = nchunks;
     c->encoded_any = true;
     c->have_collage = with_collage != 0;
     return FIC_OK;
@@ -84,6 +158,44 @@ int fic_rgb_ctx_get_lsq_error_host(fic_rgb_ctx* c, int64_t* E)
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     static_assert(sizeof(long long) == sizeof(int64_t), "E");
     HIP_TRY(hipMemcpy(E, c->lsq.E, (size_t)c->g.planes * c->g.Nr * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
+int fic_rgb_ctx_sweep_time(fic_rgb_ctx* c, double* total_ms, int* launches, int reset)
+{
+    if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_time: null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = rgb_flush_events(c);
+    if (rc) return rc;
+    if (total_ms) *total_ms = c->acc_ms;
+    if (launches) *launches = c->acc_n;
+    if (reset) { c->acc_ms = 0.0; c->acc_n = 0; }
+    return FIC_OK;
+}
+
+int fic_rgb_ctx_last_lsq_chunks(fic_rgb_ctx* c)
+{
+    if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_last_lsq_chunks: null context");
+    return c->last_search == 1 ? c->last_lsq_chunks : 0;
+}
+
+int fic_rgb_ctx_debug_lsq_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
+{
+    if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_lsq_q_host: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any || !c->lsqq.poolQ)
+        return fail(FIC_E_STATE, "fic_rgb_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
+    if (which < 0 || which > 3) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_lsq_q_host: which must be 0..3");
+    const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
+    const void* src = stores[which];
+    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
+    *size = (int64_t)bytes;
+    if (!out) return FIC_OK;
+    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_rgb_ctx_debug_lsq_q_host: %zu bytes needed", bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return FIC_OK;
 }
 

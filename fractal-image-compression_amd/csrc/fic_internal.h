@@ -191,11 +191,20 @@ struct fic_rgb_ctx {
     size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
     int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
-    int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast
+    int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast, 7 matrix cores (k_sweep_lsq_rgb_q)
+    FicLsqRgbQ lsqq{};               // the matrix-core least-squares sweep ("lsq_engine" = 1): fragments, Er, R (on first use)
+    int opt_lsq_engine = 0;          // option "lsq_engine": 0 the VALU sweeps, 1 k_sweep_lsq_rgb_q where the full-search sweep would run
+    int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, that sweep's Er times 2^-value; > 0 gives WRONG codebooks
+    int last_lsq_chunks = 0;         // pool chunks of the last least-squares sweep
+    int opt_time = 0;                // option "time_sweep": event pairs around the least-squares sweep launch (fic_rgb_ctx_sweep_time)
+    std::vector<hipEvent_t> ev;      // pairs start/stop; none is created while the option is off
+    double acc_ms = 0.0;
+    int acc_n = 0;
     bool have_input = false, encoded_any = false, have_collage = false;
     hipStream_t last_stream = nullptr;
     bool stream_used = false;        // an encode was issued on last_stream (fic_rgb_ctx_encode orders a stream switch after it)
     std::mutex mu;
+    ~fic_rgb_ctx();                  // the events (fic_capi_rgb_lsq.cpp); the memory goes with `mem`
 };
 
 namespace ficd {

@@ -244,6 +244,23 @@ int fic_launch_sweep_lsq_rgb_fast(const FicLsqRgb& q, const FicGeom& g, int chun
                                   unsigned long long* stats = nullptr,    // stats u64 [8]: "sweep_stats" counters or NULL
                                   int tau_widen = 0);                      // option "lsq_tau_widen"
 int fic_launch_finalize_lsq_rgb(const FicRgbOutputs& out, const FicLsqRgb& q, int nslots, const FicGeom& g, hipStream_t s);
+// The same search on the matrix cores (fic_lsq_rgb_q.hip, colour context option "lsq_engine" = 1), B = 4 / 8 /
+// 16: a block is one vector of 3 n entries (planar), NK = 3 n / 16.  Its stores, beside FicLsqRgb (fragments as in FicLsqQ):
+//   poolQ : f16 [planes][ndtiles][NK][64][8]   A fragments, 32 pool blocks per domain tile (rows past N_d and V == 0: zeros)
+//   rngQ  : f16 [planes][nct][NK][64][8]       B fragments, 32 columns per column tile, column = range block * n_iso + isometry
+//   rngE  : f32 [planes][Nr_pad]               the rounding allowance Er of the prune test
+//   rngR  : u32 [planes][Nr_pad]               R = n S_rr - sum_ch S_r^2 (unsigned: < 2^31.6 at B = 16)
+struct FicLsqRgbQ {
+    void* poolQ = nullptr;
+    void* rngQ = nullptr;
+    void* rngE = nullptr;
+    void* rngR = nullptr;
+    int ndtiles = 0, nct = 0;
+};
+int fic_launch_lsq_rgb_q_prep(const FicLsqRgb& q, const FicLsqRgbQ& s, const FicGeom& g, int eshift, hipStream_t st);
+// nchunks pool chunks of tiles_per_chunk domain tiles, none empty (fic_lsq_rgb_q_chunks.h); slots per plane = nchunks
+int fic_launch_sweep_lsq_rgb_q(const FicLsqRgb& q, const FicLsqRgbQ& s, const FicGeom& g, int tiles_per_chunk, int nchunks,
+                               hipStream_t st, unsigned long long* stats = nullptr, int tau_widen = 0);
 // stages of fic_launch_rgb_encode on their own, over g.planes images: scaleImageRGB and the collage of the rows in `out`
 int fic_launch_scale_rgb_planes(const int32_t* argb, int32_t* scaled, const FicGeom& g, hipStream_t s);
 int fic_launch_rgb_collage(const int32_t* scaled, const FicRgbOutputs& out, int32_t* collage, const FicGeom& g, hipStream_t s);

@@ -538,6 +538,26 @@ FIC_API int fic_encode_gray_quadtree_lsq_argb(const int32_t* argb, int w, int h,
  * quadtree entries have the signatures of fic_encode_rgb_quadtree_argb (tag 3) and fic_encode_rgb_quadtree_iso_argb (tag 6):
  * the per-level codebooks come from this search, everything after them is unchanged. */
 FIC_API int fic_rgb_ctx_get_lsq_error_host(fic_rgb_ctx* ctx, int64_t* E);
+/* The same search on the matrix cores, options of a colour context:
+ *   "lsq_engine"    0 (default: today's sweeps, launch for launch) or 1; any other value is FIC_E_ARGUMENT and leaves the option
+ *                   as it was, whatever else is set.  Under 1, an encode under "search" = 1 with full search (wK == Dw == Dh),
+ *                   "sweep" 0 or 2, B = 4 / 8 / 16 and 1 or 8 isometries launches k_sweep_lsq_rgb_q<NK, CSHIFT> (NK = 3 n / 16 =
+ *                   3, 12, 48; CSHIFT = 0 or 3): where k_sweep_lsq_rgb_fast would run at B <= 8, and where the automatic choice
+ *                   would take k_sweep_lsq_rgb_generic at B = 16.  "sweep" = 2 at B = 16 stops being refused only under this
+ *                   option.  An f16 GEMM over the 3 n entries of a block decides which pairs can be skipped; every other pair is
+ *                   evaluated as before: the codebook and E are the same bits.  "sweep" = 1, windows and "search" = 0 never see
+ *                   the option; the one-shot, quadtree and leaf-budget entries and their cached contexts never set it.  "chunks"
+ *                   then counts pool chunks in domain tiles of 32 blocks (0 = automatic).  fic_rgb_ctx_last_kernel reports the
+ *                   kernel; "sweep_stats" counts out[0] tile epilogues (32 columns x 32 pool blocks), out[1] tiles with flagged
+ *                   pairs, out[2] pairs evaluated exactly, out[3] waves.
+ *   "lsq_q_eshift"  diagnostic, -12..4 (default 0): that sweep's per-range rounding allowance Er is stored times 2^-value.
+ *                   Values > 0 put it below what the derivation in fic_lsq_rgb_q.hip allows and give WRONG codebooks.  Not for
+ *                   production use.  "lsq_tau_widen" acts on that sweep's tau as on k_sweep_lsq_rgb_fast's.
+ *   "time_sweep"    1: bracket the sweep launch of every encode under "search" = 1 with hipEvents on its stream (with 0, the
+ *                   default, no event is created); fic_rgb_ctx_sweep_time reads them as fic_ctx_sweep_time does.
+ * fic_rgb_ctx_last_lsq_chunks: pool chunks of the last least-squares sweep (0: the last encode was none). */
+FIC_API int fic_rgb_ctx_sweep_time(fic_rgb_ctx* ctx, double* total_ms, int* launches, int reset);
+FIC_API int fic_rgb_ctx_last_lsq_chunks(fic_rgb_ctx* ctx);
 FIC_API int fic_encode_rgb_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
                                     float* a, float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb,
                                     int64_t* E);
@@ -615,6 +635,11 @@ FIC_API int fic_ctx_debug_lsq_q_host(fic_ctx* ctx, int which, void* out, int64_t
  * 4 {0, varianzRange} i32 pairs [N_r], 5 Amax (f32 bits, one u32).  On an n_iso = 8 context the B fragments hold 8 adjacent
  * columns per range block, column 8 j + k the copy c_k of range j with c_k[src_k(i)] = greyR[i]; the other stores are unchanged. */
 FIC_API int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
+/* Test hook, joint RGB: raw bytes of one store of k_lsq_rgb_q_prep after an encode through k_sweep_lsq_rgb_q ("search" = 1,
+ * "lsq_engine" = 1; FIC_E_STATE before the first one), as fic_ctx_debug_lsq_q_host with NK = 3 n / 16 and element i = ch * n + pos
+ * of a block: which = 0 A fragments [planes][domain tiles][NK][64] x 8 f16, 1 B fragments [planes][column tiles][NK][64] x 8 f16,
+ * 2 the allowance Er f32 [planes][N_r padded to 64], 3 R = n S_rr - sum_ch S_r^2 u32 [planes][N_r padded to 64]. */
+FIC_API int fic_rgb_ctx_debug_lsq_q_host(fic_rgb_ctx* ctx, int which, void* out, int64_t capacity, int64_t* size);
 
 /* Test hook: what the library holds right now, process-wide, through contexts, the one-shot caches, the decoders' arenas and
  * any call in flight: out4 = {device bytes, device allocations, pinned host bytes, pinned host allocations}.  All four are 0
