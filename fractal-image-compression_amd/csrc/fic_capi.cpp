@@ -4,6 +4,7 @@
 // (decoder entries: fic_capi_decode.cpp; joint-RGB contexts: fic_capi_rgb.cpp; multi-device entry: fic_capi_multi.cpp;
 // error state, geometry and every stream writer / parser: fic_stream.cpp)
 #include "fic_internal.h"
+#include "fic_lsq_q_chunks.h"
 
 namespace ficd {
 
@@ -385,31 +386,6 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
     return FIC_OK;
 }
 
-// Pool chunks of the matrix-core least-squares sweep (k_sweep_lsq_q, fic_lsq_q.hip) in domain tiles of 32 blocks.  A chunk's
-// start costs a full first tile (1024 exact pairs per column tile of every wave), so there are two reasons to split, each with
-// its own floor under the chunk length (measured, profiles/lsq_q_timing.txt part 2, DESIGN.md 4.21 "Chunk policy"):
-//  fill:    fewer waves than the chip holds at two per SIMD (2048): split until they exist, down to chunks of 8 domain tiles;
-//  balance: up to four such rounds of waves (8192), but only with chunks of 500 domain tiles or more.
-void lsq_q_chunks(const fic_ctx* c, int ndtiles, int ct_count, int* tiles_per_chunk, int* nchunks)
-{
-    const FicGeom& g = c->g;
-    long long nc = c->opt_chunks;
-    if (nc <= 0) {
-        const long long ctw = fic_lsq_q_ct(g.B) / 4;                               // column tiles per wave
-        const long long base_waves = (ct_count + ctw - 1) / ctw * g.planes;       // wave tasks per chunk
-        long long fill = (2048 + base_waves - 1) / base_waves, bal = (8192 + base_waves - 1) / base_waves;
-        if (fill > ndtiles / 8) fill = ndtiles / 8;
-        if (bal > ndtiles / 500) bal = ndtiles / 500;
-        nc = fill > bal ? fill : bal;
-    }
-    if (nc > ndtiles) nc = ndtiles;
-    if (nc < 1) nc = 1;
-    *tiles_per_chunk = (int)((ndtiles + nc - 1) / nc);
-    const int longest = fic_lsq_q_max_tiles_per_chunk(g.B, g.n_iso);             // (a pool of 2^22 candidates or more: more chunks than asked for)
-    if (*tiles_per_chunk > longest) *tiles_per_chunk = longest;
-    *nchunks = (ndtiles + *tiles_per_chunk - 1) / *tiles_per_chunk;                // no empty chunk: every slot gets written
-}
-
 // Least-squares search ("search" = 1, fic_lsq.hip) of the span: pool build and range prep as for the VALU
 // sweeps, the extra sums, k_sweep_lsq_generic (windows, "sweep" = 1) or k_sweep_lsq_fast (full search), k_finalize_lsq.
 // Under "lsq_engine" = 1 the matrix-core sweep k_sweep_lsq_q (fic_lsq_q.hip; reported as sweep kind 7) runs
@@ -444,8 +420,11 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
         c->lsqq.nct_alloc = (int)(((long long)g.Nr * g.n_iso + 31) / 32);
         ct_begin = (int)((long long)range_begin * g.n_iso / 32);
         ct_end = (int)(((long long)(range_begin + range_count) * g.n_iso + 31) / 32);
-        lsq_q_chunks(c, c->lsqq.ndtiles, ct_end - ct_begin, &tiles_per_chunk, &nchunks);
-        nslots = nchunks;
+        // fic_lsq_q_chunks.h's fill / balance rule (4 waves per workgroup): no cap on the count, the 22-bit cap on the length
+        const LsqQChunks k = lsq_q_chunk_plan(c->lsqq.ndtiles, ct_end - ct_begin, fic_lsq_q_ct(g.B) / 4, g.planes, c->opt_chunks,
+                                              FIC_LSQ_Q_NO_CAP, fic_lsq_q_max_tiles_per_chunk(g.B, g.n_iso));
+        tiles_per_chunk = k.tiles_per_chunk;
+        nslots = nchunks = k.nchunks;
     }
     int rc = c->mem.ensure_zeroed(c->lsq.pool, P * g.Nd_pad * 16, s);      // the tail the prefetch over-reads
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.rng, P * g.Nr_pad * 8);

@@ -2,7 +2,7 @@
 // of a colour context under "search" = 1 (kernels in fic_lsq_rgb.hip), the winners' errors and the one-shot entry over the
 // cached contexts.  The quadtree entries are in fic_capi_quadtree.cpp.  Host-side orchestration only.
 #include "fic_internal.h"
-#include "fic_lsq_rgb_q_chunks.h"
+#include "fic_lsq_q_chunks.h"
 
 using namespace ficd;
 

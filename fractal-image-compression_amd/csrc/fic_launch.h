@@ -211,9 +211,9 @@ struct FicLsqQ {
     int ndtiles = 0, nct_alloc = 0;
 };
 int fic_lsq_q_ct(int B);            // column tiles (x32 columns) per workgroup of k_sweep_lsq_q
-int fic_lsq_q_max_tiles_per_chunk(int B, int n_iso);   // longest pool chunk k_sweep_lsq_q takes, in domain tiles
 int fic_launch_lsq_q_prep(const FicBuffers& b, const FicLsq& q, const FicLsqQ& s, const FicGeom& g, int eshift, hipStream_t st);
-// column tiles [ct_begin, ct_end); nchunks pool chunks of tiles_per_chunk domain tiles, none empty; slots per plane = nchunks
+// column tiles [ct_begin, ct_end); nchunks pool chunks of tiles_per_chunk domain tiles, none empty and none longer than
+// fic_lsq_q_max_tiles_per_chunk (fic_lsq_q_chunks.h); slots per plane = nchunks
 int fic_launch_sweep_lsq_q(const FicBuffers& b, const FicLsq& q, const FicLsqQ& s, const FicGeom& g, int ct_begin, int ct_end,
                            int tiles_per_chunk, int nchunks, hipStream_t st, unsigned long long* stats = nullptr,
                            int tau_widen = 0);
@@ -258,7 +258,7 @@ struct FicLsqRgbQ {
     int ndtiles = 0, nct = 0;
 };
 int fic_launch_lsq_rgb_q_prep(const FicLsqRgb& q, const FicLsqRgbQ& s, const FicGeom& g, int eshift, hipStream_t st);
-// nchunks pool chunks of tiles_per_chunk domain tiles, none empty (fic_lsq_rgb_q_chunks.h); slots per plane = nchunks
+// nchunks pool chunks of tiles_per_chunk domain tiles, none empty (fic_lsq_q_chunks.h); slots per plane = nchunks
 int fic_launch_sweep_lsq_rgb_q(const FicLsqRgb& q, const FicLsqRgbQ& s, const FicGeom& g, int tiles_per_chunk, int nchunks,
                                hipStream_t st, unsigned long long* stats = nullptr, int tau_widen = 0);
 // stages of fic_launch_rgb_encode on their own, over g.planes images: scaleImageRGB and the collage of the rows in `out`

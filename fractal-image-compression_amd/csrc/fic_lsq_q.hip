@@ -87,6 +87,10 @@
 // real row, and the group of lanes of a range block includes the lane that holds row 0 of the chunk's first tile.
 //
 // Cross-lane exchange: __shfl_xor (ds_bpermute) in B = 16's slow path and once at the end; ballots and LDS otherwise.
+//
+// Shared code (fic_lsq_q_tile.h): the prep's fragment packers, the f16 pair / maximum helpers, the constants, the flagged mask
+// and B = 16's rounds (theta from tau, group minimum); fic_lsq_q_chunks.h: the launcher's chunk conditions.  The wave decode, the
+// publish merge and the statistics are written out here and in fic_lsq_rgb_q.hip alike: shared, they cost sweep time (4.21).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -94,14 +98,10 @@
 #include "fic_launch.h"
 #include "fic_devfn.h"
 #include "fic_lsq_fit.h"
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "fic_lsq_q_chunks.h"
+#include "fic_lsq_q_tile.h"
 
 #define FIC_LSQ_Q_ECOEF 7.0e-4f            // >= 2^-10.5 (fic_q.hip's coefficient); + B * 2^-14 for flushed subnormals
-#define FIC_LSQ_Q_EABS 1.6e-5f
-#define FIC_LSQ_Q_NEVER 3.0e38f            // theta "never flagged": padding columns, and range blocks with an exact hit
 #define FIC_LSQ_Q_QFLUSH 192               // B = 4 / 8: the queue is evaluated once it holds this many pairs (and after every domain tile)
 #define FIC_LSQ_Q_WPG 4                    // waves per workgroup (independent: no barrier, no shared memory)
 
@@ -127,18 +127,11 @@ struct LsqQArgs {
     float tau_safety, tau_widen;
 };
 
-__device__ __forceinline__ int lsq_q_f16_pair(float lo, float hi)
-{
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(int, v);
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_lsq_q_prep : after k_pool, k_range (copies) and k_lsq_stat.  Workgroups [0, ndtiles): the A fragments of one domain tile
 // (32 pool blocks); [ndtiles, ndtiles + nct_alloc): the B fragments of one column tile (32 columns; zeros past N_r);
 // the rest: R and Er of 256 range blocks each.  Fragment slot (m, lane) holds elements [16 m + 8 (lane >> 5), +8) of row /
-// column lane & 31 (frag_slot of fic_q.hip, the 32x32x16 shape).
+// column lane & 31 (fic_lsq_q_tile.h packs a slot).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lsq_q_prep(const uint8_t* __restrict__ pool_pix, const u32x4* __restrict__ lsq_pool,
                                                     const uint32_t* __restrict__ rng_pix, const u32x2* __restrict__ lsq_rng,
@@ -158,14 +151,7 @@ __global__ __launch_bounds__(256) void k_lsq_q_prep(const uint8_t* __restrict__ 
                 if (ds.z != 0u) {
                     const float w = __fdiv_rn(1.0f, __fmul_rn((float)g.B, __uint_as_float(ds.w)));
                     const uint2 pw = *(const uint2*)(pool_pix + ((size_t)plane * g.Nd_pad + d) * g.n + p0);
-                    float x[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        const int px = (int)(((u < 4 ? pw.x : pw.y) >> (8 * (u & 3))) & 0xffu);
-                        x[u] = __fmul_rn((float)((px << g.lgn) - (int)ds.x), w);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) v[u] = lsq_q_f16_pair(x[2 * u], x[2 * u + 1]);
+                    v = lsq_q_pack_pool(pw.x, pw.y, g.lgn, (int)ds.x, w);
                 }
             }
             poolQ[((size_t)plane * ndtiles + bx) * NK * 64 + t] = v;
@@ -182,12 +168,7 @@ __global__ __launch_bounds__(256) void k_lsq_q_prep(const uint8_t* __restrict__ 
             if (j < g.Nr) {
                 const int S_r = (int)lsq_rng[(size_t)plane * g.Nr_pad + j].x;
                 const int mr = (2 * S_r + g.n) >> (g.lgn + 1);
-                const uint32_t w0 = rp[rng_word_index(g, j, k, p0 / 4)], w1 = rp[rng_word_index(g, j, k, p0 / 4 + 1)];
-                float x[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) x[u] = (float)((int)(((u < 4 ? w0 : w1) >> (8 * (u & 3))) & 0xffu) - mr);
-#pragma unroll
-                for (int u = 0; u < 4; u++) v[u] = lsq_q_f16_pair(x[2 * u], x[2 * u + 1]);
+                v = lsq_q_pack_range(rp[rng_word_index(g, j, k, p0 / 4)], rp[rng_word_index(g, j, k, p0 / 4 + 1)], mr);
             }
             rngQ[((size_t)plane * nct_alloc + ct) * NK * 64 + t] = v;
         }
@@ -208,19 +189,8 @@ __global__ __launch_bounds__(256) void k_lsq_q_prep(const uint8_t* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // k_sweep_lsq_q<NK, CSHIFT> : NK = n / 16 K-steps of v_mfma_f32_32x32x16_f16 per tile; 2^CSHIFT = n_iso columns per range block.
 // A wave owns CTW column tiles (their B fragments stay in VGPRs) and one pool chunk; it streams the chunk's domain tiles.
-// Accumulator element e of lane l: column l & 31, domain row (e & 3) + 8 (e >> 2) + 4 (l >> 5) of the tile.
+// Accumulator element e of lane l: column l & 31, domain row lsq_q_row(e, l >> 5) of the tile (fic_lsq_q_tile.h).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float lsq_q_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float lsq_q_max16_abs(const v16f& a)
-{
-    const float m0 = lsq_q_max3(fabsf(a[0]), fabsf(a[1]), fabsf(a[2]));
-    const float m1 = lsq_q_max3(fabsf(a[3]), fabsf(a[4]), fabsf(a[5]));
-    const float m2 = lsq_q_max3(fabsf(a[6]), fabsf(a[7]), fabsf(a[8]));
-    const float m3 = lsq_q_max3(fabsf(a[9]), fabsf(a[10]), fabsf(a[11]));
-    const float m4 = lsq_q_max3(fabsf(a[12]), fabsf(a[13]), fabsf(a[14]));
-    return lsq_q_max3(lsq_q_max3(m0, m1, m2), lsq_q_max3(m3, m4, fabsf(a[15])), 0.0f);
-}
-
 template <int NK, int CSHIFT>
 __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_lsq_q(LsqQArgs A)
 {
@@ -273,17 +243,20 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
     const float invB = NK == 1 ? 0.25f : (NK == 4 ? 0.125f : 0.0625f);
     unsigned st_tiles = 0, st_flagged = 0, st_pairs = 0;
 
-    // theta (and tau) of the column of tile ci from E_best > 0 of its range block: the chain of the header
+    // tau from 10^4 T = Ti >= 0: k_sweep_lsq_fast's chain, bit for bit
+    auto tau_chain = [&](long long Ti) __attribute__((always_inline)) {
+        return __fmul_rn(__fmul_rn(__fmul_rn(__fsqrt_rn((float)Ti), 0.01f), A.tau_safety), A.tau_widen);
+    };
+    // the queue's theta (and tau) of the column of tile ci from E_best > 0 of its range block: the chain of the header
     auto raise_theta = [&](int ci, long long Eg, float& tau_out) __attribute__((always_inline)) {
         const long long Ti = 10000ll * (long long)R[ci] - (Eg << g.lgn);        // 10^4 T, exact
         if (Ti < 0) {
             theta[ci] = -1.0f;
             tau_out = -1.0f;
         } else {
-            // tau: k_sweep_lsq_fast's chain, bit for bit; theta's minuend is tau / B (exact)
-            tau_out = __fmul_rn(__fmul_rn(__fmul_rn(__fsqrt_rn((float)Ti), 0.01f), A.tau_safety), A.tau_widen);
-            const float th = __fsub_rn(__fmul_rn(tau_out, invB), Er[ci]);
-            theta[ci] = th < 0.0f ? __fmul_rn(th, 1.00000023841857910156f) : th;    // a < Er: rounded away from zero (header)
+            tau_out = tau_chain(Ti);
+            const float th = __fsub_rn(__fmul_rn(tau_out, invB), Er[ci]);       // tau / B is exact
+            theta[ci] = th < 0.0f ? __fmul_rn(th, FIC_LSQ_Q_AWAY) : th;         // a < Er: rounded away from zero (header)
         }
     };
 
@@ -307,16 +280,7 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
     }
     // entries of one (domain tile, column tile): pool block relative to the chunk | column in wave << 22, in rounds of e
     auto push_tile = [&](const v16f& acc, int ci, int dt) __attribute__((always_inline)) {
-        uint32_t hm = 0;
-#pragma unroll
-        for (int e = 0; e < 16; e++) hm |= !(fabsf(acc[e]) <= theta[ci]) ? 1u << e : 0u;
-        const int nreal = g.Nd - dt * 32;                      // real rows of this tile (>= 1)
-        if (nreal < 32) {
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if ((e & 3) + 8 * (e >> 2) + 4 * half >= nreal) hm &= ~(1u << e);
-        }
-        if (!((okbits >> ci) & 1u)) hm = 0;
+        const uint32_t hm = lsq_q_flagged(acc, theta[ci], g.Nd - dt * 32, half, (okbits >> ci) & 1u);
         if (__builtin_amdgcn_ballot_w64(hm != 0) == 0) return;
         st_flagged++;
         dirty |= 1u << ci;
@@ -326,7 +290,7 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
             const bool mine = (hm >> e) & 1u;
             const unsigned long long b = __builtin_amdgcn_ballot_w64(mine);
             if (b == 0) continue;
-            if (mine) myq[qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] = ent0 + (uint32_t)((e & 3) + 8 * (e >> 2));
+            if (mine) myq[qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] = ent0 + (uint32_t)lsq_q_row(e, 0);
             qn += __builtin_popcountll(b);
         }
     };
@@ -407,57 +371,19 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
             bC = c;
         }
     };
-    // minimum over the lanes that share a range block: the two lane halves and the 2^CSHIFT adjacent columns
-    auto group_min_E = [&](long long e) __attribute__((always_inline)) {
-        long long o = __shfl_xor(e, 32, 64);
-        e = o < e ? o : e;
-        if constexpr (CSHIFT == 3) {
-#pragma unroll
-            for (int off = 1; off <= 4; off <<= 1) {
-                o = __shfl_xor(e, off, 64);
-                e = o < e ? o : e;
-            }
-        }
-        return e;
-    };
-    // A tile with |acc| above theta somewhere: evaluate what is flagged, then raise theta (header, "Ties")
+    // A tile with |acc| above theta somewhere: evaluate what is flagged, then raise theta (header, "Ties" and "Within a tile")
     auto slow_tile = [&](const v16f& acc, int ci, int dt) __attribute__((always_inline)) {
-        uint32_t hm = 0;
-#pragma unroll
-        for (int e = 0; e < 16; e++) hm |= !(fabsf(acc[e]) <= theta[ci]) ? 1u << e : 0u;
-        const int nreal = g.Nd - dt * 32;                      // real rows of this tile (>= 1)
-        if (nreal < 32) {
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if ((e & 3) + 8 * (e >> 2) + 4 * half >= nreal) hm &= ~(1u << e);
-        }
-        if (!((okbits >> ci) & 1u)) hm = 0;
+        const bool ok = (okbits >> ci) & 1u;
+        const uint32_t hm = lsq_q_flagged(acc, theta[ci], g.Nd - dt * 32, half, ok);
         if (__builtin_amdgcn_ballot_w64(hm != 0) == 0) return;
         st_flagged++;
         st_pairs += (unsigned)__builtin_popcount(hm);
-        // Round e takes element e of every lane: rows (e & 3) + 8 (e >> 2) and, in the other lane half, 4 more.  After a round tau
-        // is refined from the smallest E of the range block so far PLUS ONE (header, "Within a tile").
-        float tl = tau[ci];
-        long long bE = best_E[ci];
-        uint32_t bC = best_c[ci];
-#pragma unroll 1
-        for (int e = 0; e < 16; e++) {
-            const bool mine = (hm >> e) & 1u;
-            if (__builtin_amdgcn_ballot_w64(mine) == 0) continue;
-            if (mine) evaluate(ci, dt * 32 + (e & 3) + 8 * (e >> 2) + 4 * half, tl, bE, bC);
-            const long long E1 = group_min_E(bE);
-            if (E1 != FIC_LSQ_E_NONE) {
-                const long long Ti1 = 10000ll * (long long)R[ci] - ((E1 + 1) << g.lgn);
-                if (Ti1 >= 0) tl = fmaxf(tl, __fmul_rn(__fmul_rn(__fmul_rn(__fsqrt_rn((float)Ti1), 0.01f), A.tau_safety), A.tau_widen));
-            }
-        }
-        best_E[ci] = bE;
-        best_c[ci] = bC;
-        const long long Eg = group_min_E(best_E[ci]);
-        if (((okbits >> ci) & 1u) && Eg != FIC_LSQ_E_NONE) {
-            if (Eg == 0) theta[ci] = FIC_LSQ_Q_NEVER;        // exact hit
-            else raise_theta(ci, Eg, tau[ci]);
-        }
+        lsq_q_rounds<CSHIFT>(hm, dt * 32, half, ok, Er[ci], invB, theta[ci], tau[ci], best_E[ci], best_c[ci],
+                             [&](int d, float tl, long long& bE, uint32_t& bC) __attribute__((always_inline)) { evaluate(ci, d, tl, bE, bC); },
+                             [&](long long E) __attribute__((always_inline)) {           // tau of a smallest error E, -1 where T < 0
+                                 const long long Ti = 10000ll * (long long)R[ci] - (E << g.lgn);
+                                 return Ti < 0 ? -1.0f : tau_chain(Ti);
+                             });
     };
 
     // ---- the sweep -----------------------------------------------------------------------------
@@ -481,7 +407,7 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
                 for (int m = 0; m < NK; m++)
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ac[m]), __builtin_bit_cast(f16x8, rb[ci][m]), acc, 0, 0, 0);
                 st_tiles++;
-                const float mx = lsq_q_max16_abs(acc);
+                const float mx = max16_abs(acc);
                 if (__builtin_amdgcn_ballot_w64(!(mx <= theta[ci])) != 0) {
                     if constexpr (QUEUE) {
                         push_tile(acc, ci, dt);
@@ -540,8 +466,6 @@ __global__ __launch_bounds__(64 * FIC_LSQ_Q_WPG, NK == 1 ? 2 : 1) void k_sweep_l
 
 // host-side
 int fic_lsq_q_ct(int B) { return FIC_LSQ_Q_WPG * lsq_q_ctw(B * B / 16); }
-// B = 4 / 8: a chunk's candidates are numbered in 22 bits beside E in the 64-bit minimum
-int fic_lsq_q_max_tiles_per_chunk(int B, int n_iso) { return B == 16 ? (1 << 26) : (1 << 17) / n_iso; }
 
 int fic_launch_lsq_q_prep(const FicBuffers& b, const FicLsq& q, const FicLsqQ& s, const FicGeom& g, int eshift, hipStream_t st)
 {
@@ -558,8 +482,7 @@ int fic_launch_sweep_lsq_q(const FicBuffers& b, const FicLsq& q, const FicLsqQ& 
 {
     const int CT = fic_lsq_q_ct(g.B);
     if (!g.full || (g.B != 4 && g.B != 8 && g.B != 16) || (g.n_iso != 1 && g.n_iso != 8)) return -1;
-    if (ct_begin < 0 || ct_end <= ct_begin || ct_end > s.nct_alloc || tiles_per_chunk < 1 || nchunks < 1 ||
-        (long long)tiles_per_chunk * (nchunks - 1) >= s.ndtiles || (long long)tiles_per_chunk * nchunks < s.ndtiles ||
+    if (ct_begin < 0 || ct_end <= ct_begin || ct_end > s.nct_alloc || !lsq_q_chunks_cover(s.ndtiles, tiles_per_chunk, nchunks) ||
         tiles_per_chunk > fic_lsq_q_max_tiles_per_chunk(g.B, g.n_iso))
         return -1;
     LsqQArgs A;

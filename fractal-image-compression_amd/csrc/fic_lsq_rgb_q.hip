@@ -72,7 +72,7 @@
 // Minima.  Colour E is below 2^50, so a 64-bit key (E << 22) | c_rel does not exist.  Each lane keeps its own (E, c) pair, c the
 // global candidate in 32 bits, compared lexicographically; the lanes of a range block are merged by xor-shuffles (lane halves,
 // and the 8 adjacent columns with 8 isometries).  No atomics, no cap on a chunk's length; the only cap is N_d * n_iso <= 2^32 - 2
-// (fic_lsq_rgb_q_chunks.h).  The (E, c) order is total, so the merged minimum does not depend on lanes, rounds or chunks.
+// (fic_lsq_q_chunks.h).  The (E, c) order is total, so the merged minimum does not depend on lanes, rounds or chunks.
 //
 // Survivors.  All three block sizes evaluate the flagged pairs of a tile in its own lanes, in 16 rounds (accumulator element e of
 // every lane), the scheme the grey sweep keeps for B = 16: with per-lane minima a queue that hands a pair to ANY lane would need
@@ -96,6 +96,11 @@
 // Registers.  B fragments of the wave's CTW = 4 / 2 / 1 column tiles stay in VGPRs (48 / 96 / 192 per lane).  A fragments are
 // streamed in groups of G = min(NK, 12) K-steps with the next group in flight (at B = 16: 4 groups per domain tile), so that
 // 192 + 2 * 48 + 16 stay inside the 512-entry unified file at one wave per SIMD.
+//
+// Shared code (fic_lsq_q_tile.h): the prep's fragment packers, the f16 pair / maximum helpers, the constants, the flagged mask
+// and the 16 rounds (theta from tau, group minimum); fic_lsq_q_chunks.h: the chunk plan and the launcher's chunk conditions.
+// The wave decode, the publish merge and the statistics are written out here and in fic_lsq_q.hip alike: shared, they cost
+// sweep time.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -103,22 +108,14 @@
 #include "fic_launch.h"
 #include "fic_devfn.h"
 #include "fic_lsq_rgb_fit.h"
-#include "fic_lsq_rgb_q_chunks.h"
+#include "fic_lsq_q_chunks.h"
+#include "fic_lsq_q_tile.h"
 
-#ifndef FIC_LSQ_E_NONE
-#define FIC_LSQ_E_NONE 0x7FFFFFFFFFFFFFFFll
-#endif
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
 #define FIC_LSQ_RGB_Q_ECOEF 7.0e-4f            // >= 2^-11 (1 + 2^-10) + 2^-22 with 2.1e-4 to spare (header)
 #define FIC_LSQ_RGB_Q_EACC 1.1e-6f             // per K-step: >= 17 * 2^-24 * (1 + 2^-10)
 #define FIC_LSQ_RGB_Q_ESUB 1.0575e-4f          // per unit of B: >= sqrt(3) * 2^-14 (subnormal entries, kept or flushed)
-#define FIC_LSQ_RGB_Q_EABS 1.6e-5f
-#define FIC_LSQ_RGB_Q_NEVER 3.0e38f            // theta "never flagged": padding columns, and range blocks with an exact hit
 
 __host__ __device__ constexpr int lsq_rgb_q_ctw_nk(int NK) { return NK == 3 ? 4 : (NK == 12 ? 2 : 1); }
 
@@ -141,13 +138,6 @@ struct LsqRgbQArgs {
     float tau_safety, tau_widen;
 };
 
-__device__ __forceinline__ int lsq_rgb_q_f16_pair(float lo, float hi)
-{
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(int, v);
-}
-
 // rng3[plane][tile][k][w][lane], j = tile * 64 + lane (fic_lsq_rgb.hip's store)
 __device__ __forceinline__ size_t lsq_rgb_q_rng3_index(int n_iso, int DW3, int j, int k, int w)
 {
@@ -163,8 +153,8 @@ __device__ __forceinline__ long long lsq_rgb_q_cross(const uint32_t S_r[3], cons
 // ---------------------------------------------------------------------------------------------
 // k_lsq_rgb_q_prep : after k_lsq_rgb_prep.  Workgroups [0, ndtiles): the A fragments of one domain tile (32 pool blocks);
 // [ndtiles, ndtiles + nct): the B fragments of one column tile (32 columns; zeros past N_r); the rest: R and Er of 256 range
-// blocks each.  Fragment slot (m, lane) holds elements [16 m + 8 (lane >> 5), +8) of row / column lane & 31 (frag_slot of
-// fic_q.hip, the 32x32x16 shape); 8 consecutive elements lie in one channel (n is a multiple of 16).
+// blocks each.  Fragment slot (m, lane) holds elements [16 m + 8 (lane >> 5), +8) of row / column lane & 31
+// (fic_lsq_q_tile.h packs a slot); 8 consecutive elements lie in one channel (n is a multiple of 16).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lsq_rgb_q_prep(const uint8_t* __restrict__ pool3, const u32x8* __restrict__ pool_st,
                                                         const uint32_t* __restrict__ rng3, const u32x4* __restrict__ rng_st,
@@ -186,14 +176,7 @@ __global__ __launch_bounds__(256) void k_lsq_rgb_q_prep(const uint8_t* __restric
                     const float w = __fdiv_rn(1.0f, __fmul_rn((float)B, __uint_as_float(ds[5])));
                     const int Sd = (int)ds[p0 >> lgn];
                     const uint2 pw = *(const uint2*)(pool3 + (plane * Nd_pad + d) * (size_t)(3 * n) + p0);
-                    float x[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        const int px = (int)(((u < 4 ? pw.x : pw.y) >> (8 * (u & 3))) & 0xffu);
-                        x[u] = __fmul_rn((float)((px << lgn) - Sd), w);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) v[u] = lsq_rgb_q_f16_pair(x[2 * u], x[2 * u + 1]);
+                    v = lsq_q_pack_pool(pw.x, pw.y, lgn, Sd, w);
                 }
             }
             poolQ[(plane * ndtiles + bx) * NK * 64 + t] = v;
@@ -214,11 +197,7 @@ __global__ __launch_bounds__(256) void k_lsq_rgb_q_prep(const uint8_t* __restric
                 const int mr = (2 * S_r + n) >> (lgn + 1);
                 const uint32_t w0 = rp[lsq_rgb_q_rng3_index(n_iso, DW3, j, k, p0 / 4)];
                 const uint32_t w1 = rp[lsq_rgb_q_rng3_index(n_iso, DW3, j, k, p0 / 4 + 1)];
-                float x[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) x[u] = (float)((int)(((u < 4 ? w0 : w1) >> (8 * (u & 3))) & 0xffu) - mr);
-#pragma unroll
-                for (int u = 0; u < 4; u++) v[u] = lsq_rgb_q_f16_pair(x[2 * u], x[2 * u + 1]);
+                v = lsq_q_pack_range(w0, w1, mr);
             }
             rngQ[(plane * nct + ct) * NK * 64 + t] = v;
         }
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(256) void k_lsq_rgb_q_prep(const uint8_t* __restric
         }
         const float c = __fadd_rn(__fadd_rn(FIC_LSQ_RGB_Q_ECOEF, __fmul_rn((float)NK, FIC_LSQ_RGB_Q_EACC)),
                                   __fmul_rn((float)B, FIC_LSQ_RGB_Q_ESUB));
-        const float er = __fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), c), FIC_LSQ_RGB_Q_EABS);
+        const float er = __fadd_rn(__fmul_rn(__fsqrt_rn((float)ss), c), FIC_LSQ_Q_EABS);
         rngE[plane * Nr_pad + j] = __fmul_rn(er, __int_as_float((127 - eshift) << 23));
         // n S_rr may pass 2^32 at B = 16; R < 2^31.6, so the difference modulo 2^32 is R: stored unsigned
         rngR[plane * Nr_pad + j] = (rs.w << lgn) - rs.x * rs.x - rs.y * rs.y - rs.z * rs.z;
@@ -245,19 +224,8 @@ __global__ __launch_bounds__(256) void k_lsq_rgb_q_prep(const uint8_t* __restric
 // ---------------------------------------------------------------------------------------------
 // k_sweep_lsq_rgb_q<NK, CSHIFT> : NK = 3 n / 16 K-steps of v_mfma_f32_32x32x16_f16 per tile; 2^CSHIFT = n_iso columns per range
 // block.  A wave owns CTW column tiles (their B fragments stay in VGPRs) and one pool chunk; it streams the chunk's domain tiles.
-// Accumulator element e of lane l: column l & 31, domain row (e & 3) + 8 (e >> 2) + 4 (l >> 5) of the tile.
+// Accumulator element e of lane l: column l & 31, domain row lsq_q_row(e, l >> 5) of the tile (fic_lsq_q_tile.h).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float lsq_rgb_q_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float lsq_rgb_q_max16_abs(const v16f& a)
-{
-    const float m0 = lsq_rgb_q_max3(fabsf(a[0]), fabsf(a[1]), fabsf(a[2]));
-    const float m1 = lsq_rgb_q_max3(fabsf(a[3]), fabsf(a[4]), fabsf(a[5]));
-    const float m2 = lsq_rgb_q_max3(fabsf(a[6]), fabsf(a[7]), fabsf(a[8]));
-    const float m3 = lsq_rgb_q_max3(fabsf(a[9]), fabsf(a[10]), fabsf(a[11]));
-    const float m4 = lsq_rgb_q_max3(fabsf(a[12]), fabsf(a[13]), fabsf(a[14]));
-    return lsq_rgb_q_max3(lsq_rgb_q_max3(m0, m1, m2), lsq_rgb_q_max3(m3, m4, fabsf(a[15])), 0.0f);
-}
-
 template <int NK, int CSHIFT>
 __global__ __launch_bounds__(64 * FIC_LSQ_RGB_Q_WPG, 1) void k_sweep_lsq_rgb_q(LsqRgbQArgs A)
 {
@@ -305,28 +273,18 @@ __global__ __launch_bounds__(64 * FIC_LSQ_RGB_Q_WPG, 1) void k_sweep_lsq_rgb_q(L
         rbase[ci] = (uint32_t)lsq_rgb_q_rng3_index(A.n_iso, DW3, ok ? j : 0, k, 0);   // < 2^32 words per plane (the launcher checks)
         best_E[ci] = FIC_LSQ_E_NONE;
         best_c[ci] = 0xFFFFFFFFu;
-        theta[ci] = ok ? -1.0f : FIC_LSQ_RGB_Q_NEVER;
+        theta[ci] = ok ? -1.0f : FIC_LSQ_Q_NEVER;
         tau[ci] = -1.0f;
         okbits |= ok ? 1u << ci : 0u;
     }
     const float invB = NK == 3 ? 0.25f : (NK == 12 ? 0.125f : 0.0625f);
     unsigned st_tiles = 0, st_flagged = 0, st_pairs = 0;
 
-    // tau from 10^6 T = Ti >= 0: k_sweep_lsq_rgb_fast's chain, bit for bit
-    auto tau_of = [&](long long Ti) __attribute__((always_inline)) {
-        return __fmul_rn(__fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.001f), A.tau_safety), A.tau_widen);
-    };
-    // theta (and tau) of the column of tile ci from E_best > 0 of its range block: the chain of the header
-    auto raise_theta = [&](float er, uint32_t Rr, long long Eg, float& theta_out, float& tau_out) __attribute__((always_inline)) {
-        const long long Ti = 1000000ll * (long long)Rr - (Eg << A.lgn);         // 10^6 T, exact
-        float ta = -1.0f, th = -1.0f;
-        if (Ti >= 0) {
-            ta = tau_of(Ti);
-            th = __fsub_rn(__fmul_rn(ta, invB), er);                            // tau / B is exact
-            th = th < 0.0f ? __fmul_rn(th, 1.00000023841857910156f) : th;       // a < Er: rounded away from zero (header)
-        }
-        theta_out = th;
-        tau_out = ta;
+    // tau of the column of tile ci from a smallest error E of its range block, -1 where T < 0: k_sweep_lsq_rgb_fast's chain, bit
+    // for bit; theta follows from it by lsq_q_theta (the chain of the header)
+    auto tau_of = [&](int ci, long long E) __attribute__((always_inline)) {
+        const long long Ti = 1000000ll * (long long)R[ci] - (E << A.lgn);       // 10^6 T, exact
+        return Ti < 0 ? -1.0f : __fmul_rn(__fmul_rn(__fmul_rn(sqrtf((float)Ti), 0.001f), A.tau_safety), A.tau_widen);
     };
     // exact evaluation of (column of tile ci, pool block d): the arithmetic of k_sweep_lsq_rgb_fast / _generic
     auto evaluate = [&](int ci, int d, float tl, long long& bE, uint32_t& bC) __attribute__((always_inline)) {
@@ -362,57 +320,16 @@ __global__ __launch_bounds__(64 * FIC_LSQ_RGB_Q_WPG, 1) void k_sweep_lsq_rgb_q(L
             bC = c;
         }
     };
-    // minimum over the lanes that share a range block: the two lane halves and the 2^CSHIFT adjacent columns
-    auto group_min_E = [&](long long e) __attribute__((always_inline)) {
-        long long o = __shfl_xor(e, 32, 64);
-        e = o < e ? o : e;
-        if constexpr (CSHIFT == 3) {
-#pragma unroll
-            for (int off = 1; off <= 4; off <<= 1) {
-                o = __shfl_xor(e, off, 64);
-                e = o < e ? o : e;
-            }
-        }
-        return e;
-    };
-    // A tile with |acc| above theta somewhere: evaluate what is flagged, then raise theta (header, "Ties")
+    // A tile with |acc| above theta somewhere: evaluate what is flagged, then raise theta (header, "Ties" and "Within a tile")
     auto slow_tile = [&](const v16f& acc, int ci, int dt) __attribute__((always_inline)) {
-        uint32_t hm = 0;
-#pragma unroll
-        for (int e = 0; e < 16; e++) hm |= !(fabsf(acc[e]) <= theta[ci]) ? 1u << e : 0u;
-        const int nreal = A.Nd - dt * 32;                      // real rows of this tile (>= 1)
-        if (nreal < 32) {
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if ((e & 3) + 8 * (e >> 2) + 4 * half >= nreal) hm &= ~(1u << e);
-        }
-        if (!((okbits >> ci) & 1u)) hm = 0;
+        const bool ok = (okbits >> ci) & 1u;
+        const uint32_t hm = lsq_q_flagged(acc, theta[ci], A.Nd - dt * 32, half, ok);
         if (__builtin_amdgcn_ballot_w64(hm != 0) == 0) return;
         st_flagged++;
         st_pairs += (unsigned)__builtin_popcount(hm);
-        float tl = tau[ci];
-        long long bE = best_E[ci];
-        uint32_t bC = best_c[ci];
-#pragma unroll 1
-        for (int e = 0; e < 16; e++) {
-            const bool mine = (hm >> e) & 1u;
-            if (__builtin_amdgcn_ballot_w64(mine) == 0) continue;
-            if (mine) evaluate(ci, dt * 32 + (e & 3) + 8 * (e >> 2) + 4 * half, tl, bE, bC);
-            const long long E1 = group_min_E(bE);
-            if (E1 != FIC_LSQ_E_NONE) {                        // header, "Within a tile": from E_best + 1
-                const long long Ti1 = 1000000ll * (long long)R[ci] - ((E1 + 1) << A.lgn);
-                if (Ti1 >= 0) tl = fmaxf(tl, tau_of(Ti1));
-            }
-        }
-        best_E[ci] = bE;
-        best_c[ci] = bC;
-        const long long Eg = group_min_E(bE);
-        if (((okbits >> ci) & 1u) && Eg != FIC_LSQ_E_NONE) {
-            float th = FIC_LSQ_RGB_Q_NEVER, ta = tau[ci];      // Eg == 0: exact hit
-            if (Eg != 0) raise_theta(Er[ci], R[ci], Eg, th, ta);
-            theta[ci] = th;
-            tau[ci] = ta;
-        }
+        lsq_q_rounds<CSHIFT>(hm, dt * 32, half, ok, Er[ci], invB, theta[ci], tau[ci], best_E[ci], best_c[ci],
+                             [&](int d, float tl, long long& bE, uint32_t& bC) __attribute__((always_inline)) { evaluate(ci, d, tl, bE, bC); },
+                             [&](long long E) __attribute__((always_inline)) { return tau_of(ci, E); });
     };
 
     // ---- the sweep -----------------------------------------------------------------------------
@@ -446,7 +363,7 @@ __global__ __launch_bounds__(64 * FIC_LSQ_RGB_Q_WPG, 1) void k_sweep_lsq_rgb_q(L
         for (int ci = 0; ci < CTW; ci++) {
             if (ci < nci) {
                 st_tiles++;
-                const float mx = lsq_rgb_q_max16_abs(acc[ci]);
+                const float mx = max16_abs(acc[ci]);
                 if (__builtin_amdgcn_ballot_w64(!(mx <= theta[ci])) != 0) slow_tile(acc[ci], ci, dt);
             }
         }
@@ -507,9 +424,7 @@ int fic_launch_sweep_lsq_rgb_q(const FicLsqRgb& q, const FicLsqRgbQ& s, const Fi
     if ((long long)g.Nd * g.n_iso > 0xFFFFFFFEll) return -1;                       // c in 32 bits beside "none"
     if ((long long)q.Nr_pad * g.n_iso * 3 * g.DW >= (1ll << 32)) return -1;        // rbase: dword offsets within a plane
     if (s.ndtiles != (g.Nd + 31) / 32 || s.nct != (int)(((long long)g.Nr * g.n_iso + 31) / 32)) return -1;
-    if (tiles_per_chunk < 1 || nchunks < 1 || nchunks > FIC_LSQ_RGB_Q_MAX_CHUNKS ||
-        (long long)tiles_per_chunk * (nchunks - 1) >= s.ndtiles || (long long)tiles_per_chunk * nchunks < s.ndtiles)
-        return -1;
+    if (nchunks > FIC_LSQ_RGB_Q_MAX_CHUNKS || !lsq_q_chunks_cover(s.ndtiles, tiles_per_chunk, nchunks)) return -1;
     const int CT = FIC_LSQ_RGB_Q_WPG * lsq_rgb_q_ctw(g.B);
     LsqRgbQArgs A;
     A.pool3 = (const uint8_t*)q.pool3;

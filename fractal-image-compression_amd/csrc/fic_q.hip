@@ -57,6 +57,7 @@
 #include "fic_device.h"
 #include "fic_launch.h"
 #include "fic_devfn.h"
+#include "fic_lsq_q_tile.h"                // f16_pair, max3f, max16_abs: shared with the least-squares sweeps
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -120,14 +121,6 @@ __device__ __forceinline__ void frag_slot(int shape16, int NK, int s, int lane, 
 // bound of the header bit for bit).  Negative values widen the threshold (more pairs flagged, same codebooks); positive values
 // narrow it below the derivation and give WRONG codebooks -- tests/test_gpu_q_bound.py shows that the suite notices.
 __device__ __forceinline__ float q_escale(const FicGeom& g) { return __int_as_float((127 - g.q_eshift) << 23); }
-
-// two floats -> packed f16 pair (round to nearest even), element 0 in the low half
-__device__ __forceinline__ int f16_pair(float lo, float hi)
-{
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(int, v);
-}
 
 // ---------------------------------------------------------------------------------------------
 // k_pool_q : one workgroup per domain tile (32 consecutive pool blocks).  createCodebuch FC:1015-1050 (block k = (c,r) at
@@ -663,18 +656,7 @@ __device__ __forceinline__ v16f mfma_f16(v4i a, v4i b, v16f c)
 {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-// Every node is a three-input maximum (v_max3_f32 with |.| source modifiers): a two-input fmaxf of MFMA results costs two
-// extra canonicalising v_max_f32 x, x under IEEE mode, hence the constant 0 as third operand at the root.
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float max16_abs(const v16f& a)
-{
-    const float m0 = max3f(fabsf(a[0]), fabsf(a[1]), fabsf(a[2]));
-    const float m1 = max3f(fabsf(a[3]), fabsf(a[4]), fabsf(a[5]));
-    const float m2 = max3f(fabsf(a[6]), fabsf(a[7]), fabsf(a[8]));
-    const float m3 = max3f(fabsf(a[9]), fabsf(a[10]), fabsf(a[11]));
-    const float m4 = max3f(fabsf(a[12]), fabsf(a[13]), fabsf(a[14]));
-    return max3f(max3f(m0, m1, m2), max3f(m3, m4, fabsf(a[15])), 0.0f);
-}
+// max3f / max16_abs (fic_lsq_q_tile.h): every node a three-input maximum, v_max3_f32 with |.| source modifiers
 // MODE 2: |even| + |odd| per element, then the maximum
 __device__ __forceinline__ float max16_sum(const v16f& a, const v16f& b)
 {

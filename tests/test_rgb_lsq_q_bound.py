@@ -331,18 +331,18 @@ def test_the_tie_image_is_what_it_claims(oracle, n_iso):
 
 
 def test_chunk_arithmetic_under_the_sanitizers(tmp_path):
-    """tests/cpp/lsq_rgb_q_chunks_test.cpp: fic_lsq_rgb_q_chunks.h (what the launcher and the C ABI call) as a program of its own,
-    with the host compiler's address and undefined-behaviour sanitizers where it has their runtimes."""
-    src = os.path.join(ROOT, "tests", "cpp", "lsq_rgb_q_chunks_test.cpp")
+    """tests/cpp/lsq_q_chunks_test.cpp: fic_lsq_q_chunks.h (what the launchers and the C ABI call) as a program of its own, with
+    the host compiler's address and undefined-behaviour sanitizers where it has their runtimes."""
+    src = os.path.join(ROOT, "tests", "cpp", "lsq_q_chunks_test.cpp")
     probe = tmp_path / "probe.cpp"
     probe.write_text("int main() { return 0; }\n")
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
     ok = subprocess.run(["g++"] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode == 0
     if not ok or subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
         san = []
-    print("lsq_rgb_q_chunks_test built " + ("with " + san[0] if san else "WITHOUT sanitizers (the host compiler has no runtimes for them)"))
-    exe = str(tmp_path / "lsq_rgb_q_chunks_test")
+    print("lsq_q_chunks_test built " + ("with " + san[0] if san else "WITHOUT sanitizers (the host compiler has no runtimes for them)"))
+    exe = str(tmp_path / "lsq_q_chunks_test")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror"] + san + [src, "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "lsq_q_chunks.txt")], capture_output=True, text=True)
     assert r.returncode == 0 and "\n0 failures" in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr
