@@ -5,6 +5,7 @@
 // error state, geometry and every stream writer / parser: fic_stream.cpp)
 #include "fic_internal.h"
 #include "fic_lsq_q_chunks.h"
+#include "fic_sweep_chunks.h"
 
 namespace ficd {
 
@@ -25,32 +26,6 @@ bool create_device_ok(int device)
     return true;
 }
 
-int sweep_stats_option(DevMem& mem, unsigned long long*& stats, int on, hipStream_t last_stream)
-{
-    if (on && !stats) {
-        int rc = mem.ensure_zeroed(stats, 8, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
-    } else if (!on && stats) {
-        HIP_TRY(hipStreamSynchronize(last_stream));
-        mem.release(stats);
-    }
-    return FIC_OK;
-}
-
-int sweep_stats_read(const char* who, unsigned long long* stats, int device, hipStream_t last_stream, uint64_t* out8, int reset)
-{
-    if (!stats) return fail(FIC_E_STATE, "%s: set the option \"sweep_stats\" first", who);
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamSynchronize(last_stream));
-    HIP_TRY(hipMemcpy(out8, stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) {
-        HIP_TRY(hipMemset(stats, 0, 8 * sizeof(uint64_t)));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-    }
-    return FIC_OK;
-}
-
 IdleCache<fic_ctx, 16> g_idle_grey;
 
 }  // namespace ficd
@@ -59,91 +34,14 @@ using namespace ficd;
 
 fic_ctx::~fic_ctx()
 {
+    if (!own_stream) return;
     (void)hipSetDevice(device);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
+    (void)hipStreamDestroy(own_stream);
 }
 
 namespace {
 
-int flush_events(fic_ctx* c)
-{
-    for (size_t i = 0; i + 1 < c->ev.size(); i += 2) {
-        HIP_TRY(hipEventSynchronize(c->ev[i + 1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-        c->acc_ms += ms;
-        c->acc_n += 1;
-        (void)hipEventDestroy(c->ev[i]);
-        (void)hipEventDestroy(c->ev[i + 1]);
-    }
-    c->ev.clear();
-    return FIC_OK;
-}
-
-// ---- sweep orchestration helpers (used by fic_ctx_encode) ------------------------------------------------------
-
-// Stream rule of the handle API (include/fic.h): an encode on stream `s` takes over the context.  On the stream of the encode
-// before it this is one pointer comparison; on another one the host waits for the earlier encode first, since stream order no
-// longer keeps the two apart.  (The multi-device entry sets last_stream itself, after its own wait: fic_capi_multi.cpp.)
-int order_after_last_encode(fic_ctx* c, hipStream_t s)
-{
-    if (s != c->last_stream) {
-        if (c->stream_used) HIP_TRY(hipStreamSynchronize(c->last_stream));
-        c->last_stream = s;
-    }
-    c->stream_used = true;
-    return FIC_OK;
-}
-
-// "time_sweep": bracket the sweep launch with events on its stream; durations are read later by flush_events.
-int time_begin(fic_ctx* c, hipStream_t s)
-{
-    if (!c->opt_time) return FIC_OK;
-    if (c->ev.size() >= 256) {                     // bound the pending list: fold finished launches into the accumulators
-        int rc = flush_events(c);
-        if (rc) return rc;
-    }
-    hipEvent_t e0 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    c->ev.push_back(e0);
-    HIP_TRY(hipEventRecord(e0, s));
-    return FIC_OK;
-}
-int time_end(fic_ctx* c, hipStream_t s)
-{
-    if (!c->opt_time) return FIC_OK;
-    hipEvent_t e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e1));
-    c->ev.push_back(e1);
-    HIP_TRY(hipEventRecord(e1, s));
-    return FIC_OK;
-}
-
-// Pool chunks per range tile for the VALU sweeps (k_sweep_fast, k_sweep_d4).  Measured (profiles/r01l_chunk_sweep.txt):
-// every chunk pays a start-up (its first block is evaluated exactly and tau restarts), so chunks stay >= 4096 blocks
-// while aiming at ~48 K wave tasks for load balance; only a launch that could not otherwise fill the chip (one small
-// image) splits finer.  `base_waves` = wave tasks per chunk.  (k_sweep_lsq_fast pays more per start-up -- its epilogue is
-// 64-bit integer work -- and asks for `target` = 6144 wave tasks, about one resident round: profiles/lsq_timing.txt.)
-int valu_chunk_count(const fic_ctx* c, long long base_waves, long long target = 49152)
-{
-    const FicGeom& g = c->g;
-    int nchunks = c->opt_chunks;
-    if (nchunks <= 0) {
-        long long want = (target + base_waves - 1) / base_waves;
-        long long cap = g.Nd / 4096;
-        if (cap < 1) cap = 1;
-        long long nc = want < cap ? want : cap;
-        if (base_waves * nc < 4096) {
-            long long cap2 = g.Nd / 512;
-            if (cap2 < 1) cap2 = 1;
-            long long fill = (4096 + base_waves - 1) / base_waves;
-            nc = fill < cap2 ? fill : cap2;
-        }
-        nchunks = (int)(nc < 1 ? 1 : nc);
-    }
-    return nchunks > g.Nd ? g.Nd : nchunks;
-}
+// ---- sweep orchestration helpers (used by fic_ctx_encode); the pool-chunk rules are fic_sweep_chunks.h's --------------------
 
 // VALU sweep k_sweep_fast ("sweep" = 2) over tiles [tile0, tile0 + ntiles).
 int valu_sweep(fic_ctx* c, int tile0, int ntiles, hipStream_t s, int* nchunks_out)
@@ -151,12 +49,9 @@ int valu_sweep(fic_ctx* c, int tile0, int ntiles, hipStream_t s, int* nchunks_ou
     const FicGeom& g = c->g;
     int NR, NC;
     fic_fast_variant(g.B, g.n_iso, &NR, &NC);
-    int nchunks = valu_chunk_count(c, (long long)ntiles * (g.n_iso / NC) * g.planes);
-    int chunk_len = (g.Nd + nchunks - 1) / nchunks;
-    chunk_len = (chunk_len + 1) & ~1;              // even: the sweep consumes blocks in pairs
-    nchunks = (g.Nd + chunk_len - 1) / chunk_len;
-    if (fic_launch_sweep_fast(c->b, g, tile0, ntiles, chunk_len, nchunks, s)) return fail(FIC_E_HIP, "k_sweep_fast launch failed");
-    *nchunks_out = nchunks;
+    const SweepChunks k = valu_chunks(g.Nd, (long long)ntiles * (g.n_iso / NC) * g.planes, c->opt_chunks, FIC_VALU_CHUNK_TARGET, true);
+    if (fic_launch_sweep_fast(c->b, g, tile0, ntiles, k.len, k.nchunks, s)) return fail(FIC_E_HIP, "k_sweep_fast launch failed");
+    *nchunks_out = k.nchunks;
     return FIC_OK;
 }
 
@@ -175,12 +70,10 @@ int d4_prep(fic_ctx* c, hipStream_t s)
 int d4_sweep(fic_ctx* c, int tile0, int ntiles, hipStream_t s, int* nchunks_out)
 {
     const FicGeom& g = c->g;
-    int nchunks = valu_chunk_count(c, (long long)ntiles * g.planes);
-    const int chunk_len = (g.Nd + nchunks - 1) / nchunks;
-    nchunks = (g.Nd + chunk_len - 1) / chunk_len;
-    if (fic_launch_sweep_d4(c->b, c->d4_rng, c->d4_pool, g, tile0, ntiles, chunk_len, nchunks, s))
+    const SweepChunks k = valu_chunks(g.Nd, (long long)ntiles * g.planes, c->opt_chunks, FIC_VALU_CHUNK_TARGET, false);
+    if (fic_launch_sweep_d4(c->b, c->d4_rng, c->d4_pool, g, tile0, ntiles, k.len, k.nchunks, s))
         return fail(FIC_E_HIP, "k_sweep_d4 launch failed");
-    *nchunks_out = nchunks;
+    *nchunks_out = k.nchunks;
     return FIC_OK;
 }
 
@@ -255,26 +148,9 @@ int matrix_core_sweep(fic_ctx* c, int kind, int tile0, int tile1, hipStream_t s,
     const FicGeom& g = c->g;
     const MatrixCoreShape m = matrix_core_shape(g, kind);
     const int tsz = 64 * g.NR;
-    int nchunks = c->opt_chunks;
-    if (nchunks <= 0) {
-        const long long ranges = (long long)(tile1 - tile0) * tsz;
-        const long long per_wg = m.iso8 ? m.G8 : 32LL * m.ct1;
-        const long long base_wg = (ranges + per_wg - 1) / per_wg * g.planes;   // workgroups per chunk
-        long long want = (4096 + base_wg - 1) / base_wg;                       // ~4 resident per CU x 256 CUs x 4
-        long long cap = m.ndtiles / 256;                                       // >= 256 domain tiles per chunk: start-up < 10 %
-        if (cap < 1) cap = 1;
-        long long nc = want < cap ? want : cap;
-        if (base_wg * nc < 1024) {                                             // one small image: fill the chip first,
-            long long cap2 = m.ndtiles / 32;                                   // even at a higher per-chunk start-up share
-            if (cap2 < 1) cap2 = 1;
-            long long fill = (1024 + base_wg - 1) / base_wg;
-            nc = fill < cap2 ? fill : cap2;
-        }
-        nchunks = (int)(nc < 1 ? 1 : nc);
-    }
-    if (nchunks > m.ndtiles) nchunks = m.ndtiles;
-    const int tiles_per_chunk = (m.ndtiles + nchunks - 1) / nchunks;
-    nchunks = (m.ndtiles + tiles_per_chunk - 1) / tiles_per_chunk;
+    const long long ranges = (long long)(tile1 - tile0) * tsz, per_wg = m.iso8 ? m.G8 : 32LL * m.ct1;
+    const SweepChunks k = xcheck_chunks(m.ndtiles, (ranges + per_wg - 1) / per_wg * g.planes, c->opt_chunks);
+    const int tiles_per_chunk = k.len, nchunks = k.nchunks;
     if (m.iso8) {
         const int g0 = (tile0 * tsz) / m.G8, g1 = (tile1 * tsz + m.G8 - 1) / m.G8;   // groups covering the tile span
         const int rc = m.bf16 ? fic_launch_sweep_bf16(c->b, c->mfma_poolB, c->mfma_sw, c->mfma_rngA, g, m.ngroups8 * (m.G8 / 4), g0,
@@ -345,34 +221,9 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
     const int tsz = 64 * g.NR;
     const int cpr = fic_q_cols_per_range(g.B, g.n_iso);
     const int ct_begin = tile0 * tsz * cpr / 32, ct_end = tile1 * tsz * cpr / 32;
-    int nchunks = c->opt_chunks;
-    if (nchunks <= 0) {
-        // Two reasons to split the pool into chunks, each with its own price (a chunk starts with theta unset: until its
-        // first good candidate has been evaluated every pair of every tile is queued -- tens of tiles' worth of work):
-        //  fill:    fewer workgroups than the chip holds at once (`resident`): split until two rounds of them exist, but
-        //           keep >= 30 (8 isometries) / 14 (1 isometry) tiles per chunk;
-        //  balance: the kernel ends with its slowest wave, and one round of equally long waves leaves ~25 % of the
-        //           wave-cycles idle (profiles/r02w_chunk_count_sweep.txt): aim for 8 rounds, but only with chunks long
-        //           enough (>= 1024 tiles) that the start-up is noise.
-        const long long base_wg = (long long)((ct_end - ct_begin + q.CT - 1) / q.CT) * g.planes;
-        const long long resident = 256LL * fic_q_resident(g.B);
-        auto ceil_div = [](long long a, long long b) { return (a + b - 1) / b; };
-        // (one image, profiles/r03n_single_image_chunk_count_sweep.json: a chunk restarts theta, and what that costs against
-        //  the parallelism it buys depends on the columns per range block -- with 8 isometries chunks below ~30 domain tiles
-        //  lose (512x512: 0.086 ms per encode at 16 chunks, 0.092-0.094 at 28), with 1 isometry 14-tile chunks still gain
-        //  (0.060 at 35 chunks, 0.061 at 28, 0.076 at 16))
-        const long long min_tiles = g.n_iso == 8 ? 30 : 14;
-        long long fill = base_wg < resident ? ceil_div(2 * resident, base_wg) : 1;
-        if (fill > q.ndtiles / min_tiles) fill = q.ndtiles / min_tiles;
-        long long bal = ceil_div(8 * resident, base_wg);
-        if (bal > q.ndtiles / 1024) bal = q.ndtiles / 1024;
-        const long long nc = fill > bal ? fill : bal;
-        nchunks = (int)(nc < 1 ? 1 : nc);
-    }
-    if (nchunks > q.ndtiles) nchunks = q.ndtiles;
-    int tiles_per_chunk = (q.ndtiles + nchunks - 1) / nchunks;
-    tiles_per_chunk = (tiles_per_chunk + q.unroll - 1) / q.unroll * q.unroll;     // whole iterations of the unrolled sweep loop
-    nchunks = (q.ndtiles + tiles_per_chunk - 1) / tiles_per_chunk;
+    const SweepChunks k = q_chunks(q.ndtiles, (long long)((ct_end - ct_begin + q.CT - 1) / q.CT) * g.planes, 256LL * fic_q_resident(g.B),
+                                   q_min_tiles_grey(g.n_iso), q.unroll, c->opt_chunks);
+    const int tiles_per_chunk = k.len, nchunks = k.nchunks;
     if (fused_fin) {                                   // one counter per (plane, column group); the sweep leaves them at zero
         const int rc = c->mem.ensure_zeroed(c->q_fin, (size_t)g.planes * (q.nct_alloc / q.CT + 1), s);
         if (rc) return rc;
@@ -407,10 +258,9 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     if (kind == 2) {
         int NR, NC;
         fic_fast_variant(g.B, g.n_iso, &NR, &NC);
-        nchunks = valu_chunk_count(c, (long long)ntiles * (g.n_iso / NC) * g.planes, 6144);
-        chunk_len = (g.Nd + nchunks - 1) / nchunks;
-        chunk_len = (chunk_len + 1) & ~1;              // even: the sweep consumes blocks in pairs
-        nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
+        const SweepChunks k = valu_chunks(g.Nd, (long long)ntiles * (g.n_iso / NC) * g.planes, c->opt_chunks, FIC_LSQ_FAST_CHUNK_TARGET, true);
+        chunk_len = k.len;
+        nchunks = k.nchunks;                           // no empty chunk: every slot gets written
         nslots = fic_lsq_slots(g, nchunks);
     }
     int ct_begin = 0, ct_end = 0, tiles_per_chunk = 0;
@@ -430,16 +280,8 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.rng, P * g.Nr_pad * 8);
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.E, P * g.Nr * 8);
     if (rc) return rc;
-    if (c->lsq_slots < (size_t)nslots) {
-        HIP_TRY(hipStreamSynchronize(c->last_stream));
-        c->mem.release(c->lsq.slotE);
-        c->mem.release(c->lsq.slotC);
-        c->lsq_slots = 0;
-        rc = c->mem.ensure(c->lsq.slotE, P * nslots * g.Nr_pad * 8);
-        if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.slotC, P * nslots * g.Nr_pad);
-        if (rc) return rc;
-        c->lsq_slots = (size_t)nslots;
-    }
+    rc = grow_lsq_slots(c, c->lsq.slotE, c->lsq.slotC, (size_t)nslots, P * nslots * g.Nr_pad * 8, P * nslots * g.Nr_pad);
+    if (rc) return rc;
     if (fic_launch_scale(c->b.gray, c->b.scaled, g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
     if (fic_launch_pool(c->b.scaled, c->b.pool_pix, c->b.pool_st, c->b.pool_var, c->b.pool_s64, g, s))
         return fail(FIC_E_HIP, "k_pool launch failed");
@@ -456,7 +298,7 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
         if (rc) return rc;
         if (fic_launch_lsq_q_prep(c->b, c->lsq, c->lsqq, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_q_prep launch failed");
     }
-    rc = time_begin(c, s);
+    rc = c->timer.begin(s);
     if (rc) return rc;
     if (kind == 7) {
         if (fic_launch_sweep_lsq_q(c->b, c->lsq, c->lsqq, g, ct_begin, ct_end, tiles_per_chunk, nchunks, s, c->q_stats, c->opt_lsq_widen))
@@ -466,7 +308,7 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_fast launch failed");
     }
-    rc = time_end(c, s);
+    rc = c->timer.end(s);
     if (rc) return rc;
     if (fic_launch_finalize_lsq(c->b, c->o, c->lsq, nslots, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_finalize_lsq launch failed");
     c->last_chunks = nchunks;
@@ -630,7 +472,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     // another stream than the last encode's: scratch stores, keys and outputs are shared, so the new work starts after the old
-    if (int rc = order_after_last_encode(c, s)) return rc;
+    if (int rc = take_stream(c, s)) return rc;
     if (range_count == 0) return FIC_OK;
     if (c->opt_search == 1) return lsq_encode(c, range_begin, range_count, s);
 
@@ -694,7 +536,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
         if (kind == 5) rc = d4_prep(c, s);
         else if (kind >= 3) rc = matrix_core_prep(c, kind, s);          // fragment prep belongs to pool build / range prep: not timed
     }
-    if (rc == FIC_OK) rc = time_begin(c, s);
+    if (rc == FIC_OK) rc = c->timer.begin(s);
     if (rc == FIC_OK) {
         if (kind == 1) {
             if (fic_launch_sweep_generic(c->b, g, range_begin, range_count, s)) rc = fail(FIC_E_HIP, "k_sweep_generic launch failed");
@@ -708,7 +550,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
             rc = valu_sweep(c, tile0, tile1 - tile0, s, &nchunks);
         }
     }
-    if (rc == FIC_OK) rc = time_end(c, s);
+    if (rc == FIC_OK) rc = c->timer.end(s);
     if (rc != FIC_OK) return rc;
     c->last_chunks = nchunks;
     c->last_kind = kind;
@@ -724,10 +566,7 @@ int fic_ctx_encode(fic_ctx* c, int range_begin, int range_count, void* hip_strea
 int fic_ctx_sync(fic_ctx* c)
 {
     if (!c) return fail(FIC_E_ARGUMENT, "fic_ctx_sync: null context");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    c->stream_used = false;                            // nothing pending: the caller may destroy that stream, the next encode waits for nothing
-    return FIC_OK;
+    return ctx_sync(c);
 }
 
 int fic_ctx_get_results_host(fic_ctx* c, int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows,
@@ -836,10 +675,9 @@ int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
     } else if (!strcmp(name, "q_noflag")) {            // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
         c->opt_noflag = value ? 1 : 0;
     } else if (!strcmp(name, "time_sweep")) {
-        c->opt_time = value ? 1 : 0;
+        c->timer.on = value ? 1 : 0;
     } else if (!strcmp(name, "sweep_stats")) {
-        HIP_TRY(hipSetDevice(c->device));
-        return sweep_stats_option(c->mem, c->q_stats, value, c->last_stream);
+        return sweep_stats_option(c, c->q_stats, value);
     } else {
         return fail(FIC_E_ARGUMENT, "unknown option '%s'", name);
     }
@@ -851,19 +689,14 @@ int fic_ctx_sweep_time(fic_ctx* c, double* total_ms, int* launches, int reset)
     if (!c) return fail(FIC_E_ARGUMENT, "fic_ctx_sweep_time: null context");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = flush_events(c);
-    if (rc) return rc;
-    if (total_ms) *total_ms = c->acc_ms;
-    if (launches) *launches = c->acc_n;
-    if (reset) { c->acc_ms = 0.0; c->acc_n = 0; }
-    return FIC_OK;
+    return c->timer.read(total_ms, launches, reset);
 }
 
 int fic_ctx_sweep_stats(fic_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_ctx_sweep_stats: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    return sweep_stats_read("fic_ctx_sweep_stats", c->q_stats, c->device, c->last_stream, out8, reset);
+    return sweep_stats_read(c, "fic_ctx_sweep_stats", c->q_stats, out8, reset);
 }
 
 int fic_ctx_info(fic_ctx* c, int* out10)
@@ -957,17 +790,8 @@ int fic_ctx_debug_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int
 {
     if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: null argument");
     if (!c->encoded_any || !c->q_pool) return fail(FIC_E_STATE, "fic_ctx_debug_q_host: no encode through the default sweep (\"sweep\" = 6) yet");
-    if (which < 0 || which > 5) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_q_host: which must be 0..5");
     const void* const stores[6] = {c->q_pool, c->q_flat, c->q_rng, c->q_E, c->b.rng_st, c->q_rngC};
-    const void* src = stores[which];
-    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
-    *size = (int64_t)bytes;
-    if (!out) return FIC_OK;
-    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_q_host: %zu bytes needed", bytes);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return FIC_OK;
+    return debug_store_host(c, "fic_ctx_debug_q_host", stores, 6, which, out, capacity, size);
 }
 
 int fic_ctx_debug_lsq_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
@@ -975,17 +799,8 @@ int fic_ctx_debug_lsq_q_host(fic_ctx* c, int which, void* out, int64_t capacity,
     if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_lsq_q_host: null argument");
     if (!c->encoded_any || !c->lsqq.poolQ)
         return fail(FIC_E_STATE, "fic_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
-    if (which < 0 || which > 3) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_lsq_q_host: which must be 0..3");
     const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
-    const void* src = stores[which];
-    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
-    *size = (int64_t)bytes;
-    if (!out) return FIC_OK;
-    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_ctx_debug_lsq_q_host: %zu bytes needed", bytes);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return FIC_OK;
+    return debug_store_host(c, "fic_ctx_debug_lsq_q_host", stores, 4, which, out, capacity, size);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // fic_capi_rgb.cpp -- C ABI, joint-RGB path: encodeRGB (FC:171-219) as one-shot entry and as batched device-resident
 // contexts (fic_rgb_ctx_*), decodeRGB from a context's codebook (on the decode job of fic_capi_decode.cpp).  Host-side orchestration only.
 #include "fic_internal.h"
+#include "fic_sweep_chunks.h"
 
 using namespace ficd;
 
@@ -35,30 +36,15 @@ void rgb_plane(const fic_rgb_ctx* c, int p, FicRgbBuffers* b, FicRgbOutputs* o)
     o->qrows = c->qrows + P * nr * 5;
     o->iso = c->iso ? c->iso + P * nr : nullptr;
 }
-// pool chunks of the matrix-core full search: the policy of the grey q sweep (fic_capi.cpp, q_sweep), or the "chunks" option
+// pool chunks of the matrix-core full search: fic_sweep_chunks.h's rule of k_sweep_q (one image at a time), or the "chunks" option
 void rgb_q_chunks(fic_rgb_ctx* c)
 {
     const FicGeom& g = c->g;
-    FicRgbQ& q = c->q;
-    const int unroll = fic_q_unroll(g.B, 1), CT = fic_q_ct(g.B);
+    const int CT = fic_q_ct(g.B);
     const int nct = (int)(((long long)g.Nr * g.n_iso + 31) / 32);       // n_iso = 8: 8 columns per range block
-    long long nc = c->opt_chunks;
-    if (nc <= 0) {
-        const long long base_wg = (nct + CT - 1) / CT;
-        const long long resident = 256LL * fic_q_resident(g.B);
-        auto ceil_div = [](long long a, long long b) { return (a + b - 1) / b; };
-        long long fill = base_wg < resident ? ceil_div(2 * resident, base_wg) : 1;
-        if (fill > q.ndtiles / 16) fill = q.ndtiles / 16;
-        long long bal = ceil_div(8 * resident, base_wg);
-        if (bal > q.ndtiles / 1024) bal = q.ndtiles / 1024;
-        nc = fill > bal ? fill : bal;
-    }
-    if (nc < 1) nc = 1;
-    if (nc > q.ndtiles) nc = q.ndtiles;
-    int tpc = (int)((q.ndtiles + nc - 1) / nc);
-    tpc = (tpc + unroll - 1) / unroll * unroll;
-    q.tiles_per_chunk = tpc;
-    q.nchunks = (q.ndtiles + tpc - 1) / tpc;
+    const SweepChunks k = q_chunks(c->q.ndtiles, (nct + CT - 1) / CT, 256LL * fic_q_resident(g.B), FIC_RGB_Q_MIN_TILES, fic_q_unroll(g.B, 1), c->opt_chunks);
+    c->q.tiles_per_chunk = k.len;
+    c->q.nchunks = k.nchunks;
 }
 // buffers of the matrix-core full search (same shapes as the grey q sweep)
 int rgb_q_setup(fic_rgb_ctx* c)
@@ -147,7 +133,7 @@ int fic_rgb_ctx_set_argb_host(fic_rgb_ctx* c, const int32_t* argb)
     HIP_TRY(hipSetDevice(c->device));
     const size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
     if (int rc = c->mem.ensure(c->argb_own, npix)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));     // a previous encode may still read the copy
+    HIP_TRY(hipStreamSynchronize(c->last_stream));     // an earlier encode may still read the copy
     HIP_TRY(hipMemcpy(c->argb_own, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
     c->argb = c->argb_own;
     c->have_input = true;
@@ -172,13 +158,9 @@ int fic_rgb_ctx_encode(fic_rgb_ctx* c, int with_collage, void* hip_stream)
     if (!c->have_input) return fail(FIC_E_STATE, "fic_rgb_ctx_encode: no input image set");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
-    const hipStream_t prev = c->last_stream;
-    const bool switched = c->stream_used && s != prev;    // an earlier encode, issued on another stream
-    c->last_stream = s;
-    c->stream_used = true;
-    if (c->opt_search == 1) return rgb_lsq_encode(c, with_collage, s, prev, switched);      // least squares
-    // scaled image, pool, keys and outputs are shared: the new work starts after the old
-    if (switched) HIP_TRY(hipStreamSynchronize(prev));
+    // scaled image, pool, stores, keys and outputs are shared with an earlier encode: on another stream the new work starts after it
+    if (int rc = take_stream(c, s)) return rc;
+    if (c->opt_search == 1) return rgb_lsq_encode(c, with_collage, s);      // least squares
     const FicGeom& g = c->g;
     // Full search: the matrix-core sweep where it pays (its prep costs ~50 us; the VALU sweep does ~1e11 pairs/s), or where
     // the VALU full-search kernel does not exist (B = 16).  FIC_RGB_SWEEP=1|2 / option "sweep" override.
@@ -250,12 +232,11 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         return FIC_OK;
     }
     if (!strcmp(name, "time_sweep")) {                 // event pairs around the least-squares sweep launch (fic_rgb_ctx_sweep_time)
-        c->opt_time = value ? 1 : 0;
+        c->timer.on = value ? 1 : 0;
         return FIC_OK;
     }
     if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
-        HIP_TRY(hipSetDevice(c->device));
-        return sweep_stats_option(c->mem, c->q.stats, value, c->last_stream);
+        return sweep_stats_option(c, c->q.stats, value);
     }
     return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: unknown option '%s'", name);
 }
@@ -266,18 +247,9 @@ int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capac
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->encoded_any || c->last_sweep != 2 || !c->q.poolQ)
         return fail(FIC_E_STATE, "fic_rgb_ctx_debug_q_host: no encode through the matrix-core sweep (\"sweep\" = 2) yet");
-    if (which < 0 || which > 5) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_q_host: which must be 0..5");
     const FicRgbQ& q = c->q;
-    const void* const stores[6] = {q.poolQ, q.dflat, q.rngQ, q.rngE, q.qst, q.amax};
-    const void* src = stores[which];
-    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them (last plane encoded)
-    *size = (int64_t)bytes;
-    if (!out) return FIC_OK;
-    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_rgb_ctx_debug_q_host: %zu bytes needed", bytes);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return FIC_OK;
+    const void* const stores[6] = {q.poolQ, q.dflat, q.rngQ, q.rngE, q.qst, q.amax};         // as of the last plane encoded
+    return debug_store_host(c, "fic_rgb_ctx_debug_q_host", stores, 6, which, out, capacity, size);
 }
 
 int fic_rgb_ctx_last_sweep(fic_rgb_ctx* c)
@@ -290,7 +262,7 @@ int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_stats: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    return sweep_stats_read("fic_rgb_ctx_sweep_stats", c->q.stats, c->device, c->last_stream, out8, reset);
+    return sweep_stats_read(c, "fic_rgb_ctx_sweep_stats", c->q.stats, out8, reset);
 }
 
 int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
@@ -322,10 +294,7 @@ int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
 int fic_rgb_ctx_sync(fic_rgb_ctx* c)
 {
     if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sync: null context");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    c->stream_used = false;                            // nothing pending: the caller may destroy that stream, the next encode waits for nothing
-    return FIC_OK;
+    return ctx_sync(c);
 }
 
 int fic_rgb_ctx_get_results_host(fic_rgb_ctx* c, int32_t* idx_local, float* a, float* bR, float* bG, float* bB, int32_t* qrows5,

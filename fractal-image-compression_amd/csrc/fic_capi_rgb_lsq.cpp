@@ -3,59 +3,17 @@
 // cached contexts.  The quadtree entries are in fic_capi_quadtree.cpp.  Host-side orchestration only.
 #include "fic_internal.h"
 #include "fic_lsq_q_chunks.h"
+#include "fic_sweep_chunks.h"
 
 using namespace ficd;
-
-fic_rgb_ctx::~fic_rgb_ctx()
-{
-    if (ev.empty()) return;
-    (void)hipSetDevice(device);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-}
-
-namespace {
-
-// "time_sweep" of a colour context: fic_capi.cpp's scheme.  Pairs of events bracket the sweep launch on its stream and are
-// read later; with the option off no event is created.
-int rgb_flush_events(fic_rgb_ctx* c)
-{
-    for (size_t i = 0; i + 1 < c->ev.size(); i += 2) {
-        HIP_TRY(hipEventSynchronize(c->ev[i + 1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-        c->acc_ms += ms;
-        c->acc_n += 1;
-        (void)hipEventDestroy(c->ev[i]);
-        (void)hipEventDestroy(c->ev[i + 1]);
-    }
-    c->ev.clear();
-    return FIC_OK;
-}
-int rgb_time_mark(fic_rgb_ctx* c, hipStream_t s, bool begin)
-{
-    if (!c->opt_time) return FIC_OK;
-    if (begin && c->ev.size() >= 256) {                // bound the pending list: fold finished launches into the accumulators
-        int rc = rgb_flush_events(c);
-        if (rc) return rc;
-    }
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreate(&e));
-    c->ev.push_back(e);
-    HIP_TRY(hipEventRecord(e, s));
-    return FIC_OK;
-}
-
-}  // namespace
 
 // scaleImageRGB as for the reference's search, then the planar byte stores and sums, k_sweep_lsq_rgb_generic (windows, B = 16,
 // "sweep" = 1) or k_sweep_lsq_rgb_fast (full search at B <= 8), k_finalize_lsq_rgb and the reference's collage of the rows.
 // Under "lsq_engine" = 1 a full search with "sweep" 0 or 2 at B = 4 / 8 / 16 runs k_sweep_lsq_rgb_q instead:
 // where the fast sweep would run at B <= 8, and where the automatic choice would take the generic kernel at B = 16 ("sweep" = 2
 // is accepted there only under this option).  "sweep" = 1, windows and "search" = 0 never see the option.
-int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev, bool switched)
+int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s)
 {
-    // the byte stores, sums, slots and outputs are shared with the earlier encode: the new work starts after it
-    if (switched) HIP_TRY(hipStreamSynchronize(prev));
     const FicGeom& g = c->g;
     int NC = 1;
     const bool fast_ok = g.full && fic_lsq_rgb_variant(g.B, g.n_iso, &NC) == 0;
@@ -71,15 +29,9 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     const size_t nrp = (size_t)q.Nr_pad;
     int nchunks = 1, chunk_len = g.Nd, nslots = 1;
     if (kind == 2) {
-        // about one resident round of waves (6144 wave tasks), chunks of 16 pool blocks or more; "chunks" overrides
-        const long long tasks = (long long)(q.Nr_pad / 64) * (g.n_iso / NC) * g.planes;
-        long long nc = c->opt_chunks > 0 ? c->opt_chunks : (6144 + tasks - 1) / tasks;
-        const long long cap = c->opt_chunks > 0 ? g.Nd : (g.Nd / 16 > 1 ? g.Nd / 16 : 1);
-        if (nc > cap) nc = cap;
-        if (nc > 4096) nc = 4096;
-        if (nc < 1) nc = 1;
-        chunk_len = (int)((g.Nd + nc - 1) / nc);
-        nchunks = (g.Nd + chunk_len - 1) / chunk_len;  // no empty chunk: every slot gets written
+        const SweepChunks k = rgb_lsq_fast_chunks(g.Nd, (long long)(q.Nr_pad / 64) * (g.n_iso / NC) * g.planes, c->opt_chunks);
+        chunk_len = k.len;
+        nchunks = k.nchunks;                           // no empty chunk: every slot gets written
         nslots = fic_lsq_rgb_slots(g, nchunks);
     }
     LsqRgbQPlan plan{};
@@ -98,16 +50,8 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     if (rc == FIC_OK) rc = m.ensure_zeroed(q.rng_st, P * nrp * 16, s);
     if (rc == FIC_OK) rc = m.ensure(q.E, P * g.Nr * 8);
     if (rc) return rc;
-    if (c->lsq_slots < (size_t)nslots) {
-        HIP_TRY(hipStreamSynchronize(prev));             // an earlier encode, on whatever stream it ran, may still use the slots
-        m.release(q.slotE);
-        m.release(q.slotC);
-        c->lsq_slots = 0;
-        rc = m.ensure(q.slotE, P * nslots * nrp * 8);
-        if (rc == FIC_OK) rc = m.ensure(q.slotC, P * nslots * nrp);
-        if (rc) return rc;
-        c->lsq_slots = (size_t)nslots;
-    }
+    rc = grow_lsq_slots(c, q.slotE, q.slotC, (size_t)nslots, P * nslots * nrp * 8, P * nslots * nrp);
+    if (rc) return rc;
     FicRgbOutputs o;                                   // image 0 of the batch: the kernels take the image from their grid
     o.idx_local = c->idx_local; o.idx_global = c->idx_global; o.a = c->a; o.bR = c->bR; o.bG = c->bG; o.bB = c->bB;
     o.qrows = c->qrows; o.iso = c->iso;
@@ -123,7 +67,7 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
         if (rc) return rc;
         if (fic_launch_lsq_rgb_q_prep(q, f, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_rgb_q_prep launch failed");
     }
-    rc = rgb_time_mark(c, s, true);
+    rc = c->timer.begin(s);
     if (rc) return rc;
     if (kind == 7) {
         if (fic_launch_sweep_lsq_rgb_q(q, c->lsqq, g, plan.tiles_per_chunk, plan.nchunks, s, c->q.stats, c->opt_lsq_widen))
@@ -133,7 +77,7 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStr
     } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->q.stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_rgb_fast launch failed");
     }
-    rc = rgb_time_mark(c, s, false);
+    rc = c->timer.end(s);
     if (rc) return rc;
     if (fic_launch_finalize_lsq_rgb(o, q, nslots, g, s)) return fail(FIC_E_HIP, "k_finalize_lsq_rgb launch failed");
     if (with_collage && fic_launch_rgb_collage(c->scaled, o, c->collage, g, s)) return fail(FIC_E_HIP, "k_collage_rgb launch failed");
@@ -166,12 +110,7 @@ int fic_rgb_ctx_sweep_time(fic_rgb_ctx* c, double* total_ms, int* launches, int 
     if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_time: null context");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = rgb_flush_events(c);
-    if (rc) return rc;
-    if (total_ms) *total_ms = c->acc_ms;
-    if (launches) *launches = c->acc_n;
-    if (reset) { c->acc_ms = 0.0; c->acc_n = 0; }
-    return FIC_OK;
+    return c->timer.read(total_ms, launches, reset);
 }
 
 int fic_rgb_ctx_last_lsq_chunks(fic_rgb_ctx* c)
@@ -186,17 +125,8 @@ int fic_rgb_ctx_debug_lsq_q_host(fic_rgb_ctx* c, int which, void* out, int64_t c
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->encoded_any || !c->lsqq.poolQ)
         return fail(FIC_E_STATE, "fic_rgb_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
-    if (which < 0 || which > 3) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_lsq_q_host: which must be 0..3");
     const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
-    const void* src = stores[which];
-    const size_t bytes = c->mem.bytes_of(src);         // the stores exactly as the owner holds them
-    *size = (int64_t)bytes;
-    if (!out) return FIC_OK;
-    if (capacity < (int64_t)bytes) return fail(FIC_E_CAPACITY, "fic_rgb_ctx_debug_lsq_q_host: %zu bytes needed", bytes);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return FIC_OK;
+    return debug_store_host(c, "fic_rgb_ctx_debug_lsq_q_host", stores, 4, which, out, capacity, size);
 }
 
 int fic_encode_rgb_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local, float* a,

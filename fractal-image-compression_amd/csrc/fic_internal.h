@@ -1,5 +1,5 @@
-// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the two context types, the
-// idle-context caches of the one-shot entries, the "sweep_stats" counter block, the decode job and the release hooks; error
+// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the two context types and the
+// core they share (fic_ctx_core.cpp), the idle-context caches of the one-shot entries, the "sweep_stats" counter block, the decode job and the release hooks; error
 // reporting, geometry validation and the stream formats come with fic_stream.h, the ownership of device memory with
 // fic_devmem.h (the HIP runtime's allocation calls are made in fic_devmem.cpp and nowhere else).  Not part of the public
 // interface.
@@ -48,10 +48,49 @@ bool create_device_ok(int device);
 int encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device,
                    int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows);
 
-// The "sweep_stats" counter block of either context (fic_capi.cpp): 8 u64 device counters of k_sweep_q, held by the context's
-// owner.  The option switches it on (zeroed) or off; the read entry copies it out and may reset it.
-int sweep_stats_option(DevMem& mem, unsigned long long*& stats, int on, hipStream_t last_stream);
-int sweep_stats_read(const char* who, unsigned long long* stats, int device, hipStream_t last_stream, uint64_t* out8, int reset);
+// "time_sweep": event pairs bracket the sweep launch on its stream and are read later (fic_*_ctx_sweep_time).
+struct SweepTimer {
+    int on = 0;                      // the option; while it is off no event is created
+    std::vector<hipEvent_t> ev;      // pending pairs start/stop
+    double acc_ms = 0.0;
+    int acc_n = 0;
+    int begin(hipStream_t s);        // folds the pending list into the accumulators first once it holds 256 events
+    int end(hipStream_t s);
+    int flush();                     // waits for the pending pairs and adds them up
+    int read(double* total_ms, int* launches, int reset);
+};
+
+// What a context is apart from its pixels: fic_ctx and fic_rgb_ctx derive from it, the helpers below (fic_ctx_core.cpp) are
+// written once for both.
+struct CtxCore {
+    int device = 0;
+    FicGeom g;
+    DevMem mem;                      // owns every device and pinned pointer of the context
+    std::mutex mu;
+    bool have_input = false, encoded_any = false;
+    hipStream_t last_stream = nullptr;
+    bool stream_used = false;        // an encode was issued on last_stream (take_stream orders a stream switch after it)
+    SweepTimer timer;
+    size_t lsq_slots = 0;            // slots per plane the least-squares slot stores have room for
+    ~CtxCore();                      // the pending events; the memory goes with `mem`
+};
+
+// Stream rule of the handle API (include/fic.h), in this one place: an encode on stream `s` takes over the
+// context.  On the stream of the encode before it this is one pointer comparison; on another one the host waits for the earlier
+// encode first, since stream order no longer keeps the two apart.  Afterwards last_stream is `s` and nothing reads any other
+// stream.  (The multi-device entry sets last_stream itself, after its own wait: fic_capi_multi.cpp.)
+int take_stream(CtxCore* c, hipStream_t s);
+// fic_*_ctx_sync: waits for last_stream; nothing is pending then, the caller may destroy that stream
+int ctx_sync(CtxCore* c);
+// Room for `nslots` slots per plane in the two slot stores of a least-squares search (sizeE, sizeC as DevMem::ensure counts
+// them); growing waits for last_stream, whose sweep may still use the old stores
+int grow_lsq_slots(CtxCore* c, void*& slotE, uint32_t*& slotC, size_t nslots, size_t sizeE, size_t sizeC);
+// The fic_*_debug_*_host entries behind their own preconditions: store `which` of `stores` exactly as the owner holds it
+int debug_store_host(CtxCore* c, const char* who, const void* const* stores, int nstores, int which, void* out, int64_t capacity, int64_t* size);
+// The "sweep_stats" counter block of either context: 8 u64 device counters of k_sweep_q, held by the context's owner.  The
+// option switches it on (zeroed) or off; the read entry copies it out and may reset it.
+int sweep_stats_option(CtxCore* c, unsigned long long*& stats, int on);
+int sweep_stats_read(CtxCore* c, const char* who, unsigned long long* stats, uint64_t* out8, int reset);
 
 
 // device arena of a decode (fic_capi_decode.cpp): one allocation kept between calls, taken and given back by a DecodeJob
@@ -100,9 +139,8 @@ struct DecodeJob {
 };
 
 // The encode of a colour context under "search" = 1 (fic_capi_rgb_lsq.cpp); the caller holds the context's lock, has made its
-// device current and recorded the stream; `prev` is the stream of the context's encode before this one, `switched` says that
-// there was one and that it is another stream than `s`
-int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s, hipStream_t prev, bool switched);
+// device current and taken the stream (take_stream)
+int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s);
 
 // what fic_release_cache() frees besides the idle contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp
@@ -111,11 +149,8 @@ void release_comms();              // fic_capi_multi.cpp
 }  // namespace ficd
 
 // Device-resident working set of `planes` grey images of one geometry on one device (fic_ctx_* of include/fic.h).
-struct fic_ctx {
-    int device = 0;
-    FicGeom g;
-    ficd::DevMem mem;                // owns every device and pinned pointer below; b, o and lsq view what it holds
-    FicBuffers b;
+struct fic_ctx : ficd::CtxCore {
+    FicBuffers b;                    // b, o and lsq view what `mem` holds
     FicOutputs o;
     uint8_t* gray_own = nullptr;     // context-owned input copy
     int32_t* argb_stage = nullptr;   // staging for ARGB uploads
@@ -140,33 +175,21 @@ struct fic_ctx {
     uint32_t* d4_rng = nullptr;      // k_sweep_d4: range / domain slots of the group-Fourier form (n_iso = 8, B = 8 / 16)
     uint32_t* d4_pool = nullptr;
     FicLsq lsq{};                    // least-squares search ("search" = 1): statistics, per-chunk slots, the winners' E (on first use)
-    size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
     int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
     FicLsqQ lsqq{};                  // the matrix-core least-squares sweep ("lsq_engine" = 1): fragments, Er, R (on first use)
     int opt_lsq_engine = 0;          // option "lsq_engine": 0 k_sweep_lsq_fast, 1 k_sweep_lsq_q wherever the former would run
     int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, k_sweep_lsq_q's Er times 2^-value; > 0 gives WRONG codebooks
-    bool have_input = false;
-    bool encoded_any = false;
-    hipStream_t last_stream = nullptr;
-    bool stream_used = false;        // an encode was issued on last_stream (fic_ctx_encode orders a stream switch after it)
     hipStream_t own_stream = nullptr; // non-blocking stream of the multi-device entry (created on demand)
-    int opt_sweep = 0, opt_chunks = 0, opt_time = 0, opt_noflag = 0;
+    int opt_sweep = 0, opt_chunks = 0, opt_noflag = 0;
     int last_chunks = 0, last_kind = 0, last_fused = 0, last_tiles_per_chunk = 0;
-    std::vector<hipEvent_t> ev;      // pairs start/stop
-    double acc_ms = 0.0;
-    int acc_n = 0;
-    std::mutex mu;
-    ~fic_ctx();                      // events and the own stream (fic_capi.cpp); the memory goes with `mem`
+    ~fic_ctx();                      // the own stream (fic_capi.cpp)
 };
 
 // Device-resident working set of `planes` colour images of one geometry (fic_rgb_ctx_* of include/fic.h, fic_capi_rgb.cpp).
 // The kernels take the image from their grid: a batch is one launch per stage on the caller's stream (only the matrix-core
 // full search runs image by image).
-struct fic_rgb_ctx {
-    int device = 0;
-    FicGeom g;
-    ficd::DevMem mem;                // owns every device pointer below; q views what it holds
+struct fic_rgb_ctx : ficd::CtxCore {
     int32_t* argb_own = nullptr;     // context-owned input copy
     const int32_t* argb = nullptr;   // input in use (own copy or the caller's device pointer)
     int32_t* scaled = nullptr;       // per plane: [H/2][W/2]
@@ -188,7 +211,6 @@ struct fic_rgb_ctx {
     int opt_chunks = 0;              // pool chunks of the matrix-core sweep (0 = automatic)
     int last_sweep = 0;              // what the last encode ran: 1 / 2
     FicLsqRgb lsq;                   // least-squares search ("search" = 1): byte stores, sums, per-chunk slots, the winners' E (on first use)
-    size_t lsq_slots = 0;            // slots per plane the slot stores have room for
     int opt_search = 0, last_search = 0;
     int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
     int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast, 7 matrix cores (k_sweep_lsq_rgb_q)
@@ -196,15 +218,7 @@ struct fic_rgb_ctx {
     int opt_lsq_engine = 0;          // option "lsq_engine": 0 the VALU sweeps, 1 k_sweep_lsq_rgb_q where the full-search sweep would run
     int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, that sweep's Er times 2^-value; > 0 gives WRONG codebooks
     int last_lsq_chunks = 0;         // pool chunks of the last least-squares sweep
-    int opt_time = 0;                // option "time_sweep": event pairs around the least-squares sweep launch (fic_rgb_ctx_sweep_time)
-    std::vector<hipEvent_t> ev;      // pairs start/stop; none is created while the option is off
-    double acc_ms = 0.0;
-    int acc_n = 0;
-    bool have_input = false, encoded_any = false, have_collage = false;
-    hipStream_t last_stream = nullptr;
-    bool stream_used = false;        // an encode was issued on last_stream (fic_rgb_ctx_encode orders a stream switch after it)
-    std::mutex mu;
-    ~fic_rgb_ctx();                  // the events (fic_capi_rgb_lsq.cpp); the memory goes with `mem`
+    bool have_collage = false;
 };
 
 namespace ficd {
