@@ -162,6 +162,13 @@ def lib():
         "fic_encode_rgb_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_encode_rgb_quadtree_iso_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
         "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
+        "fic_encode_gray_quadtree_rd_u8": (C.c_int, [u8p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
+        "fic_encode_gray_quadtree_rd_argb": (C.c_int, [i32p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
+        "fic_encode_rgb_quadtree_rd_argb": (C.c_int, [i32p] + [C.c_int] * 7 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
+        "fic_encode_rgb_quadtree_iso_rd_argb": (C.c_int, [i32p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
+        "fic_debug_qt_rd_keys": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)] + [C.c_int] * 4 + [C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
+        "fic_debug_qt_select_weighted": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "fic_debug_live_memory": (C.c_int, [C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
@@ -876,3 +883,92 @@ def debug_qt_select(keys, rank, device=0):
     key, t, above = C.c_uint32(), C.c_float(), C.c_int64()
     check(lib().fic_debug_qt_select(device, ptr(k, C.c_uint32), k.size, int(rank), C.byref(key), C.byref(t), C.byref(above)))
     return key.value, np.float32(t.value), above.value
+
+
+# ---- quadtree encode by rate-distortion pruning -----------------------------------------------------------------
+QT_RD_LAMBDA, QT_RD_LEAVES, QT_RD_SSE = 0, 1, 2
+
+
+def _rd_goal(tag, n_iso, lam, max_leaves, max_bytes, max_sse):
+    """(goal, value) of an RD entry from the one keyword given."""
+    if sum(v is not None for v in (lam, max_leaves, max_bytes, max_sse)) != 1:
+        raise ValueError("pass exactly one of lam=, max_leaves=, max_bytes= and max_sse=")
+    if lam is not None:
+        goal, value = QT_RD_LAMBDA, int(lam)
+    elif max_sse is not None:
+        goal, value = QT_RD_SSE, int(max_sse)
+    else:
+        goal, value = QT_RD_LEAVES, int(max_leaves) if max_bytes is None else quadtree_leaves_for_bytes(tag, n_iso, max_bytes)
+    if not 0 <= value < 1 << 64:
+        raise FicError(-3, f"{('lam', 'max_leaves', 'max_sse')[goal]} = {value}: outside 0 .. 2^64 - 1")
+    return goal, value
+
+
+def _encode_rd(fn, head, search, goal, value, w, h, B_min, cols, device):
+    """One RD entry of the C ABI: (leaves int32 [n, cols], lambda int, stats uint64 [4] as QT_STATS_FIELDS)."""
+    cap = (w // B_min) * (h // B_min) if B_min > 0 and w > 0 and h > 0 else 1
+    out = np.zeros((max(cap, 1), cols), np.int32)
+    n, lam, stats = C.c_int(), C.c_uint32(), np.zeros(4, np.uint64)
+    check(fn(*head, search_id(search), goal, value, device, ptr(out, C.c_int32), out.shape[0], C.byref(n), C.byref(lam), ptr(stats, C.c_uint64)))
+    return out[:n.value].copy(), int(lam.value), stats
+
+
+def encode_gray_quadtree_rd(gray, B_max, B_min, wK=0, n_iso=1, search="reference", lam=None, max_leaves=None, max_bytes=None,
+                            max_sse=None, device=0):
+    """encode_gray_quadtree with the tree that minimises collage SSE + lam * leaves (fic_encode_gray_quadtree_rd_u8 / _argb).
+    Exactly one of: lam= (an integer 0 .. 2^32 - 1), max_leaves= / max_bytes= (a tag-2 stream; the smallest lam whose tree
+    fits), max_sse= (the tree of fewest leaves whose collage SSE is <= max_sse; T(0) when none is, see stats[0]).  Returns
+    (leaves [n, 7], lam, stats uint64 [4] = QT_STATS_FIELDS); the leaves go to write_run_quadtree unchanged."""
+    goal, value = _rd_goal(2, n_iso, lam, max_leaves, max_bytes, max_sse)
+    g = np.asarray(gray)
+    if g.dtype == np.uint8:
+        g = np.ascontiguousarray(g)
+        fn, p = lib().fic_encode_gray_quadtree_rd_u8, ptr(g, C.c_uint8)
+    else:
+        g = np.ascontiguousarray(g, np.int32)
+        fn, p = lib().fic_encode_gray_quadtree_rd_argb, ptr(g, C.c_int32)
+    h, w = g.shape
+    return _encode_rd(fn, (p, w, h, B_max, B_min, wK, n_iso), search, goal, value, w, h, B_min, 7, device)
+
+
+def encode_rgb_quadtree_rd(argb, w, h, B_max, B_min, wK=0, search="reference", lam=None, max_leaves=None, max_bytes=None, max_sse=None,
+                           device=0):
+    """encode_rgb_quadtree by rate-distortion pruning (tag 3; fic_encode_rgb_quadtree_rd_argb): (leaves [n, 8], lam, stats)."""
+    goal, value = _rd_goal(3, 1, lam, max_leaves, max_bytes, max_sse)
+    a = _argb_image(argb, w, h)
+    return _encode_rd(lib().fic_encode_rgb_quadtree_rd_argb, (ptr(a, C.c_int32), w, h, B_max, B_min, wK), search, goal, value, w, h, B_min, 8, device)
+
+
+def encode_rgb_quadtree_iso_rd(argb, w, h, B_max, B_min, wK=0, n_iso=8, search="reference", lam=None, max_leaves=None, max_bytes=None,
+                               max_sse=None, device=0):
+    """encode_rgb_quadtree_iso by rate-distortion pruning (tag 6; fic_encode_rgb_quadtree_iso_rd_argb): (leaves [n, 9], lam, stats)."""
+    goal, value = _rd_goal(6, n_iso, lam, max_leaves, max_bytes, max_sse)
+    a = _argb_image(argb, w, h)
+    return _encode_rd(lib().fic_encode_rgb_quadtree_iso_rd_argb, (ptr(a, C.c_int32), w, h, B_max, B_min, wK, n_iso), search, goal, value, w, h,
+                      B_min, 9, device)
+
+
+def debug_qt_rd_keys(sse, w, h, B_max, B_min, device=0):
+    """The pruning's keys and gains of the per-level SSE arrays `sse` ({B: uint32 [Rh, Rw]} as debug_quadtree_sse returns them):
+    (e uint32 [n], G int64 [n]), the blocks of B_max first, then those of B_max / 2 (fic_debug_qt_rd_keys)."""
+    levels = _qt_levels(B_max, B_min)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(sse[B]).astype(np.uint32).reshape(-1) for B in levels]))
+    if [np.asarray(sse[B]).size for B in levels] != [(h // B) * (w // B) for B in levels]:
+        raise FicError(-3, "the SSE arrays do not have the levels' sizes")
+    n = sum((h // B) * (w // B) for B in levels[:-1])
+    keys, gains = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int64)
+    check(lib().fic_debug_qt_rd_keys(device, ptr(flat, C.c_uint32), w, h, B_max, B_min, ptr(keys, C.c_uint32), ptr(gains, C.c_int64)))
+    return keys[:n], gains[:n]
+
+
+def debug_qt_select_weighted(keys, gains, need, device=0):
+    """The weighted select on (keys uint32 [n], gains int64 [n]): (the first boundary among the descending distinct keys and 0
+    at which the gain of the keys above it reaches `need`, the number of those keys, their gain) (fic_debug_qt_select_weighted)."""
+    k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+    g = np.ascontiguousarray(gains, np.int64).reshape(-1)
+    if g.size != k.size:
+        raise FicError(-3, "keys and gains differ in length")
+    key, above, gain = C.c_uint32(), C.c_int64(), C.c_int64()
+    check(lib().fic_debug_qt_select_weighted(device, ptr(k, C.c_uint32), ptr(g, C.c_int64), k.size, int(need), C.byref(key), C.byref(above),
+                                             C.byref(gain)))
+    return key.value, above.value, gain.value

@@ -100,14 +100,25 @@ struct QtBudget {
     uint64_t* stats4;        // NULL or {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4}
 };
 
+// Encode by rate-distortion pruning: the tree that minimises D + lambda N, lambda given (goal 0) or chosen on
+// the device from the SSE arrays of this encode: the smallest whose tree has at most `value` leaves (goal 1), or the smallest
+// that gives the tree of fewest leaves with a collage SSE <= `value` (goal 2).
+struct QtRd {
+    int goal;
+    uint64_t value;
+    uint32_t* lambda_out;    // the lambda in force (also set on FIC_E_CAPACITY)
+    uint64_t* stats4;        // as QtBudget's
+};
+
 // The encode behind fic_encode_*_quadtree_* and the SSE test hooks: every level through the one-shot contexts, then the
 // per-level SSE, the split and the compaction on the device.  leaves / sse_out may be NULL.  budget: NULL, or the threshold
-// comes from the budget's select instead of the argument.  search: the criterion of the per-level codebooks (0 the
+// comes from the budget's select instead of the argument.  rd: NULL, or the split rule is "e(v) > lambda" on the keys of the
+// pruning instead of the threshold's.  search: the criterion of the per-level codebooks (0 the
 // reference's, 1 least squares: DESIGN.md 4.19 grey, 4.20 colour); everything after them is the same code.
 template <typename Fmt>
 int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, float threshold,
               int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* sse_out, int64_t sse_capacity,
-              const QtBudget* budget = nullptr, int search = 0)
+              const QtBudget* budget = nullptr, int search = 0, const QtRd* rd = nullptr)
 {
     if (!gray && !argb) return fail(FIC_E_ARGUMENT, "%s encode: null image", Fmt::kStream.kind);
     if (threshold != threshold) return fail(FIC_E_ARGUMENT, "%s encode: threshold is NaN", Fmt::kStream.kind);
@@ -117,6 +128,9 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     if (budget && budget->max_leaves < L.g[0].Nr)
         return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %lld, the image has %d blocks of side %d", Fmt::kStream.kind,
                     (long long)budget->max_leaves, L.g[0].Nr, B_max);
+    if (rd && rd->goal == FIC_QT_RD_LEAVES && rd->value < (uint64_t)L.g[0].Nr)
+        return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %llu, the image has %d blocks of side %d", Fmt::kStream.kind,
+                    (unsigned long long)rd->value, L.g[0].Nr, B_max);
     size_t sse_total = 0;
     for (int l = 0; l < L.nl; l++) sse_total += (size_t)L.g[l].Nr;
     if (sse_out && sse_capacity < (int64_t)sse_total)
@@ -140,8 +154,12 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     const size_t o_cnt = off, o_offs = o_cnt + align256((size_t)top.Nr * 4), o_leaves = o_offs + align256(((size_t)top.Nr + 1) * 4);
     // a budget: the split keys of every block above B_min, the select's histograms and result, the tree's statistics
     const int n1 = L.nl == 3 ? L.g[1].Nr : 0, nkeys = top.Nr + n1;
-    const size_t o_keys = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4), o_sel = o_keys + (budget ? align256((size_t)nkeys * 4) : 0),
-                 o_stats = o_sel + (budget ? align256(FIC_QT_SELECT_WORDS * 4) : 0), total = o_stats + (budget ? 256 : 0);
+    // pruning: the same and the gains G_v; the statistics' 256 bytes also hold the top-level SSE sum (+64) and a given lambda (+128)
+    static_assert(FIC_QT_SELECT_W_WORDS * 8 >= FIC_QT_SELECT_WORDS * 4, "one select area for both selects");
+    const size_t o_keys = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4), o_gains = o_keys + (budget || rd ? align256((size_t)nkeys * 4) : 0),
+                 o_sel = o_gains + (rd ? align256((size_t)nkeys * 8) : 0),
+                 o_stats = o_sel + (rd ? align256(FIC_QT_SELECT_W_WORDS * 8) : (budget ? align256(FIC_QT_SELECT_WORDS * 4) : 0)),
+                 total = o_stats + (budget || rd ? 256 : 0);
     if (rc == FIC_OK) rc = mem.alloc(scratch, total);
     if (rc == FIC_OK && Fmt::prepare(c[0])) rc = fail(FIC_E_HIP, "k_scale launch failed");
     const uint32_t* sse[kQtMaxLevels];
@@ -170,9 +188,43 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
             else *budget->threshold_out = threshold;
         }
     }
+    const uint32_t *d_keys = (const uint32_t*)(scratch + o_keys), *d_lambda = nullptr;
+    if (rc == FIC_OK && rd) {
+        unsigned long long* d_top = (unsigned long long*)(scratch + o_stats + 64);
+        if (fic_launch_qt_rd_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, n1, (uint32_t*)(scratch + o_keys), (long long*)(scratch + o_gains), d_top, nullptr))
+            rc = fail(FIC_E_HIP, "%s pruning keys launch failed", Fmt::kStream.kind);
+        uint32_t lambda = (uint32_t)rd->value;
+        if (rc == FIC_OK && rd->goal == FIC_QT_RD_LAMBDA) {
+            d_lambda = (const uint32_t*)(scratch + o_stats + 128);
+            hipError_t e = hipMemsetD32Async((hipDeviceptr_t)(scratch + o_stats + 128), (int)lambda, 1, nullptr);
+            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
+        } else if (rc == FIC_OK) {
+            int bad;
+            if (rd->goal == FIC_QT_RD_LEAVES) {       // the select of 4.18 on the new keys, rank S = (M - Ntop) / 3
+                const uint64_t S = (rd->value - (uint64_t)top.Nr) / 3;
+                uint32_t* d_sel = (uint32_t*)(scratch + o_sel);
+                bad = fic_launch_qt_select(d_keys, (uint32_t)nkeys, (uint32_t)(S < (uint64_t)nkeys ? S : (uint64_t)nkeys), d_sel, nullptr);
+                d_lambda = d_sel + 4 * 256;
+            } else {                                  // the summed gain has to reach sum S_top - max_sse
+                unsigned long long* d_sel = (unsigned long long*)(scratch + o_sel);
+                const uint64_t cap = (uint64_t)INT64_MAX;
+                bad = fic_launch_qt_select_w(d_keys, (const long long*)(scratch + o_gains), (uint32_t)nkeys, d_top,
+                                             (long long)(rd->value < cap ? rd->value : cap), d_sel, nullptr);
+                d_lambda = (const uint32_t*)(d_sel + 4 * 256);
+            }
+            if (bad) rc = fail(FIC_E_HIP, "%s pruning select launch failed", Fmt::kStream.kind);
+            if (rc == FIC_OK) {     // the caller's copy; the walkers read it where it is
+                hipError_t e = hipMemcpy(&lambda, d_lambda, sizeof(uint32_t), hipMemcpyDeviceToHost);
+                if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
+            }
+        }
+        if (rc == FIC_OK) *rd->lambda_out = lambda;
+    }
     int* d_offs = (int*)(scratch + o_offs);
-    if (rc == FIC_OK && fic_launch_qt_compact<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, threshold,
-                                                                 (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr))
+    if (rc == FIC_OK && (rd ? fic_launch_qt_compact_rd<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, d_lambda,
+                                                                          (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr)
+                            : fic_launch_qt_compact<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, threshold,
+                                                                       (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr)))
         rc = fail(FIC_E_HIP, "%s compaction launch failed", Fmt::kStream.kind);
     int n = 0;
     if (rc == FIC_OK) {
@@ -180,12 +232,14 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
     if (rc == FIC_OK && n_leaves) *n_leaves = n;
-    if (rc == FIC_OK && budget && budget->stats4) {
+    uint64_t* stats4 = budget ? budget->stats4 : (rd ? rd->stats4 : nullptr);
+    if (rc == FIC_OK && stats4) {
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stats4");
-        if (fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, threshold, (unsigned long long*)(scratch + o_stats), nullptr))
+        if (rd ? fic_launch_qt_tree_stats_rd(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, d_lambda, (unsigned long long*)(scratch + o_stats), nullptr)
+               : fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, threshold, (unsigned long long*)(scratch + o_stats), nullptr))
             rc = fail(FIC_E_HIP, "%s tree statistics launch failed", Fmt::kStream.kind);
         else {
-            hipError_t e = hipMemcpy(budget->stats4, scratch + o_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+            hipError_t e = hipMemcpy(stats4, scratch + o_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
             if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
         }
     }
@@ -406,6 +460,125 @@ int fic_decode_rgb_quadtree_iso_run(const uint8_t* run, int64_t len, int zoom, i
                                     int* w_out, int* h_out, float* avg_error_io, int* iterations)
 {
     return qt_decode_run<QtRgbIsoHost>(run, len, zoom, device, argb_out, capacity_pixels, w_out, h_out, avg_error_io, iterations);
+}
+
+}  // extern "C"
+
+// ---- encode by rate-distortion pruning -------------------------------------------------------------------
+namespace {
+
+// The checks of an RD entry that need no geometry; the ladder, the window and max_leaves >= N_top follow in qt_encode, all
+// before any device work.
+template <typename Fmt>
+int qt_encode_rd(const char* entry, const uint8_t* gray, const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int search,
+                 int goal, uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* lambda_out, uint64_t* stats4)
+{
+    if ((!gray && !argb) || !leaves || !n_leaves || !lambda_out) return fail(FIC_E_ARGUMENT, "%s: null argument", entry);
+    if (goal < FIC_QT_RD_LAMBDA || goal > FIC_QT_RD_SSE) return fail(FIC_E_ARGUMENT, "%s: goal = %d, need 0 (lambda), 1 (leaves) or 2 (SSE)", entry, goal);
+    if (search != 0 && search != 1) return fail(FIC_E_ARGUMENT, "%s: search = %d, need 0 (reference) or 1 (least squares)", entry, search);
+    if (goal == FIC_QT_RD_LAMBDA && value > 0xFFFFFFFFull)
+        return fail(FIC_E_ARGUMENT, "%s: lambda = %llu, need 0 .. 2^32 - 1", entry, (unsigned long long)value);
+    const QtRd rd{goal, value, lambda_out, stats4};
+    return qt_encode<Fmt>(gray, argb, w, h, B_max, B_min, wK, n_iso, 0.0f, device, leaves, capacity, n_leaves, nullptr, 0, nullptr, search, &rd);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fic_encode_gray_quadtree_rd_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int search, int goal,
+                                   uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* lambda_out,
+                                   uint64_t* stats4)
+{
+    return qt_encode_rd<QtGreyHost>("fic_encode_gray_quadtree_rd_u8", gray, nullptr, w, h, B_max, B_min, wK, n_iso, search, goal, value, device,
+                                    leaves, capacity, n_leaves, lambda_out, stats4);
+}
+
+int fic_encode_gray_quadtree_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int search, int goal,
+                                     uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* lambda_out,
+                                     uint64_t* stats4)
+{
+    return qt_encode_rd<QtGreyHost>("fic_encode_gray_quadtree_rd_argb", nullptr, argb, w, h, B_max, B_min, wK, n_iso, search, goal, value, device,
+                                    leaves, capacity, n_leaves, lambda_out, stats4);
+}
+
+int fic_encode_rgb_quadtree_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int search, int goal, uint64_t value,
+                                    int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* lambda_out, uint64_t* stats4)
+{
+    return qt_encode_rd<QtRgbHost>("fic_encode_rgb_quadtree_rd_argb", nullptr, argb, w, h, B_max, B_min, wK, 1, search, goal, value, device, leaves,
+                                   capacity, n_leaves, lambda_out, stats4);
+}
+
+int fic_encode_rgb_quadtree_iso_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int search, int goal,
+                                        uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves, uint32_t* lambda_out,
+                                        uint64_t* stats4)
+{
+    return qt_encode_rd<QtRgbIsoHost>("fic_encode_rgb_quadtree_iso_rd_argb", nullptr, argb, w, h, B_max, B_min, wK, n_iso, search, goal, value,
+                                      device, leaves, capacity, n_leaves, lambda_out, stats4);
+}
+
+// Test hook: k_qt_rd_keys on the caller's SSE arrays (the levels concatenated, as fic_debug_quadtree_sse returns them)
+int fic_debug_qt_rd_keys(int device, const uint32_t* sse, int w, int h, int B_max, int B_min, uint32_t* keys, int64_t* gains)
+{
+    if (!sse || !keys || !gains) return fail(FIC_E_ARGUMENT, "fic_debug_qt_rd_keys: null argument");
+    if (!((B_max == 8 || B_max == 16) && (B_min == 4 || B_min == 8) && B_min < B_max))
+        return fail(FIC_E_ARGUMENT, "fic_debug_qt_rd_keys: levels B_max=%d B_min=%d", B_max, B_min);
+    if (w <= 0 || h <= 0 || (w % B_max) || (h % B_max) || (int64_t)(w / B_min) * (h / B_min) >= 0x7FFFFFFFll)
+        return fail(FIC_E_GEOMETRY, "fic_debug_qt_rd_keys: image %dx%d, B_max=%d", w, h, B_max);
+    int rc = check_device(device);
+    if (rc) return rc;
+    int nl = 0, Rw[kQtMaxLevels], Nr[kQtMaxLevels];
+    size_t o_sse[kQtMaxLevels], off = 0;
+    for (int B = B_max; B >= B_min; B /= 2, nl++) {
+        Rw[nl] = w / B;
+        Nr[nl] = (w / B) * (h / B);
+        o_sse[nl] = off;
+        off += (size_t)Nr[nl] * 4;      // concatenated, like the caller's: one copy
+    }
+    const int n1 = nl == 3 ? Nr[1] : 0, nkeys = Nr[0] + n1;
+    const size_t o_keys = align256(off), o_gains = o_keys + align256((size_t)nkeys * 4), o_top = o_gains + align256((size_t)nkeys * 8);
+    DevMem mem(device);
+    char* scratch = nullptr;
+    rc = mem.alloc(scratch, o_top + 256);
+    if (rc) return rc;
+    const uint32_t* lv[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    for (int l = 0; l < nl; l++) lv[l] = (const uint32_t*)(scratch + o_sse[l]);
+    hipError_t e = hipMemcpy(scratch, sse, off, hipMemcpyHostToDevice);
+    if (e == hipSuccess && fic_launch_qt_rd_keys(lv, Rw, nl, B_max, Rw[0], Nr[0], n1, (uint32_t*)(scratch + o_keys), (long long*)(scratch + o_gains),
+                                                 (unsigned long long*)(scratch + o_top), nullptr))
+        return fail(FIC_E_HIP, "fic_debug_qt_rd_keys: launch failed");
+    if (e == hipSuccess) e = hipMemcpy(keys, scratch + o_keys, (size_t)nkeys * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(gains, scratch + o_gains, (size_t)nkeys * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_qt_rd_keys: %s", hipGetErrorString(e));
+    return FIC_OK;
+}
+
+// Test hook: the weighted select (k_qt_select_hist_w x 4, k_qt_select_final_w) on the caller's keys and gains
+int fic_debug_qt_select_weighted(int device, const uint32_t* keys, const int64_t* gains, int64_t n, int64_t need, uint32_t* key_out,
+                                 int64_t* above_out, int64_t* gain_out)
+{
+    if (!keys || !gains || !key_out || !above_out || !gain_out) return fail(FIC_E_ARGUMENT, "fic_debug_qt_select_weighted: null argument");
+    if (n < 1 || n >= 0x7FFFFFFFll) return fail(FIC_E_ARGUMENT, "fic_debug_qt_select_weighted: n = %lld", (long long)n);
+    int rc = check_device(device);
+    if (rc) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "gains");
+    DevMem mem(device);
+    char* scratch = nullptr;
+    const size_t o_gains = align256((size_t)n * 4), o_sel = o_gains + align256((size_t)n * 8);
+    rc = mem.alloc(scratch, o_sel + FIC_QT_SELECT_W_WORDS * 8);
+    if (rc) return rc;
+    uint64_t res[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemcpy(scratch, keys, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(scratch + o_gains, gains, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && fic_launch_qt_select_w((const uint32_t*)scratch, (const long long*)(scratch + o_gains), (uint32_t)n, nullptr,
+                                                  (long long)need, (unsigned long long*)(scratch + o_sel), nullptr))
+        return fail(FIC_E_HIP, "fic_debug_qt_select_weighted: launch failed");
+    if (e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 8, sizeof(res), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_qt_select_weighted: %s", hipGetErrorString(e));
+    *key_out = (uint32_t)res[0];
+    *above_out = (int64_t)res[1];
+    *gain_out = (int64_t)res[2];
+    return FIC_OK;
 }
 
 }  // extern "C"

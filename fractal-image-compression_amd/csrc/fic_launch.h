@@ -336,6 +336,25 @@ int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32
 // stats u64 [4] = {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4} of the tree under `threshold`
 int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
                              unsigned long long* stats, hipStream_t s);
+// Encode by rate-distortion pruning, on the same per-level SSE arrays.  keys u32 / gains i64 [Ntop + n1]: e(v)
+// and G_v of every block above B_min in the order of fic_launch_qt_keys; *top_sum = the sum of the SSE of the top-level blocks.
+int fic_launch_qt_rd_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
+                          long long* gains, unsigned long long* top_sum, hipStream_t s);
+// Weighted radix select over n < 2^31 (key, gain) pairs: work u64 [FIC_QT_SELECT_W_WORDS] = four 256-bin gain sums, then {b in the
+// low 32 bits, #{keys > b}, their summed gain, 0}: b the largest of the keys and 0 with sum_{key > b} gain >= need, 0 when there is
+// none; need = *total - value (total a device pointer), or value when total is NULL.  The cumulated gain over descending distinct
+// keys must not fall.
+constexpr int FIC_QT_SELECT_W_WORDS = 4 * 256 + 4;
+int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total, long long value,
+                           unsigned long long* work, hipStream_t s);
+// fic_launch_qt_compact / _tree_stats with the split rule "e(v) > *lambda": keys as fic_launch_qt_rd_keys writes them, lambda a
+// device pointer (where a select left it)
+template <typename Fmt>
+int fic_launch_qt_compact_rd(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
+                             int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys, const uint32_t* lambda, int* counts,
+                             int* offs, int32_t* leaves, hipStream_t s);
+int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys,
+                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s);
 // one paint (decodeGreyScale / decodeRGB) of the n leaves of side g.B (one plane; g = that level's geometry)
 template <typename Fmt>
 int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,

@@ -18,6 +18,10 @@
 //   k_qt_keys / k_qt_select_hist / k_qt_select_final / k_qt_tree_stats
 //                            encode to a leaf budget: the split keys e(v), a radix select of the key that
 //                            the budget falls on and its threshold, the collage SSE and the leaves per level of the tree
+//   k_qt_rd_keys / k_qt_select_hist_w / k_qt_select_final_w
+//                            encode by rate-distortion pruning: the keys e(v) and gains G_v of min D + lambda N,
+//                            and the select of the key at which the summed gain reaches an SSE target
+// The walkers (k_qt_count, k_qt_scatter, k_qt_tree_stats) take the split rule as a type: QtByThreshold (4.13) or QtByKey (4.23).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -181,9 +185,26 @@ __device__ __forceinline__ bool qt_split(const FicQtLevels& L, int l, int x, int
     return (double)s > (double)L.threshold * (double)B * (double)B;
 }
 
+// The split rules of the walkers: split(L, l, x, y) for the block of level l at pixel (x, y).  QtByThreshold: the rule above.
+// QtByKey: a block above B_min splits iff its key e(v) > lambda; keys as k_qt_rd_keys writes them (level 0,
+// then level 1), lambda read from device memory, where the select left it.
+struct QtByThreshold {
+    __device__ __forceinline__ bool operator()(const FicQtLevels& L, int l, int x, int y) const { return qt_split(L, l, x, y); }
+};
+struct QtByKey {
+    const uint32_t* keys;
+    const uint32_t* lambda;
+    __device__ __forceinline__ bool operator()(const FicQtLevels& L, int l, int x, int y) const
+    {
+        if (l >= L.nl - 1) return false;
+        const int B = L.B_max >> l;
+        return keys[(l ? L.Ntop : 0) + (y / B) * L.Rw[l] + x / B] > *lambda;
+    }
+};
+
 // Walks the subtree of top-level block t in DFS order; emit(x, y, l) per leaf.
-template <typename F>
-__device__ __forceinline__ void qt_walk(const FicQtLevels& L, int t, F emit)
+template <typename Split, typename F>
+__device__ __forceinline__ void qt_walk(const FicQtLevels& L, const Split& split, int t, F emit)
 {
     int sx[8], sy[8], sl[8];
     int sp = 0;
@@ -194,7 +215,7 @@ __device__ __forceinline__ void qt_walk(const FicQtLevels& L, int t, F emit)
     while (sp > 0) {
         sp--;
         const int x = sx[sp], y = sy[sp], l = sl[sp];
-        if (qt_split(L, l, x, y)) {
+        if (split(L, l, x, y)) {
             const int h = (L.B_max >> l) / 2;       // children pushed BR, BL, TR, TL: popped TL first
             sx[sp] = x + h; sy[sp] = y + h; sl[sp] = l + 1; sp++;
             sx[sp] = x;     sy[sp] = y + h; sl[sp] = l + 1; sp++;
@@ -206,12 +227,13 @@ __device__ __forceinline__ void qt_walk(const FicQtLevels& L, int t, F emit)
     }
 }
 
-__global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L, int* __restrict__ counts)
+template <typename Split>
+__global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L, Split split, int* __restrict__ counts)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= L.Ntop) return;
     int n = 0;
-    qt_walk(L, t, [&](int, int, int) { n++; });
+    qt_walk(L, split, t, [&](int, int, int) { n++; });
     counts[t] = n;
 }
 
@@ -243,14 +265,14 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
 }
 
 // Leaf rows of Fmt::QW + 3 ints, formats with kIso one more: the iso column follows the quantised row
-template <typename Fmt>
-__global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, const int* __restrict__ offs, int32_t* __restrict__ leaves)
+template <typename Fmt, typename Split>
+__global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, Split split, const int* __restrict__ offs, int32_t* __restrict__ leaves)
 {
     constexpr int QW = Fmt::QW;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= L.Ntop) return;
     int o = offs[t];
-    qt_walk(L, t, [&](int x, int y, int l) {
+    qt_walk(L, split, t, [&](int x, int y, int l) {
         const int B = L.B_max >> l;
         const int j = (y / B) * L.Rw[l] + x / B;
         int32_t* r = leaves + Fmt::kLeafInts * (size_t)o;
@@ -366,15 +388,16 @@ __global__ __launch_bounds__(256) void k_qt_select_final(const uint32_t* __restr
     }
 }
 
-// stats u64 [4], zeroed by the launcher: the collage SSE summed over the leaves of the tree under L.threshold, and its leaves
+// stats u64 [4], zeroed by the launcher: the collage SSE summed over the leaves of the tree under the split rule, and its leaves
 // of side B_max, B_max / 2, B_max / 4.  One thread per top-level block, k_qt_count's walk; wave sums, then one atomic per
 // wave and non-zero value.
-__global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L, unsigned long long* __restrict__ stats)
+template <typename Split>
+__global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L, Split split, unsigned long long* __restrict__ stats)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     unsigned long long v[4] = {0, 0, 0, 0};
     if (t < L.Ntop)
-        qt_walk(L, t, [&](int x, int y, int l) {
+        qt_walk(L, split, t, [&](int x, int y, int l) {
             const int B = L.B_max >> l;
             v[0] += L.sse[l][(y / B) * L.Rw[l] + x / B];
             v[1 + l]++;
@@ -384,6 +407,186 @@ __global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L, unsigned l
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
         if ((threadIdx.x & 63) == 0 && v[i]) atomicAdd(&stats[i], v[i]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Encode by rate-distortion pruning: the tree T(lambda) that minimises D + lambda N, D the summed SSE of the
+// leaves and N their number, lambda an integer in 0 .. 2^32 - 1.  With S_v the u32 of k_leaf_sse widened to 64 bits, block v
+// above B_min wants to split iff the cost of its children, sum of J(c), is < S_v + lambda, where J(c) = S_c + lambda at B_min and
+// min(S_c + lambda, sum of J over c's children) above; k(v) is the smallest lambda >= 0 at which it does not:
+//   children of side B_min:      k(v) = max(0, ceil((S_v - sum S_c) / 3))
+//   top block of three levels:   the smallest lambda with f(lambda) = sum_c min(S_c + lambda, SS_c + 4 lambda) - S_v - lambda >= 0
+//                                (SS_c the sum over c's children); f has slope >= 3 and f(ceil(S_v / 3)) >= 0, so a bisection
+//                                over [0, ceil(S_v / 3)] finds it in at most 31 steps, and k(v) < 2^31
+// e(v) = min(k(v), k(parent)) and G_v = S_v - sum S_c (signed).  All of it in int64: S <= 2^32 - 1, lambda < 2^31, so no term
+// passes 2^37.  One thread per block above B_min in the order of k_qt_keys; a thread of level 1 works its parent's k out again
+// (21 loads) instead of waiting for it.  *top_sum (zeroed by the launcher) += the sum of S over the top-level blocks.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long qt_child_sum(const FicQtLevels& L, int l, int j)
+{
+    const int x = j % L.Rw[l], y = j / L.Rw[l], Rc = L.Rw[l + 1];
+    const uint32_t* c = L.sse[l + 1] + (size_t)(2 * y) * Rc + 2 * x;
+    return (long long)c[0] + (long long)c[1] + (long long)c[Rc] + (long long)c[Rc + 1];
+}
+
+__device__ __forceinline__ uint32_t qt_rd_k_last(long long S, long long kids)
+{
+    const long long g = S - kids;
+    return g <= 0 ? 0u : (uint32_t)((g + 2) / 3);
+}
+
+__device__ __forceinline__ uint32_t qt_rd_k_top(const FicQtLevels& L, int j)      // three levels, j a block of level 0
+{
+    const long long S = L.sse[0][j];
+    const int x = j % L.Rw[0], y = j / L.Rw[0];
+    long long sc[4], scc[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int jc = (2 * y + (c >> 1)) * L.Rw[1] + 2 * x + (c & 1);
+        sc[c] = L.sse[1][jc];
+        scc[c] = qt_child_sum(L, 1, jc);
+    }
+    auto f = [&](long long lam) {
+        long long s = -S - lam;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const long long whole = sc[c] + lam, parts = scc[c] + 4 * lam;
+            s += whole < parts ? whole : parts;
+        }
+        return s;
+    };
+    if (f(0) >= 0) return 0u;
+    long long lo = 0, hi = (S + 2) / 3;             // f(lo) < 0 <= f(hi)
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (f(mid) >= 0) hi = mid;
+        else lo = mid;
+    }
+    return (uint32_t)hi;
+}
+
+__global__ __launch_bounds__(256) void k_qt_rd_keys(FicQtLevels L, int n1, uint32_t* __restrict__ keys, long long* __restrict__ gains,
+                                                    unsigned long long* __restrict__ top_sum)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long s_top = 0;
+    if (t < L.Ntop) {
+        const long long S = L.sse[0][t], kids = qt_child_sum(L, 0, t);
+        keys[t] = L.nl == 3 ? qt_rd_k_top(L, t) : qt_rd_k_last(S, kids);
+        gains[t] = S - kids;
+        s_top = (unsigned long long)S;
+    } else if (t < L.Ntop + n1) {
+        const int j = t - L.Ntop, x = j % L.Rw[1], y = j / L.Rw[1];
+        const long long S = L.sse[1][j], kids = qt_child_sum(L, 1, j);
+        const uint32_t k = qt_rd_k_last(S, kids), kp = qt_rd_k_top(L, (y / 2) * L.Rw[0] + x / 2);
+        keys[t] = k < kp ? k : kp;
+        gains[t] = S - kids;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s_top += __shfl_xor(s_top, off, 64);
+    if ((threadIdx.x & 63) == 0 && s_top) atomicAdd(top_sum, s_top);
+}
+
+// The weighted select: with A(x) = the sum of gain over the keys > x, the largest b among the keys and 0 with A(b) >= need, or
+// 0 when there is none.  Precondition: A is non-increasing in x (the summed gain over descending distinct keys never falls).
+// Then "A(x) < need" is monotone in x, and x0 = min{x : A(x) < need} (2^32 when there is none, i.e. need <= 0) comes out of
+// the radix select of 4.18 with int64 gain sums in the bins: per pass, with `acc` the gain above the prefix, the digit is the
+// smallest d with acc + #{gain of digits > d} < need -- every larger digit passes too, none smaller does -- and acc grows by
+// that sum.  x0 is a key or 0, and b = the largest key < x0.  need = *total - value (an SSE target: the top-level sum minus
+// max_sse, both on the device) or, total NULL, value itself.
+//
+// qt_select_w_resolve: x0's prefix and acc after `npass` passes from their final bins (i64 [4][256]), by all 256 threads: an
+// inclusive suffix scan of the pass's 256 sums in LDS, then the smallest passing digit through an LDS atomicMin.
+__device__ __forceinline__ void qt_select_w_resolve(const long long* __restrict__ bins, int npass, long long need, uint32_t& prefix,
+                                                    bool& none)
+{
+    __shared__ long long s_suf[256];
+    __shared__ long long s_acc;
+    __shared__ uint32_t s_prefix;
+    __shared__ int s_d;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_prefix = 0; s_acc = 0; }
+    none = false;
+    for (int p = 0; p < npass; p++) {
+        __syncthreads();
+        const uint32_t pre = s_prefix;
+        const long long acc = s_acc, own = bins[256 * p + tid];
+        s_suf[tid] = own;
+        if (tid == 0) s_d = 256;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const long long v = tid + off < 256 ? s_suf[tid + off] : 0;
+            __syncthreads();
+            s_suf[tid] += v;
+            __syncthreads();
+        }
+        const long long above = s_suf[tid] - own;       // the gain of the digits > tid
+        if (acc + above < need) atomicMin(&s_d, tid);
+        __syncthreads();
+        const int d = s_d;                              // uniform
+        if (d == 256) { none = true; break; }           // pass 0 only: later, digit 255 passes by the choice before it
+        if (tid == d) { s_prefix = (pre << 8) | (uint32_t)d; s_acc = acc + above; }
+    }
+    __syncthreads();
+    prefix = s_prefix;
+}
+
+__device__ __forceinline__ long long qt_select_w_need(const unsigned long long* __restrict__ total, long long value)
+{
+    return total ? (long long)*total - value : value;
+}
+
+// One pass: k_qt_select_hist with the gains summed per bin (64-bit LDS adds, one global atomic per bin with a non-zero sum).
+__global__ __launch_bounds__(256) void k_qt_select_hist_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
+                                                          const unsigned long long* __restrict__ total, long long value,
+                                                          long long* __restrict__ bins, int pass)
+{
+    __shared__ unsigned long long hist[256];
+    hist[threadIdx.x] = 0;
+    uint32_t prefix;
+    bool none;
+    qt_select_w_resolve(bins, pass, qt_select_w_need(total, value), prefix, none);      // its barriers also cover hist's zeroes
+    if (none) return;                                                                   // uniform
+    const int shift = 24 - 8 * pass;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const uint32_t k = keys[i];
+        if (pass == 0 || (k >> (shift + 8)) == prefix) atomicAdd(&hist[(k >> shift) & 255u], (unsigned long long)gains[i]);
+    }
+    __syncthreads();
+    const unsigned long long c = hist[threadIdx.x];
+    if (c) atomicAdd((unsigned long long*)&bins[256 * pass + threadIdx.x], c);
+}
+
+// The last step, again over all keys: out u64 [4], zeroed by the launcher = {b in the low 32 bits, #{keys > b}, the sum of
+// their gains (signed), 0}.  b = max{key < x0} or 0; the keys > b are those >= max(x0, 1).  Wave sums, then one atomic
+// each per wave and non-zero value.
+__global__ __launch_bounds__(256) void k_qt_select_final_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
+                                                           const unsigned long long* __restrict__ total, long long value,
+                                                           const long long* __restrict__ bins, unsigned long long* __restrict__ out)
+{
+    uint32_t prefix;
+    bool none;
+    qt_select_w_resolve(bins, 4, qt_select_w_need(total, value), prefix, none);
+    const unsigned long long x0 = none ? 0x100000000ull : (unsigned long long)prefix, from = x0 ? x0 : 1ull;
+    uint32_t b = 0;
+    unsigned long long cnt = 0, gain = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const uint32_t k = keys[i];
+        if (k < x0 && k > b) b = k;
+        if (k >= from) { cnt++; gain += (unsigned long long)gains[i]; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t ob = __shfl_xor(b, off, 64);
+        b = ob > b ? ob : b;
+        cnt += __shfl_xor(cnt, off, 64);
+        gain += __shfl_xor(gain, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (b) atomicMax((uint32_t*)out, b);
+        if (cnt) atomicAdd(out + 1, cnt);
+        if (gain) atomicAdd(out + 2, gain);
     }
 }
 
@@ -541,13 +744,39 @@ int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32
     return 0;
 }
 
+template <typename Split>
+static int qt_tree_stats(const FicQtLevels& L, const Split& split, unsigned long long* stats, hipStream_t s)
+{
+    if (hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_qt_tree_stats<Split>, dim3((L.Ntop + 255) / 256), dim3(256), 0, s, L, split, stats);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
 int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
                              unsigned long long* stats, hipStream_t s)
 {
-    if (hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -1;
-    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold);
-    hipLaunchKernelGGL(k_qt_tree_stats, dim3((Ntop + 255) / 256), dim3(256), 0, s, L, stats);
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold), QtByThreshold{}, stats, s);
+}
+
+int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys,
+                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s)
+{
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f), QtByKey{keys, lambda}, stats, s);
+}
+
+template <typename Fmt, typename Split>
+static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int* offs, int32_t* leaves, hipStream_t s)
+{
+    const int nb = (L.Ntop + 255) / 256;
+    hipLaunchKernelGGL(k_qt_count<Split>, dim3(nb), dim3(256), 0, s, L, split, counts);
     FIC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, L.Ntop);
+    FIC_LAUNCH_CHECK();
+    if (leaves) {
+        hipLaunchKernelGGL((k_qt_scatter<Fmt, Split>), dim3(nb), dim3(256), 0, s, L, split, (const int*)offs, leaves);
+        FIC_LAUNCH_CHECK();
+    }
     return 0;
 }
 
@@ -556,16 +785,38 @@ int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrow
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
                           hipStream_t s)
 {
-    const FicQtLevels L = qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold);
-    const int nb = (Ntop + 255) / 256;
-    hipLaunchKernelGGL(k_qt_count, dim3(nb), dim3(256), 0, s, L, counts);
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold), QtByThreshold{}, counts, offs, leaves, s);
+}
+
+template <typename Fmt>
+int fic_launch_qt_compact_rd(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
+                             int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys, const uint32_t* lambda, int* counts,
+                             int* offs, int32_t* leaves, hipStream_t s)
+{
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, 0.0f), QtByKey{keys, lambda}, counts, offs, leaves, s);
+}
+
+int fic_launch_qt_rd_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
+                          long long* gains, unsigned long long* top_sum, hipStream_t s)
+{
+    if (hipMemsetAsync(top_sum, 0, sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f);
+    hipLaunchKernelGGL(k_qt_rd_keys, dim3((Ntop + n1 + 255) / 256), dim3(256), 0, s, L, n1, keys, gains, top_sum);
     FIC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, Ntop);
-    FIC_LAUNCH_CHECK();
-    if (leaves) {
-        hipLaunchKernelGGL(k_qt_scatter<Fmt>, dim3(nb), dim3(256), 0, s, L, (const int*)offs, leaves);
+    return 0;
+}
+
+int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total, long long value,
+                           unsigned long long* work, hipStream_t s)
+{
+    if (hipMemsetAsync(work, 0, FIC_QT_SELECT_W_WORDS * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
+    for (int pass = 0; pass < 4; pass++) {
+        hipLaunchKernelGGL(k_qt_select_hist_w, dim3(nb), dim3(256), 0, s, keys, gains, n, total, value, (long long*)work, pass);
         FIC_LAUNCH_CHECK();
     }
+    hipLaunchKernelGGL(k_qt_select_final_w, dim3(nb), dim3(256), 0, s, keys, gains, n, total, value, (const long long*)work, work + 4 * 256);
+    FIC_LAUNCH_CHECK();
     return 0;
 }
 
@@ -587,6 +838,8 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
                                           hipStream_t);                                                                               \
     template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \
                                             int, int, int, float, int*, int*, int32_t*, hipStream_t);                                 \
+    template int fic_launch_qt_compact_rd<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int, \
+                                               int, int, int, const uint32_t*, const uint32_t*, int*, int*, int32_t*, hipStream_t);   \
     template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const Fmt::Leaf*, int, FicDecodeState*, uint32_t*,     \
                                                      int, const FicGeom&, hipStream_t);
 FIC_QT_INSTANTIATE(QtGrey)

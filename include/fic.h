@@ -440,6 +440,61 @@ FIC_API int64_t fic_quadtree_leaves_for_bytes(int tag, int n_iso, int64_t max_by
 FIC_API int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int64_t rank, uint32_t* key_out, float* threshold_out,
                                 int64_t* above_out);
 
+/* ---- quadtree encode by rate-distortion pruning ---------------------------------- */
+/* The quadtree encodes above with the tree chosen by what a split buys against what it costs: T(lambda) minimises
+ * D + lambda * N over all trees of the ladder, D the collage SSE summed over the leaves and N the number of leaves.  Levels,
+ * geometry, wK, per-level codebooks, collage SSE, leaf order and leaf rows are those of the fixed-threshold entry of the same
+ * name; the levels are encoded once and lambda is chosen on the device.  Exact integers: with S_v the collage SSE of block v
+ * (uint32, the all-ones mark as 2^32 - 1) and an integer 0 <= lambda <= 2^32 - 1,
+ *   J(v) = S_v + lambda at side B_min, else min(S_v + lambda, sum of J over the four children);
+ *   v wants to split iff that sum is < S_v + lambda (a tie keeps the block whole);
+ *   in T(lambda) a block is split iff it and all its ancestors want to.
+ * With k(v) the smallest lambda at which v does not want to split, e(v) = min(k(v), k(parent(v))), G_v = S_v - the sum of S over
+ * v's children (signed) and N_top the blocks of side B_max: T(lambda) has N(lambda) = N_top + 3 #{v : e(v) > lambda} leaves and
+ * the collage SSE D(lambda) = sum S_top - sum_{e(v) > lambda} G_v; N never rises and D never falls as lambda grows, and every
+ * T(lambda) has the least collage SSE of all trees with its number of leaves.
+ *   search      0: the reference's criterion for the per-level codebooks, 1: least squares
+ *   goal/value  FIC_QT_RD_LAMBDA  value = lambda; above 2^32 - 1 is FIC_E_ARGUMENT
+ *               FIC_QT_RD_LEAVES  value = max_leaves >= N_top (else FIC_E_ARGUMENT): the smallest lambda whose tree has at most
+ *                                 max_leaves leaves, the (S+1)-th largest e(v) with S = (max_leaves - N_top) / 3, 0 when there
+ *                                 are S or fewer.  Blocks that share that key all stay whole: the tree may have fewer leaves
+ *               FIC_QT_RD_SSE     value = max_sse: the tree of fewest leaves among the T(lambda) with D <= max_sse, and the
+ *                                 smallest lambda that gives it (an e(v) or 0).  If even D(0) > max_sse the result is T(0) with
+ *                                 *lambda_out = 0 and FIC_OK: the caller sees it in stats4[0] > value
+ *   lambda_out  the lambda in force; set on FIC_E_CAPACITY too, like *n_leaves
+ *   stats4      NULL, or uint64 [4] as in the budget entries
+ * Checked before any device work: null pointers (FIC_E_ARGUMENT), goal outside 0..2, search outside 0..1, the ranges of value
+ * above, and the levels, geometry and window as in the fixed-threshold entries.  The leaf tables go through the stream writers
+ * and decoders unchanged. */
+#define FIC_QT_RD_LAMBDA 0
+#define FIC_QT_RD_LEAVES 1
+#define FIC_QT_RD_SSE 2
+FIC_API int fic_encode_gray_quadtree_rd_u8(const uint8_t* gray, int w, int h, int B_max, int B_min, int wK, int n_iso, int search,
+                                           int goal, uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves,
+                                           uint32_t* lambda_out, uint64_t* stats4);
+FIC_API int fic_encode_gray_quadtree_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int search,
+                                             int goal, uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves,
+                                             uint32_t* lambda_out, uint64_t* stats4);
+/* The same for the colour codec (tag 3 rows, leaves [capacity][8]) and for colour with n_iso = 1 or 8 isometries (tag 6 rows,
+ * leaves [capacity][9]). */
+FIC_API int fic_encode_rgb_quadtree_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int search, int goal,
+                                            uint64_t value, int device, int32_t* leaves, int64_t capacity, int* n_leaves,
+                                            uint32_t* lambda_out, uint64_t* stats4);
+FIC_API int fic_encode_rgb_quadtree_iso_rd_argb(const int32_t* argb, int w, int h, int B_max, int B_min, int wK, int n_iso, int search,
+                                                int goal, uint64_t value, int device, int32_t* leaves, int64_t capacity,
+                                                int* n_leaves, uint32_t* lambda_out, uint64_t* stats4);
+/* Test hook: the keys and gains of the pruning alone, no encode.  sse: the levels B_max .. B_min concatenated, as
+ * fic_debug_quadtree_sse returns them; keys / gains [N_top (+ the blocks of B_max / 2 with three levels)]: e(v) and G_v, the
+ * blocks of B_max in scanline order first, then those of B_max / 2. */
+FIC_API int fic_debug_qt_rd_keys(int device, const uint32_t* sse, int w, int h, int B_max, int B_min, uint32_t* keys, int64_t* gains);
+/* Test hook: the weighted select of FIC_QT_RD_SSE alone, on the caller's (key, gain) pairs, 1 <= n < 2^31.  With the distinct
+ * keys in descending order followed by 0, *key_out = the first boundary at which the sum of gain over the keys > boundary is
+ * >= need (0 when none is), *above_out = the number of those keys, *gain_out = their summed gain.  need <= 0 selects the
+ * largest key.  Precondition: that sum does not fall from one boundary to the next (the keys and gains of the pruning
+ * guarantee it; gains of any sign inside a group of equal keys are fine). */
+FIC_API int fic_debug_qt_select_weighted(int device, const uint32_t* keys, const int64_t* gains, int64_t n, int64_t need,
+                                         uint32_t* key_out, int64_t* above_out, int64_t* gain_out);
+
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
  *                     group-Fourier form, for 8 isometries at B = 8; k_sweep_fast otherwise)
