@@ -14,7 +14,7 @@ from .capi import encode_gray_quadtree_budget, encode_rgb_quadtree_budget, encod
 from .capi import quadtree_leaves_for_bytes, debug_qt_select
 from .capi import encode_gray_quadtree_rd, encode_rgb_quadtree_rd, encode_rgb_quadtree_iso_rd
 from .capi import RgbEncoder
-from .host import Encoder, FractalCompression, RasterImage, encode_gray, encode_rgb_per_channel
+from .host import Encoder, QuadtreeEncoder, FractalCompression, RasterImage, encode_gray, encode_rgb_per_channel
 from .sharding import ShardedEncoder, shard_spans, shard_planes, gather_records, pack_records, unpack_records
 
 __all__ = ["capi", "synth", "sharding", "FicError", "declared_symbols", "geometry", "write_run_gray", "decode_gray_run", "decode_rgb_run", "encode_rgb", "write_run_rgb", "Encoder",
@@ -24,4 +24,4 @@ __all__ = ["capi", "synth", "sharding", "FicError", "declared_symbols", "geometr
            "write_run_gray_iso", "write_run_rgb_iso", "decode_gray_iso_run", "decode_rgb_iso_run", "encode_rgb_quadtree_iso",
            "write_run_rgb_quadtree_iso", "decode_rgb_quadtree_iso_run", "debug_rgb_quadtree_iso_sse", "RgbEncoder",
            "encode_gray_quadtree_budget", "encode_rgb_quadtree_budget", "encode_rgb_quadtree_iso_budget", "quadtree_leaves_for_bytes",
-           "debug_qt_select", "encode_gray_quadtree_rd", "encode_rgb_quadtree_rd", "encode_rgb_quadtree_iso_rd"]
+           "debug_qt_select", "encode_gray_quadtree_rd", "encode_rgb_quadtree_rd", "encode_rgb_quadtree_iso_rd", "QuadtreeEncoder"]

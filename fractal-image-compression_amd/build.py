@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libfic_hip.so")
-SOURCES = ["fic_prep.hip", "fic_sweep.hip", "fic_lsq.hip", "fic_lsq_q.hip", "fic_lsq_rgb.hip", "fic_lsq_rgb_q.hip", "fic_q.hip", "fic_d4.hip", "fic_decode.hip", "fic_rgb.hip", "fic_quadtree.hip", "fic_stream.cpp", "fic_devmem.cpp", "fic_ctx_core.cpp", "fic_capi.cpp", "fic_capi_lsq.cpp", "fic_capi_decode.cpp", "fic_capi_rgb.cpp", "fic_capi_rgb_lsq.cpp", "fic_capi_multi.cpp", "fic_capi_quadtree.cpp"]
+SOURCES = ["fic_prep.hip", "fic_sweep.hip", "fic_lsq.hip", "fic_lsq_q.hip", "fic_lsq_rgb.hip", "fic_lsq_rgb_q.hip", "fic_q.hip", "fic_d4.hip", "fic_decode.hip", "fic_rgb.hip", "fic_quadtree.hip", "fic_stream.cpp", "fic_devmem.cpp", "fic_ctx_core.cpp", "fic_capi.cpp", "fic_capi_lsq.cpp", "fic_capi_decode.cpp", "fic_capi_rgb.cpp", "fic_capi_rgb_lsq.cpp", "fic_capi_multi.cpp", "fic_capi_quadtree.cpp", "fic_capi_qt_ctx.cpp"]
 # round 1's exact-covariance matrix-core sweeps ("sweep" = 3 / 4): superseded by k_sweep_q, kept as independent cross-checks
 # for the test-suite.  FIC_BUILD_XCHECK=0 leaves them out (a deployment build; tests that need them skip).
 XCHECK_SOURCES = ["fic_mfma.hip", "fic_bf16.hip"]
@@ -18,7 +18,7 @@ XCHECK_SOURCES = ["fic_mfma.hip", "fic_bf16.hip"]
 
 def xcheck():
     return os.environ.get("FIC_BUILD_XCHECK", "1") != "0"
-HEADERS = ["fic_device.h", "fic_launch.h", "fic_devfn.h", "fic_internal.h", "fic_stream.h", "fic_devmem.h", "fic_lsq_fit.h", "fic_lsq_rgb_fit.h", "fic_lsq_q_chunks.h", "fic_sweep_chunks.h", "fic_lsq_q_tile.h", "fic_d4_tables.h", os.path.join("..", "..", "include", "fic.h")]
+HEADERS = ["fic_device.h", "fic_launch.h", "fic_devfn.h", "fic_internal.h", "fic_stream.h", "fic_devmem.h", "fic_lsq_fit.h", "fic_lsq_rgb_fit.h", "fic_lsq_q_chunks.h", "fic_sweep_chunks.h", "fic_qt_batch_plan.h", "fic_lsq_q_tile.h", "fic_d4_tables.h", os.path.join("..", "..", "include", "fic.h")]
 # -ffp-contract=off: the Java reference never fuses a*b+c (FractalCompression.java:641,683);
 # hipcc's device default is "fast".  No fast-math: f32 divide/sqrt stay correctly rounded.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

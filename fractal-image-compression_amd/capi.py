@@ -170,6 +170,20 @@ def lib():
         "fic_debug_qt_select_weighted": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.POINTER(C.c_uint32),
                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "fic_debug_live_memory": (C.c_int, [C.POINTER(C.c_int64)]),
+        "fic_qt_ctx_create": (vp, [C.c_int] * 9),
+        "fic_qt_ctx_destroy": (None, [vp]),
+        "fic_qt_ctx_set_gray_host": (C.c_int, [vp, u8p]),
+        "fic_qt_ctx_set_argb_host": (C.c_int, [vp, i32p]),
+        "fic_qt_ctx_set_gray_device": (C.c_int, [vp, vp]),
+        "fic_qt_ctx_set_argb_device": (C.c_int, [vp, vp]),
+        "fic_qt_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
+        "fic_qt_ctx_encode_threshold": (C.c_int, [vp, f32p, vp]),
+        "fic_qt_ctx_encode_budget": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
+        "fic_qt_ctx_encode_rd": (C.c_int, [vp, C.c_int, u64p, vp]),
+        "fic_qt_ctx_sync": (C.c_int, [vp]),
+        "fic_qt_ctx_get_results_host": (C.c_int, [vp, i32p, C.POINTER(C.c_uint32), u64p]),
+        "fic_qt_ctx_get_leaves_host": (C.c_int, [vp, C.c_int, i32p, C.c_int64, ip]),
+        "fic_qt_ctx_result_device_ptrs": (C.c_int, [vp] + [C.POINTER(vp)] * 4),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,419 @@
+// fic_capi_qt_ctx.cpp -- C ABI, the batched quadtree encoder handle (fic_qt_ctx_* of include/fic.h): `planes`
+// images of one geometry through the per-level contexts (created with `planes`) and the batched kernels of fic_quadtree.hip,
+// under the device-pointer contract and the stream rule of the other two handles.  An encode enqueues everything
+// on the caller's stream and returns: the per-plane parameters go up from a pinned staging buffer, every rule's parameter is
+// read from device memory by the kernels that need it, and nothing comes back before the caller asks.  Plane p of a batch is
+// what the one-shot entry of the same format (fic_capi_quadtree.cpp) returns for image p.  Host-side orchestration only.
+#include "fic_internal.h"
+#include "fic_qt_batch_plan.h"
+
+using namespace ficd;
+
+static_assert(kQtPlanSelectWords == FIC_QT_SELECT_WORDS && kQtPlanSelectWords == FIC_QT_SELECT_W_WORDS, "the plan's select areas");
+
+// The levels are contexts of their own (grey: fic_ctx, colour: fic_rgb_ctx with the isometry column); `mem` owns the one device
+// store (QtBatchPlan), the pinned staging buffer and a copy of a host input.
+struct fic_qt_ctx : ficd::CtxCore {
+    int colour = 0, B_max = 0, B_min = 0, n_iso = 1, planes = 1;
+    QtLevels L;
+    QtBatchPlan plan{};
+    fic_ctx* grey[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    fic_rgb_ctx* rgb[kQtMaxLevels] = {nullptr, nullptr, nullptr};
+    char* store = nullptr;
+    char* staging = nullptr;             // pinned: kQtPlanStagingSlots slots, each with the event of the copy that last read it
+    hipEvent_t slot_ev[kQtPlanStagingSlots] = {};
+    bool slot_busy[kQtPlanStagingSlots] = {};
+    int next_slot = 0;
+    uint8_t* gray_own = nullptr;         // a host input's device copy (grey), the staging of an ARGB upload to a grey context
+    int32_t* argb_own = nullptr;
+    int opt_search = 0;
+    template <typename T>
+    T* at(QtArea a) const { return (T*)(store + plan.a[a].off); }
+};
+
+namespace {
+
+enum QtRule { kRuleThreshold, kRuleBudget, kRuleRd };
+
+const char* qt_kind(const fic_qt_ctx* c) { return c->colour ? kQtRgbIsoStream.kind : kQtGreyStream.kind; }
+
+// every level gets the same device input (never copied)
+int qt_ctx_input(fic_qt_ctx* c, const void* dev)
+{
+    for (int l = 0; l < c->L.nl; l++)
+        if (int rc = c->colour ? fic_rgb_ctx_set_argb_device(c->rgb[l], dev) : fic_ctx_set_gray_device(c->grey[l], dev)) return rc;
+    c->have_input = true;
+    return FIC_OK;
+}
+
+// The common head of the three encodes: the state checks, the stream rule, a free staging slot.  Holds c->mu.
+int qt_ctx_begin(fic_qt_ctx* c, const char* who, hipStream_t s, int* slot)
+{
+    if (!c->have_input) return fail(FIC_E_STATE, "%s: no input image set", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = take_stream(c, s)) return rc;
+    *slot = c->next_slot;
+    if (c->slot_busy[*slot]) HIP_TRY(hipEventSynchronize(c->slot_ev[*slot]));      // the copy of four encodes ago: long done
+    c->slot_busy[*slot] = false;
+    return FIC_OK;
+}
+
+// Everything of an encode behind its checks, enqueued on s: the parameters' upload from staging slot `slot` (`up` says which
+// area it fills), the levels, the SSE, the rule's keys and select, the compaction, the statistics.
+template <typename Dev>
+int qt_ctx_run(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStream_t s)
+{
+    const QtBatchPlan& Q = c->plan;
+    const QtLevels& L = c->L;
+    const char* kind = qt_kind(c);
+    const FicGeom& top = L.g[0];
+    const size_t P = (size_t)c->planes;
+    {
+        const char* src = c->staging + (size_t)slot * Q.staging_slot + (up == kQtValues ? Q.staging_values : 0);
+        HIP_TRY(hipMemcpyAsync(c->store + Q.a[up].off, src, P * Q.a[up].elem, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c->slot_ev[slot], s));
+        c->slot_busy[slot] = true;
+        c->next_slot = (slot + 1) % kQtPlanStagingSlots;
+    }
+    for (int l = 0; l < L.nl; l++) {
+        int rc = c->colour ? fic_rgb_ctx_set_option(c->rgb[l], "search", c->opt_search) : fic_ctx_set_option(c->grey[l], "search", c->opt_search);
+        if (rc == FIC_OK) rc = c->colour ? fic_rgb_ctx_encode(c->rgb[l], 0, s) : fic_ctx_encode(c->grey[l], 0, -1, s);
+        if (rc) return rc;
+    }
+    // grey: every level reads the top context's scaled copy, made here for all planes (the original, 2:1 scaled: FC:970-1007)
+    if (!c->colour && fic_launch_scale(c->grey[0]->b.gray, c->grey[0]->b.scaled, c->grey[0]->g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
+
+    FicQtPlanes B{};
+    B.planes = c->planes;
+    B.nkeys = Q.nkeys;
+    B.sse_stride = Q.a[kQtSse].stride;
+    B.leaf_stride = Q.a[kQtLeaves].stride;
+    B.n_leaves = c->at<int>(kQtNLeaves);
+    B.param = c->at<uint32_t>(kQtParam);
+    B.ranks = c->at<uint32_t>(kQtRanks);
+    B.values = c->at<long long>(kQtValues);
+    const uint32_t* sse[kQtMaxLevels];
+    const int32_t* qrows[kQtMaxLevels];
+    const int32_t* iso[kQtMaxLevels];
+    int Rw[kQtMaxLevels];
+    for (int l = 0; l < L.nl; l++) {
+        B.Nr[l] = L.g[l].Nr;
+        Rw[l] = L.g[l].Rw;
+        uint32_t* d_sse = c->at<uint32_t>(kQtSse) + Q.sse_level[l];
+        sse[l] = d_sse;
+        const typename Dev::Px *image, *scaled;
+        if constexpr (sizeof(typename Dev::Px) == 1) {
+            image = c->grey[l]->b.gray;
+            scaled = c->grey[0]->b.scaled;
+            qrows[l] = c->grey[l]->o.qrows;
+            iso[l] = c->n_iso > 1 ? c->grey[l]->o.iso : nullptr;
+        } else {                                    // every level reads its own scaleImageRGB copy, made by its encode
+            image = c->rgb[l]->argb;
+            scaled = c->rgb[l]->scaled;
+            qrows[l] = c->rgb[l]->qrows;
+            iso[l] = c->rgb[l]->iso;                // NULL on n_iso = 1: the identity
+        }
+        if (fic_launch_leaf_sse<Dev>(image, scaled, qrows[l], iso[l], d_sse, L.g[l], s, &B)) return fail(FIC_E_HIP, "k_leaf_sse launch failed");
+    }
+    uint32_t* d_keys = c->at<uint32_t>(kQtKeys);
+    if (rule == kRuleBudget) {
+        if (fic_launch_qt_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, s, &B) ||
+            fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, 0, c->at<uint32_t>(kQtSelect), s, &B, 1))
+            return fail(FIC_E_HIP, "%s budget select launch failed", kind);
+    } else if (rule == kRuleRd) {
+        long long* d_gains = c->at<long long>(kQtGains);
+        unsigned long long* d_top = c->at<unsigned long long>(kQtTopSum);
+        if (fic_launch_qt_rd_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, d_gains, d_top, s, &B))
+            return fail(FIC_E_HIP, "%s pruning keys launch failed", kind);
+        int bad = 0;
+        if (goal == FIC_QT_RD_LEAVES) bad = fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, 0, c->at<uint32_t>(kQtSelect), s, &B, 0);
+        else if (goal == FIC_QT_RD_SSE) bad = fic_launch_qt_select_w(d_keys, d_gains, (uint32_t)Q.nkeys, d_top, 0, c->at<unsigned long long>(kQtSelect), s, &B);
+        if (bad) return fail(FIC_E_HIP, "%s pruning select launch failed", kind);
+    }
+    int *d_cnt = c->at<int>(kQtCounts), *d_offs = c->at<int>(kQtOffs);
+    int32_t* d_leaves = c->at<int32_t>(kQtLeaves);
+    unsigned long long* d_stats = c->at<unsigned long long>(kQtStats);
+    if (rule == kRuleRd) {
+        if (fic_launch_qt_compact_rd<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_cnt, d_offs, d_leaves, s, &B))
+            return fail(FIC_E_HIP, "%s compaction launch failed", kind);
+        if (fic_launch_qt_tree_stats_rd(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_stats, s, &B))
+            return fail(FIC_E_HIP, "%s tree statistics launch failed", kind);
+    } else {
+        if (fic_launch_qt_compact<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, 0.0f, d_cnt, d_offs, d_leaves, s, &B))
+            return fail(FIC_E_HIP, "%s compaction launch failed", kind);
+        if (fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, 0.0f, d_stats, s, &B))
+            return fail(FIC_E_HIP, "%s tree statistics launch failed", kind);
+    }
+    c->encoded_any = true;
+    return FIC_OK;
+}
+
+int qt_ctx_run_any(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStream_t s)
+{
+    return c->colour ? qt_ctx_run<QtRgbIso>(c, rule, goal, up, slot, s) : qt_ctx_run<QtGrey>(c, rule, goal, up, slot, s);
+}
+
+// the rank of the select for a budget of M leaves: S = (M - Ntop) / 3 blocks may split, the block of rank S must not
+uint32_t qt_rank(uint64_t M, const QtBatchPlan& Q)
+{
+    const uint64_t S = (M - (uint64_t)Q.Ntop) / 3;
+    return (uint32_t)(S < (uint64_t)Q.nkeys ? S : (uint64_t)Q.nkeys);
+}
+
+void qt_ctx_free(fic_qt_ctx* c)
+{
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    for (hipEvent_t e : c->slot_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int l = 0; l < kQtMaxLevels; l++) {
+        if (c->grey[l]) fic_ctx_destroy(c->grey[l]);
+        if (c->rgb[l]) fic_rgb_ctx_destroy(c->rgb[l]);
+    }
+    delete c;
+}
+
+}  // namespace
+
+extern "C" {
+
+fic_qt_ctx* fic_qt_ctx_create(int device, int colour, int w, int h, int B_max, int B_min, int wK, int n_iso, int planes)
+{
+    if (colour != 0 && colour != 1) { fail(FIC_E_ARGUMENT, "fic_qt_ctx_create: colour = %d, need 0 (grey) or 1 (joint RGB)", colour); return nullptr; }
+    QtLevels L;
+    if (qt_levels(w, h, B_max, B_min, wK, n_iso, &L)) return nullptr;
+    if (planes < 1) { fail(FIC_E_ARGUMENT, "planes=%d", planes); return nullptr; }
+    int Nr[kQtMaxLevels] = {0, 0, 0};
+    for (int l = 0; l < L.nl; l++) Nr[l] = L.g[l].Nr;
+    QtBatchPlan plan;
+    const char* why = "";
+    if (qt_batch_plan(planes, L.nl, Nr, colour ? QtRgbIso::kLeafInts : QtGrey::kLeafInts, &plan, &why)) {
+        fail(FIC_E_GEOMETRY, "fic_qt_ctx_create: %d planes of %dx%d, %d -> %d: %s would pass 2^31 - 1", planes, w, h, B_max, B_min, why);
+        return nullptr;
+    }
+    if (!create_device_ok(device)) return nullptr;
+    fic_qt_ctx* c = new fic_qt_ctx();
+    c->device = device;
+    c->mem.set_device(device);
+    c->colour = colour;
+    c->B_max = B_max;
+    c->B_min = B_min;
+    c->n_iso = n_iso;
+    c->planes = planes;
+    c->L = L;
+    c->g = L.g[0];
+    c->g.planes = planes;
+    c->plan = plan;
+    int rc = FIC_OK;
+    for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
+        const FicGeom& g = L.g[l];
+        if (colour) c->rgb[l] = fic_rgb_ctx_create_iso(device, w, h, g.B, g.wK, n_iso, planes);
+        else c->grey[l] = fic_ctx_create(device, w, h, g.B, g.wK, n_iso, planes);
+        if (!c->rgb[l] && !c->grey[l]) rc = g_err_code ? g_err_code : FIC_E_HIP;
+    }
+    if (rc == FIC_OK) rc = c->mem.alloc(c->store, plan.total);
+    if (rc == FIC_OK) rc = c->mem.alloc(c->staging, plan.staging_slot * kQtPlanStagingSlots, kMemPinned);
+    for (int i = 0; i < kQtPlanStagingSlots && rc == FIC_OK; i++)
+        if (hipEventCreateWithFlags(&c->slot_ev[i], hipEventDisableTiming) != hipSuccess) rc = fail(FIC_E_HIP, "fic_qt_ctx_create: hipEventCreateWithFlags failed");
+    if (rc == FIC_OK) {
+        // results read before the first encode are zeros.  The fill is only enqueued (null stream); encodes run on other streams
+        hipError_t e = hipMemset(c->store, 0, plan.total);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "fic_qt_ctx_create: hipMemset: %s", hipGetErrorString(e));
+    }
+    if (rc != FIC_OK) {
+        ErrKeep keep;
+        qt_ctx_free(c);
+        return nullptr;
+    }
+    return c;
+}
+
+void fic_qt_ctx_destroy(fic_qt_ctx* c)
+{
+    if (c) qt_ctx_free(c);
+}
+
+int fic_qt_ctx_set_gray_host(fic_qt_ctx* c, const uint8_t* gray)
+{
+    if (!c || !gray) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_host: null argument");
+    if (c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_host: a colour context takes ARGB input");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->planes * c->g.W * c->g.H;
+    if (int rc = c->mem.ensure(c->gray_own, bytes)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->last_stream));     // an earlier encode may still read the copy
+    HIP_TRY(hipMemcpy(c->gray_own, gray, bytes, hipMemcpyHostToDevice));
+    return qt_ctx_input(c, c->gray_own);
+}
+
+int fic_qt_ctx_set_argb_host(fic_qt_ctx* c, const int32_t* argb)
+{
+    if (!c || !argb) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_host: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)c->planes * c->g.W * c->g.H;
+    if (int rc = c->mem.ensure(c->argb_own, npix)) return rc;
+    if (!c->colour)
+        if (int rc = c->mem.ensure(c->gray_own, npix)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(c->argb_own, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (c->colour) return qt_ctx_input(c, c->argb_own);
+    if (fic_launch_argb_to_gray(c->argb_own, c->gray_own, npix, nullptr)) return fail(FIC_E_HIP, "k_argb_to_gray launch failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return qt_ctx_input(c, c->gray_own);
+}
+
+int fic_qt_ctx_set_gray_device(fic_qt_ctx* c, const void* dev_gray)
+{
+    if (!c || !dev_gray) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: null argument");
+    if (c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: a colour context takes ARGB input");
+    if ((uintptr_t)dev_gray % 8 != 0)                  // fic_ctx_set_gray_device's rule, refused here before any level has taken the pointer
+        return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: alignment: address %p is not a multiple of 8 bytes (the input in force stays)", dev_gray);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return qt_ctx_input(c, dev_gray);
+}
+
+int fic_qt_ctx_set_argb_device(fic_qt_ctx* c, const void* dev_argb)
+{
+    if (!c || !dev_argb) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: null argument");
+    if (!c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: a grey context takes device input as bytes (fic_qt_ctx_set_gray_device)");
+    if ((uintptr_t)dev_argb % 4 != 0)
+        return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: alignment: address %p is not a multiple of 4 bytes (the input in force stays)", dev_argb);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return qt_ctx_input(c, dev_argb);
+}
+
+int fic_qt_ctx_set_option(fic_qt_ctx* c, const char* name, int value)
+{
+    if (!c || !name) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!strcmp(name, "search")) {
+        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: search must be 0 (the reference's criterion) or 1 (least squares)");
+        c->opt_search = value;
+        return FIC_OK;
+    }
+    return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: unknown option '%s'", name);
+}
+
+int fic_qt_ctx_encode_threshold(fic_qt_ctx* c, const float* thresholds, void* hip_stream)
+{
+    if (!c || !thresholds) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_encode_threshold: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (int p = 0; p < c->planes; p++)
+        if (thresholds[p] != thresholds[p]) return fail(FIC_E_ARGUMENT, "%s encode: threshold is NaN (plane %d)", qt_kind(c), p);
+    int slot = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int rc = qt_ctx_begin(c, "fic_qt_ctx_encode_threshold", s, &slot)) return rc;
+    memcpy(c->staging + (size_t)slot * c->plan.staging_slot, thresholds, (size_t)c->planes * sizeof(float));
+    return qt_ctx_run_any(c, kRuleThreshold, 0, kQtParam, slot, s);
+}
+
+int fic_qt_ctx_encode_budget(fic_qt_ctx* c, const int64_t* max_leaves, void* hip_stream)
+{
+    if (!c || !max_leaves) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_encode_budget: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->opt_search != 0)
+        return fail(FIC_E_ARGUMENT, "fic_qt_ctx_encode_budget: the threshold budget runs on the reference's criterion only (\"search\" = 0); fic_qt_ctx_encode_rd takes both");
+    const FicGeom& top = c->L.g[0];
+    for (int p = 0; p < c->planes; p++)
+        if (max_leaves[p] < top.Nr)
+            return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %lld, the image has %d blocks of side %d (plane %d)", qt_kind(c), (long long)max_leaves[p],
+                        top.Nr, top.B, p);
+    int slot = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int rc = qt_ctx_begin(c, "fic_qt_ctx_encode_budget", s, &slot)) return rc;
+    uint32_t* ranks = (uint32_t*)(c->staging + (size_t)slot * c->plan.staging_slot);
+    for (int p = 0; p < c->planes; p++) ranks[p] = qt_rank((uint64_t)max_leaves[p], c->plan);
+    return qt_ctx_run_any(c, kRuleBudget, 0, kQtRanks, slot, s);
+}
+
+int fic_qt_ctx_encode_rd(fic_qt_ctx* c, int goal, const uint64_t* values, void* hip_stream)
+{
+    const char* entry = "fic_qt_ctx_encode_rd";
+    if (!c || !values) return fail(FIC_E_ARGUMENT, "%s: null argument", entry);
+    if (goal < FIC_QT_RD_LAMBDA || goal > FIC_QT_RD_SSE) return fail(FIC_E_ARGUMENT, "%s: goal = %d, need 0 (lambda), 1 (leaves) or 2 (SSE)", entry, goal);
+    std::lock_guard<std::mutex> lk(c->mu);
+    const FicGeom& top = c->L.g[0];
+    for (int p = 0; p < c->planes; p++) {
+        if (goal == FIC_QT_RD_LAMBDA && values[p] > 0xFFFFFFFFull)
+            return fail(FIC_E_ARGUMENT, "%s: lambda = %llu, need 0 .. 2^32 - 1 (plane %d)", entry, (unsigned long long)values[p], p);
+        if (goal == FIC_QT_RD_LEAVES && values[p] < (uint64_t)top.Nr)
+            return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %llu, the image has %d blocks of side %d (plane %d)", qt_kind(c),
+                        (unsigned long long)values[p], top.Nr, top.B, p);
+    }
+    int slot = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int rc = qt_ctx_begin(c, entry, s, &slot)) return rc;
+    char* stage = c->staging + (size_t)slot * c->plan.staging_slot;
+    QtArea up = kQtParam;
+    if (goal == FIC_QT_RD_LAMBDA) {
+        for (int p = 0; p < c->planes; p++) ((uint32_t*)stage)[p] = (uint32_t)values[p];
+    } else if (goal == FIC_QT_RD_LEAVES) {
+        up = kQtRanks;
+        for (int p = 0; p < c->planes; p++) ((uint32_t*)stage)[p] = qt_rank(values[p], c->plan);
+    } else {                                           // the summed gain has to reach sum S_top - max_sse
+        up = kQtValues;
+        const uint64_t cap = (uint64_t)INT64_MAX;
+        for (int p = 0; p < c->planes; p++) ((long long*)(stage + c->plan.staging_values))[p] = (long long)(values[p] < cap ? values[p] : cap);
+    }
+    return qt_ctx_run_any(c, kRuleRd, goal, up, slot, s);
+}
+
+int fic_qt_ctx_sync(fic_qt_ctx* c)
+{
+    if (!c) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_sync: null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rc = ctx_sync(c)) return rc;
+    // the levels ran on the same stream: nothing of theirs is pending either, and none waits for that stream again
+    for (int l = 0; l < c->L.nl; l++)
+        if (int rc = c->colour ? fic_rgb_ctx_sync(c->rgb[l]) : fic_ctx_sync(c->grey[l])) return rc;
+    return FIC_OK;
+}
+
+int fic_qt_ctx_get_results_host(fic_qt_ctx* c, int32_t* n_leaves, uint32_t* param, uint64_t* stats)
+{
+    if (!c) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_get_results_host: null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any) return fail(FIC_E_STATE, "fic_qt_ctx_get_results_host: nothing encoded yet");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    // the three areas follow each other in the store: one copy
+    const QtBatchPlan& Q = c->plan;
+    const size_t P = (size_t)c->planes, o0 = Q.a[kQtNLeaves].off, bytes = Q.a[kQtStats].off + P * 32 - o0;
+    std::vector<char> buf(bytes);
+    HIP_TRY(hipMemcpy(buf.data(), c->store + o0, bytes, hipMemcpyDeviceToHost));
+    if (n_leaves) memcpy(n_leaves, buf.data(), P * 4);
+    if (param) memcpy(param, buf.data() + (Q.a[kQtParam].off - o0), P * 4);
+    if (stats) memcpy(stats, buf.data() + (Q.a[kQtStats].off - o0), P * 32);
+    return FIC_OK;
+}
+
+int fic_qt_ctx_get_leaves_host(fic_qt_ctx* c, int plane, int32_t* leaves, int64_t capacity, int* n_leaves)
+{
+    if (!c || !leaves || !n_leaves) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_get_leaves_host: null argument");
+    if (plane < 0 || plane >= c->planes) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_get_leaves_host: plane %d outside 0..%d", plane, c->planes - 1);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any) return fail(FIC_E_STATE, "fic_qt_ctx_get_leaves_host: nothing encoded yet");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    int n = 0;
+    HIP_TRY(hipMemcpy(&n, c->at<int>(kQtNLeaves) + plane, sizeof(int), hipMemcpyDeviceToHost));
+    *n_leaves = n;
+    if (capacity < n) return fail(FIC_E_CAPACITY, "%s encode: %d leaves, room for %lld", qt_kind(c), n, (long long)capacity);
+    const size_t stride = c->plan.a[kQtLeaves].stride;
+    HIP_TRY(hipMemcpy(leaves, c->at<int32_t>(kQtLeaves) + (size_t)plane * stride, (size_t)n * c->plan.leaf_ints * 4, hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
+int fic_qt_ctx_result_device_ptrs(fic_qt_ctx* c, void** leaves, void** n_leaves, void** param, void** stats)
+{
+    if (!c) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_result_device_ptrs: null context");
+    if (leaves) *leaves = c->at<void>(kQtLeaves);
+    if (n_leaves) *n_leaves = c->at<void>(kQtNLeaves);
+    if (param) *param = c->at<void>(kQtParam);
+    if (stats) *stats = c->at<void>(kQtStats);
+    return FIC_OK;
+}
+
+}  // extern "C"

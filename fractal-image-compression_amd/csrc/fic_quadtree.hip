@@ -22,6 +22,8 @@
 //                            encode by rate-distortion pruning: the keys e(v) and gains G_v of min D + lambda N,
 //                            and the select of the key at which the summed gain reaches an SSE target
 // The walkers (k_qt_count, k_qt_scatter, k_qt_tree_stats) take the split rule as a type: QtByThreshold (4.13) or QtByKey (4.23).
+// Every encoder kernel takes a batch of planes (FicQtPlanes in fic_launch.h): the plane is a grid dimension, so no
+// workgroup spans two planes, and the one-shot entries are the batch of one plane.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -135,15 +137,22 @@ __device__ __forceinline__ uint32_t qt_row_sse(const int32_t* __restrict__ prow,
 // k_leaf_sse<Fmt, B>: sse[j] = sum over the block's pixels (and channels) of (orig - value)^2, exact.  One thread per pixel row
 // of a range block, ordered like k_decode_paint (block row, pixel row, block column); the B row sums of a block meet in sse[j]
 // (zeroed by the launcher) through integer atomics, so the result does not depend on their order.  At most
-// 256 * 3 * 255^2 < 2^32 per block.
+// 256 * 3 * 255^2 < 2^32 per block.  A batch: blockIdx.y is the plane -- image [planes][H][W], scaled [planes][Hs][Ws], qrows
+// [planes][Nr][QW], iso [planes][Nr], sse [planes][sse_stride]; the workgroups of a plane end with the plane, so none spans two.
 // ---------------------------------------------------------------------------------------------
 template <typename Fmt, int B>
 __global__ __launch_bounds__(256) void k_leaf_sse(const typename Fmt::Px* __restrict__ image, const typename Fmt::Px* __restrict__ scaled,
                                                   const int32_t* __restrict__ qrows, const int32_t* __restrict__ iso,
-                                                  uint32_t* __restrict__ sse, FicGeom g)
+                                                  uint32_t* __restrict__ sse, FicGeom g, size_t sse_stride)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= g.Nr * B) return;
+    const size_t p = blockIdx.y;
+    image += p * g.W * g.H;
+    scaled += p * g.Ws * g.Hs;
+    qrows += p * g.Nr * Fmt::QW;
+    if (iso) iso += p * g.Nr;
+    sse += p * sse_stride;
     const int bx = t % g.Rw, row = t / g.Rw;
     const int ry = row % B, by = row / B;
     const int j = by * g.Rw + bx;
@@ -166,39 +175,69 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const typename Fmt::Px* __rest
 // the rows at its offset: {x, y, B} and the level's quantised row, {idx_local, qa, qb, iso} (grey) or {idx_local, q1, q2, q3,
 // q4} (colour; QtRgbIso: + iso).
 // ---------------------------------------------------------------------------------------------
+// A batch of planes (blockIdx.y of the walkers and the key kernels; one plane: all strides unused): the arrays of plane p start
+// p strides behind those of plane 0 -- sse_stride u32 for the SSE of every level, Nr[l] rows for qrows and iso -- and the
+// threshold rule reads its threshold from thr[p] (device memory: given by the caller or left there by the budget's select).
 struct FicQtLevels {
     const uint32_t* sse[3];
-    const int32_t* qrows[3];     // Fmt::QW ints per range block (k_qt_scatter)
+    const int32_t* qrows[3];     // QW ints per range block (k_qt_scatter)
     const int32_t* iso[3];       // NULL: n_iso = 1 (iso 0)
     int Rw[3];
+    int Nr[3];                   // range blocks per plane and level
     int nl;                      // levels
     int B_max;
     int Rw_top, Ntop;
-    float threshold;
+    int QW;                      // ints per row of qrows (0: none given)
+    size_t sse_stride;
+    float threshold;             // thr == NULL: the threshold, by value
+    const float* thr;            // [planes]
 };
+
+// Entry l of a per-level array by selection, not by address: the walkers' l is a run-time value, and the levels of a plane
+// (qt_plane's copy) stay in registers only while nothing indexes them in memory.
+template <typename T>
+__device__ __forceinline__ T qt_lv(const T (&a)[3], int l) { return l == 0 ? a[0] : (l == 1 ? a[1] : a[2]); }
+
+// The levels of plane p: what the per-block code below works on, whichever plane it is
+__device__ __forceinline__ FicQtLevels qt_plane(FicQtLevels L, int p)
+{
+#pragma unroll
+    for (int l = 0; l < 3; l++)
+        if (l < L.nl) {
+            L.sse[l] += (size_t)p * L.sse_stride;
+            if (L.qrows[l]) L.qrows[l] += (size_t)p * L.Nr[l] * L.QW;
+            if (L.iso[l]) L.iso[l] += (size_t)p * L.Nr[l];
+        }
+    if (L.thr) L.threshold = L.thr[p];
+    return L;
+}
 
 __device__ __forceinline__ bool qt_split(const FicQtLevels& L, int l, int x, int y)
 {
     if (l >= L.nl - 1) return false;
     const int B = L.B_max >> l;
-    const uint32_t s = L.sse[l][(y / B) * L.Rw[l] + x / B];
+    const uint32_t s = qt_lv(L.sse, l)[(y / B) * qt_lv(L.Rw, l) + x / B];
     return (double)s > (double)L.threshold * (double)B * (double)B;
 }
 
 // The split rules of the walkers: split(L, l, x, y) for the block of level l at pixel (x, y).  QtByThreshold: the rule above.
 // QtByKey: a block above B_min splits iff its key e(v) > lambda; keys as k_qt_rd_keys writes them (level 0,
 // then level 1), lambda read from device memory, where the select left it.
+// at(p): the rule of plane p (keys [planes][nkeys], lambda [planes]; the threshold comes with qt_plane).
 struct QtByThreshold {
+    __device__ __forceinline__ QtByThreshold at(int) const { return *this; }
     __device__ __forceinline__ bool operator()(const FicQtLevels& L, int l, int x, int y) const { return qt_split(L, l, x, y); }
 };
 struct QtByKey {
     const uint32_t* keys;
     const uint32_t* lambda;
+    int nkeys;
+    __device__ __forceinline__ QtByKey at(int p) const { return QtByKey{keys + (size_t)p * nkeys, lambda + p, nkeys}; }
     __device__ __forceinline__ bool operator()(const FicQtLevels& L, int l, int x, int y) const
     {
         if (l >= L.nl - 1) return false;
         const int B = L.B_max >> l;
-        return keys[(l ? L.Ntop : 0) + (y / B) * L.Rw[l] + x / B] > *lambda;
+        return keys[(l ? L.Ntop : 0) + (y / B) * qt_lv(L.Rw, l) + x / B] > *lambda;
     }
 };
 
@@ -228,22 +267,28 @@ __device__ __forceinline__ void qt_walk(const FicQtLevels& L, const Split& split
 }
 
 template <typename Split>
-__global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L, Split split, int* __restrict__ counts)
+__global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L0, Split split0, int* __restrict__ counts)      // counts [planes][Ntop]
 {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= L.Ntop) return;
+    const int t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    if (t >= L0.Ntop) return;
+    const FicQtLevels L = qt_plane(L0, p);
+    const Split split = split0.at(p);
     int n = 0;
     qt_walk(L, split, t, [&](int, int, int) { n++; });
-    counts[t] = n;
+    counts[(size_t)p * L.Ntop + t] = n;
 }
 
 // Exclusive scan of counts[0 .. n) into offs[0 .. n), offs[n] = the total.  One workgroup: every thread sums a contiguous
-// slice, the slice sums are scanned in LDS, then every thread writes its slice's offsets.
+// slice, the slice sums are scanned in LDS, then every thread writes its slice's offsets.  A batch: one workgroup per plane
+// (blockIdx.x) on counts [planes][n] and offs [planes][n + 1]; totals (NULL or [planes]) gets every plane's total once more.
 #define FIC_QT_SCAN_THREADS 1024
-__global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __restrict__ counts, int* __restrict__ offs, int n)
+__global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __restrict__ counts, int* __restrict__ offs, int n,
+                                                                 int* __restrict__ totals)
 {
     __shared__ int part[FIC_QT_SCAN_THREADS];
     const int t = threadIdx.x;
+    counts += (size_t)blockIdx.x * n;
+    offs += (size_t)blockIdx.x * (n + 1);
     const int per = (n + FIC_QT_SCAN_THREADS - 1) / FIC_QT_SCAN_THREADS;
     const int i0 = t * per, i1 = i0 + per < n ? i0 + per : n;
     int s = 0;
@@ -261,27 +306,35 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
         offs[i] = run;
         run += counts[i];
     }
-    if (t == FIC_QT_SCAN_THREADS - 1) offs[n] = part[t];
+    if (t == FIC_QT_SCAN_THREADS - 1) {
+        offs[n] = part[t];
+        if (totals) totals[blockIdx.x] = part[t];
+    }
 }
 
 // Leaf rows of Fmt::QW + 3 ints, formats with kIso one more: the iso column follows the quantised row
 template <typename Fmt, typename Split>
-__global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L, Split split, const int* __restrict__ offs, int32_t* __restrict__ leaves)
+__global__ __launch_bounds__(256) void k_qt_scatter(FicQtLevels L0, Split split0, const int* __restrict__ offs, int32_t* __restrict__ leaves,
+                                                    size_t leaf_stride)      // offs [planes][Ntop + 1], leaves [planes][leaf_stride] ints
 {
     constexpr int QW = Fmt::QW;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= L.Ntop) return;
-    int o = offs[t];
+    const int t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    if (t >= L0.Ntop) return;
+    const FicQtLevels L = qt_plane(L0, p);
+    const Split split = split0.at(p);
+    leaves += (size_t)p * leaf_stride;
+    int o = offs[(size_t)p * (L.Ntop + 1) + t];
     qt_walk(L, split, t, [&](int x, int y, int l) {
         const int B = L.B_max >> l;
-        const int j = (y / B) * L.Rw[l] + x / B;
+        const int j = (y / B) * qt_lv(L.Rw, l) + x / B;
+        const int32_t *rows = qt_lv(L.qrows, l), *isos = qt_lv(L.iso, l);
         int32_t* r = leaves + Fmt::kLeafInts * (size_t)o;
         r[0] = x;
         r[1] = y;
         r[2] = B;
 #pragma unroll
-        for (int k = 0; k < QW; k++) r[3 + k] = L.qrows[l][QW * j + k];
-        if constexpr (Fmt::kIso) r[3 + QW] = L.iso[l] ? L.iso[l][j] : 0;
+        for (int k = 0; k < QW; k++) r[3 + k] = rows[QW * j + k];
+        if constexpr (Fmt::kIso) r[3 + QW] = isos ? isos[j] : 0;
         o++;
     });
 }
@@ -300,9 +353,11 @@ __device__ __forceinline__ uint32_t qt_key(const FicQtLevels& L, int l, int j)
     return k > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)k;
 }
 
-__global__ __launch_bounds__(256) void k_qt_keys(FicQtLevels L, int n1, uint32_t* __restrict__ keys)
+__global__ __launch_bounds__(256) void k_qt_keys(FicQtLevels L0, int n1, uint32_t* __restrict__ keys)      // keys [planes][Ntop + n1]
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
+    const FicQtLevels L = qt_plane(L0, blockIdx.y);
+    keys += (size_t)blockIdx.y * (L.Ntop + n1);
     if (t < L.Ntop) {
         keys[t] = qt_key(L, 0, t);
     } else if (t < L.Ntop + n1) {
@@ -357,11 +412,16 @@ __device__ __forceinline__ void qt_select_resolve(const uint32_t* __restrict__ b
 
 // One pass: 256 threads per workgroup with a grid stride over the keys, a 256-bin histogram in LDS, one global atomic per
 // non-empty bin.
-__global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t rank, uint32_t* __restrict__ bins,
-                                                        int pass)
+// A batch is P independent selects, blockIdx.y the plane: keys [planes][n], work [planes][FIC_QT_SELECT_WORDS] (bins, then the
+// result), and the rank of plane p is ranks[p], read from device memory (ranks NULL: `rank`).
+__global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t rank, const uint32_t* __restrict__ ranks,
+                                                        uint32_t* __restrict__ work, int pass)
 {
     __shared__ uint32_t hist[256];
     hist[threadIdx.x] = 0;
+    keys += (size_t)blockIdx.y * n;
+    uint32_t* bins = work + (size_t)blockIdx.y * FIC_QT_SELECT_WORDS;
+    if (ranks) rank = ranks[blockIdx.y];
     uint32_t prefix, rem;
     qt_select_resolve(bins, pass, rank, prefix, rem);       // its barriers also cover hist's zeroes
     const int shift = 24 - 8 * pass;
@@ -376,8 +436,13 @@ __global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restri
 
 // One workgroup: resolves the last pass.  out = {K, the bits of the threshold, #{keys > K}, 0}; the threshold is the smallest
 // float >= K / 256: K rounded up to a float, times 2^-8 (exact).
-__global__ __launch_bounds__(256) void k_qt_select_final(const uint32_t* __restrict__ bins, uint32_t rank, uint32_t* __restrict__ out)
+// One workgroup per plane (blockIdx.x); param (NULL or [planes]) gets word `param_word` of the plane's result: the rule's parameter.
+__global__ __launch_bounds__(256) void k_qt_select_final(uint32_t* __restrict__ work, uint32_t rank, const uint32_t* __restrict__ ranks,
+                                                         uint32_t* __restrict__ param, int param_word)
 {
+    const uint32_t* bins = work + (size_t)blockIdx.x * FIC_QT_SELECT_WORDS;
+    uint32_t* out = work + (size_t)blockIdx.x * FIC_QT_SELECT_WORDS + 4 * 256;
+    if (ranks) rank = ranks[blockIdx.x];
     uint32_t K, rem;
     qt_select_resolve(bins, 4, rank, K, rem);
     if (threadIdx.x == 0) {
@@ -385,6 +450,7 @@ __global__ __launch_bounds__(256) void k_qt_select_final(const uint32_t* __restr
         out[1] = __float_as_uint(__fmul_rn(__uint2float_ru(K), 0x1p-8f));
         out[2] = rank - rem;
         out[3] = 0;
+        if (param) param[blockIdx.x] = out[param_word];
     }
 }
 
@@ -392,14 +458,17 @@ __global__ __launch_bounds__(256) void k_qt_select_final(const uint32_t* __restr
 // of side B_max, B_max / 2, B_max / 4.  One thread per top-level block, k_qt_count's walk; wave sums, then one atomic per
 // wave and non-zero value.
 template <typename Split>
-__global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L, Split split, unsigned long long* __restrict__ stats)
+__global__ __launch_bounds__(256) void k_qt_tree_stats(FicQtLevels L0, Split split0, unsigned long long* __restrict__ stats)   // stats [planes][4]
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
+    const FicQtLevels L = qt_plane(L0, blockIdx.y);
+    const Split split = split0.at(blockIdx.y);
+    stats += 4 * (size_t)blockIdx.y;
     unsigned long long v[4] = {0, 0, 0, 0};
     if (t < L.Ntop)
         qt_walk(L, split, t, [&](int x, int y, int l) {
             const int B = L.B_max >> l;
-            v[0] += L.sse[l][(y / B) * L.Rw[l] + x / B];
+            v[0] += qt_lv(L.sse, l)[(y / B) * qt_lv(L.Rw, l) + x / B];
             v[1 + l]++;
         });
 #pragma unroll
@@ -466,10 +535,14 @@ __device__ __forceinline__ uint32_t qt_rd_k_top(const FicQtLevels& L, int j)    
     return (uint32_t)hi;
 }
 
-__global__ __launch_bounds__(256) void k_qt_rd_keys(FicQtLevels L, int n1, uint32_t* __restrict__ keys, long long* __restrict__ gains,
-                                                    unsigned long long* __restrict__ top_sum)
+__global__ __launch_bounds__(256) void k_qt_rd_keys(FicQtLevels L0, int n1, uint32_t* __restrict__ keys, long long* __restrict__ gains,
+                                                    unsigned long long* __restrict__ top_sum)   // keys, gains [planes][Ntop + n1], top_sum [planes]
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
+    const FicQtLevels L = qt_plane(L0, blockIdx.y);
+    keys += (size_t)blockIdx.y * (L.Ntop + n1);
+    gains += (size_t)blockIdx.y * (L.Ntop + n1);
+    top_sum += blockIdx.y;
     unsigned long long s_top = 0;
     if (t < L.Ntop) {
         const long long S = L.sse[0][t], kids = qt_child_sum(L, 0, t);
@@ -538,12 +611,19 @@ __device__ __forceinline__ long long qt_select_w_need(const unsigned long long* 
 }
 
 // One pass: k_qt_select_hist with the gains summed per bin (64-bit LDS adds, one global atomic per bin with a non-zero sum).
+// A batch, as k_qt_select_hist: blockIdx.y the plane, keys and gains [planes][n], total [planes], work [planes]
+// [FIC_QT_SELECT_W_WORDS], and the value of plane p is values[p] (values NULL: `value`).
 __global__ __launch_bounds__(256) void k_qt_select_hist_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
                                                           const unsigned long long* __restrict__ total, long long value,
-                                                          long long* __restrict__ bins, int pass)
+                                                          const long long* __restrict__ values, long long* __restrict__ work, int pass)
 {
     __shared__ unsigned long long hist[256];
     hist[threadIdx.x] = 0;
+    keys += (size_t)blockIdx.y * n;
+    gains += (size_t)blockIdx.y * n;
+    if (total) total += blockIdx.y;
+    if (values) value = values[blockIdx.y];
+    long long* bins = work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS;
     uint32_t prefix;
     bool none;
     qt_select_w_resolve(bins, pass, qt_select_w_need(total, value), prefix, none);      // its barriers also cover hist's zeroes
@@ -561,10 +641,18 @@ __global__ __launch_bounds__(256) void k_qt_select_hist_w(const uint32_t* __rest
 // The last step, again over all keys: out u64 [4], zeroed by the launcher = {b in the low 32 bits, #{keys > b}, the sum of
 // their gains (signed), 0}.  b = max{key < x0} or 0; the keys > b are those >= max(x0, 1).  Wave sums, then one atomic
 // each per wave and non-zero value.
+// param (NULL or u32 [planes], zeroed by the launcher) gets every plane's b once more: the lambda its walkers read.
 __global__ __launch_bounds__(256) void k_qt_select_final_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
                                                            const unsigned long long* __restrict__ total, long long value,
-                                                           const long long* __restrict__ bins, unsigned long long* __restrict__ out)
+                                                           const long long* __restrict__ values, unsigned long long* __restrict__ work,
+                                                           uint32_t* __restrict__ param)
 {
+    keys += (size_t)blockIdx.y * n;
+    gains += (size_t)blockIdx.y * n;
+    if (total) total += blockIdx.y;
+    if (values) value = values[blockIdx.y];
+    const long long* bins = (const long long*)work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS;
+    unsigned long long* out = work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS + 4 * 256;
     uint32_t prefix;
     bool none;
     qt_select_w_resolve(bins, 4, qt_select_w_need(total, value), prefix, none);
@@ -585,6 +673,7 @@ __global__ __launch_bounds__(256) void k_qt_select_final_w(const uint32_t* __res
     }
     if ((threadIdx.x & 63) == 0) {
         if (b) atomicMax((uint32_t*)out, b);
+        if (b && param) atomicMax(param + blockIdx.y, b);
         if (cnt) atomicAdd(out + 1, cnt);
         if (gain) atomicAdd(out + 2, gain);
     }
@@ -692,20 +781,25 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt:
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
+// planes of a launch and the stride of its SSE arrays (P NULL: one plane)
+static inline int qt_planes(const FicQtPlanes* P) { return P ? P->planes : 1; }
+
 template <typename Fmt>
 int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* scaled, const int32_t* qrows, const int32_t* iso,
-                        uint32_t* sse, const FicGeom& g, hipStream_t s)
+                        uint32_t* sse, const FicGeom& g, hipStream_t s, const FicQtPlanes* P)
 {
-    if (hipMemsetAsync(sse, 0, (size_t)g.Nr * sizeof(uint32_t), s) != hipSuccess) return -1;
+    const size_t stride = P ? P->sse_stride : (size_t)g.Nr;
+    if (hipMemset2DAsync(sse, stride * sizeof(uint32_t), 0, (size_t)g.Nr * sizeof(uint32_t), (size_t)qt_planes(P), s) != hipSuccess) return -1;
     auto k = g.B == 4 ? k_leaf_sse<Fmt, 4> : (g.B == 8 ? k_leaf_sse<Fmt, 8> : k_leaf_sse<Fmt, 16>);
-    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256), dim3(256), 0, s, image, scaled, qrows, iso, sse, g);
+    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256, qt_planes(P)), dim3(256), 0, s, image, scaled, qrows, iso, sse, g, stride);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-// qrows / iso NULL: for the kernels that read the SSE alone
+// qrows / iso NULL: for the kernels that read the SSE alone.  P: the strides of a batch and, for the threshold rule (by_threshold),
+// its thresholds: P->param as floats
 static FicQtLevels qt_levels_arg(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw, int nl,
-                                 int B_max, int Rw_top, int Ntop, float threshold)
+                                 int B_max, int Rw_top, int Ntop, float threshold, int QW, const FicQtPlanes* P, bool by_threshold)
 {
     FicQtLevels L{};
     for (int l = 0; l < nl; l++) {
@@ -713,68 +807,75 @@ static FicQtLevels qt_levels_arg(const uint32_t* const* sse, const int32_t* cons
         L.qrows[l] = qrows ? qrows[l] : nullptr;
         L.iso[l] = iso ? iso[l] : nullptr;
         L.Rw[l] = Rw[l];
+        L.Nr[l] = P ? P->Nr[l] : 0;
     }
     L.nl = nl;
     L.B_max = B_max;
     L.Rw_top = Rw_top;
     L.Ntop = Ntop;
+    L.QW = qrows ? QW : 0;
+    L.sse_stride = P ? P->sse_stride : 0;
     L.threshold = threshold;
+    L.thr = P && by_threshold ? (const float*)P->param : nullptr;
     return L;
 }
 
 int fic_launch_qt_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                       hipStream_t s)
+                       hipStream_t s, const FicQtPlanes* P)
 {
-    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f);
-    hipLaunchKernelGGL(k_qt_keys, dim3((Ntop + n1 + 255) / 256), dim3(256), 0, s, L, n1, keys);
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false);
+    hipLaunchKernelGGL(k_qt_keys, dim3((Ntop + n1 + 255) / 256, qt_planes(P)), dim3(256), 0, s, L, n1, keys);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s)
+int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s, const FicQtPlanes* P, int param_word)
 {
-    if (hipMemsetAsync(work, 0, FIC_QT_SELECT_WORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
+    const int planes = qt_planes(P);
+    if (hipMemsetAsync(work, 0, (size_t)planes * FIC_QT_SELECT_WORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
     const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
+    const uint32_t* ranks = P ? P->ranks : nullptr;
     for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_qt_select_hist, dim3(nb), dim3(256), 0, s, keys, n, rank, work, pass);
+        hipLaunchKernelGGL(k_qt_select_hist, dim3(nb, planes), dim3(256), 0, s, keys, n, rank, ranks, work, pass);
         FIC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_qt_select_final, dim3(1), dim3(256), 0, s, (const uint32_t*)work, rank, work + 4 * 256);
+    hipLaunchKernelGGL(k_qt_select_final, dim3(planes), dim3(256), 0, s, work, rank, ranks, P ? P->param : nullptr, param_word);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
 template <typename Split>
-static int qt_tree_stats(const FicQtLevels& L, const Split& split, unsigned long long* stats, hipStream_t s)
+static int qt_tree_stats(const FicQtLevels& L, const Split& split, unsigned long long* stats, hipStream_t s, int planes)
 {
-    if (hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -1;
-    hipLaunchKernelGGL(k_qt_tree_stats<Split>, dim3((L.Ntop + 255) / 256), dim3(256), 0, s, L, split, stats);
+    if (hipMemsetAsync(stats, 0, (size_t)planes * 4 * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_qt_tree_stats<Split>, dim3((L.Ntop + 255) / 256, planes), dim3(256), 0, s, L, split, stats);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
 int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
-                             unsigned long long* stats, hipStream_t s)
+                             unsigned long long* stats, hipStream_t s, const FicQtPlanes* P)
 {
-    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold), QtByThreshold{}, stats, s);
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold, 0, P, true), QtByThreshold{}, stats, s, qt_planes(P));
 }
 
 int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys,
-                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s)
+                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s, const FicQtPlanes* P)
 {
-    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f), QtByKey{keys, lambda}, stats, s);
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false), QtByKey{keys, lambda, P ? P->nkeys : 0}, stats, s,
+                         qt_planes(P));
 }
 
 template <typename Fmt, typename Split>
-static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int* offs, int32_t* leaves, hipStream_t s)
+static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes* P)
 {
-    const int nb = (L.Ntop + 255) / 256;
-    hipLaunchKernelGGL(k_qt_count<Split>, dim3(nb), dim3(256), 0, s, L, split, counts);
+    const int nb = (L.Ntop + 255) / 256, planes = qt_planes(P);
+    hipLaunchKernelGGL(k_qt_count<Split>, dim3(nb, planes), dim3(256), 0, s, L, split, counts);
     FIC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_qt_scan, dim3(1), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, L.Ntop);
+    hipLaunchKernelGGL(k_qt_scan, dim3(planes), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, L.Ntop, P ? P->n_leaves : nullptr);
     FIC_LAUNCH_CHECK();
     if (leaves) {
-        hipLaunchKernelGGL((k_qt_scatter<Fmt, Split>), dim3(nb), dim3(256), 0, s, L, split, (const int*)offs, leaves);
+        hipLaunchKernelGGL((k_qt_scatter<Fmt, Split>), dim3(nb, planes), dim3(256), 0, s, L, split, (const int*)offs, leaves, P ? P->leaf_stride : (size_t)0);
         FIC_LAUNCH_CHECK();
     }
     return 0;
@@ -783,39 +884,43 @@ static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int
 template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                           int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s)
+                          hipStream_t s, const FicQtPlanes* P)
 {
-    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold), QtByThreshold{}, counts, offs, leaves, s);
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold, Fmt::QW, P, true), QtByThreshold{}, counts, offs, leaves, s, P);
 }
 
 template <typename Fmt>
 int fic_launch_qt_compact_rd(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                              int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys, const uint32_t* lambda, int* counts,
-                             int* offs, int32_t* leaves, hipStream_t s)
+                             int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes* P)
 {
-    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, 0.0f), QtByKey{keys, lambda}, counts, offs, leaves, s);
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, 0.0f, Fmt::QW, P, false), QtByKey{keys, lambda, P ? P->nkeys : 0},
+                           counts, offs, leaves, s, P);
 }
 
 int fic_launch_qt_rd_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                          long long* gains, unsigned long long* top_sum, hipStream_t s)
+                          long long* gains, unsigned long long* top_sum, hipStream_t s, const FicQtPlanes* P)
 {
-    if (hipMemsetAsync(top_sum, 0, sizeof(unsigned long long), s) != hipSuccess) return -1;
-    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f);
-    hipLaunchKernelGGL(k_qt_rd_keys, dim3((Ntop + n1 + 255) / 256), dim3(256), 0, s, L, n1, keys, gains, top_sum);
+    if (hipMemsetAsync(top_sum, 0, (size_t)qt_planes(P) * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false);
+    hipLaunchKernelGGL(k_qt_rd_keys, dim3((Ntop + n1 + 255) / 256, qt_planes(P)), dim3(256), 0, s, L, n1, keys, gains, top_sum);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
 int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total, long long value,
-                           unsigned long long* work, hipStream_t s)
+                           unsigned long long* work, hipStream_t s, const FicQtPlanes* P)
 {
-    if (hipMemsetAsync(work, 0, FIC_QT_SELECT_W_WORDS * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const int planes = qt_planes(P);
+    if (hipMemsetAsync(work, 0, (size_t)planes * FIC_QT_SELECT_W_WORDS * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    if (P && hipMemsetAsync(P->param, 0, (size_t)planes * sizeof(uint32_t), s) != hipSuccess) return -1;      // k_qt_select_final_w's atomicMax
     const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
+    const long long* values = P ? P->values : nullptr;
     for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_qt_select_hist_w, dim3(nb), dim3(256), 0, s, keys, gains, n, total, value, (long long*)work, pass);
+        hipLaunchKernelGGL(k_qt_select_hist_w, dim3(nb, planes), dim3(256), 0, s, keys, gains, n, total, value, values, (long long*)work, pass);
         FIC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_qt_select_final_w, dim3(nb), dim3(256), 0, s, keys, gains, n, total, value, (const long long*)work, work + 4 * 256);
+    hipLaunchKernelGGL(k_qt_select_final_w, dim3(nb, planes), dim3(256), 0, s, keys, gains, n, total, value, values, work, P ? P->param : nullptr);
     FIC_LAUNCH_CHECK();
     return 0;
 }
@@ -835,11 +940,12 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
 
 #define FIC_QT_INSTANTIATE(Fmt)                                                                                                       \
     template int fic_launch_leaf_sse<Fmt>(const Fmt::Px*, const Fmt::Px*, const int32_t*, const int32_t*, uint32_t*, const FicGeom&,  \
-                                          hipStream_t);                                                                               \
+                                          hipStream_t, const FicQtPlanes*);                                                           \
     template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \
-                                            int, int, int, float, int*, int*, int32_t*, hipStream_t);                                 \
+                                            int, int, int, float, int*, int*, int32_t*, hipStream_t, const FicQtPlanes*);             \
     template int fic_launch_qt_compact_rd<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int, \
-                                               int, int, int, const uint32_t*, const uint32_t*, int*, int*, int32_t*, hipStream_t);   \
+                                               int, int, int, const uint32_t*, const uint32_t*, int*, int*, int32_t*, hipStream_t,    \
+                                               const FicQtPlanes*);                                                                   \
     template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const Fmt::Leaf*, int, FicDecodeState*, uint32_t*,     \
                                                      int, const FicGeom&, hipStream_t);
 FIC_QT_INSTANTIATE(QtGrey)

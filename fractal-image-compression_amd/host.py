@@ -264,6 +264,174 @@ class Encoder:
         return out
 
 
+class QuadtreeEncoder:
+    """Handle API of the quadtree codec (fic_qt_ctx_*): `planes` images of one geometry, every split rule, device
+    resident and asynchronous like Encoder.  colour=False: grey, leaf rows of 7 ints (write_run_quadtree); colour=True: joint RGB
+    with the isometry column, rows of 9 ints (write_run_rgb_quadtree_iso), n_iso 1 or 8.  wK = 0: full search at every level.
+    Plane p's results are those of the one-shot entry (encode_gray_quadtree*, encode_rgb_quadtree_iso*) on image p."""
+
+    def __init__(self, width, height, B_max, B_min, wK=0, n_iso=1, planes=1, colour=False, device=0):
+        L = capi.lib()
+        self.width, self.height, self.B_max, self.B_min, self.wK, self.n_iso = width, height, B_max, B_min, wK, n_iso
+        self.planes, self.colour, self.device = planes, bool(colour), device
+        self.cols = 9 if colour else 7
+        self.tag = 6 if colour else 2
+        self._keep = None
+        self._h = L.fic_qt_ctx_create(device, 1 if colour else 0, width, height, B_max, B_min, wK, n_iso, planes)
+        if not self._h:
+            raise FicError(L.fic_last_error_code() or -3, capi.last_error())
+        self.max_leaves = (width // B_min) * (height // B_min)      # rows per plane of the device leaf table
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.lib().fic_qt_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    # ---- input -----------------------------------------------------------------------------
+    def _set_device(self, t, itemsize, align, fn, what):
+        n = self.planes * self.height * self.width
+        if not t.is_cuda or t.element_size() != itemsize or not t.is_contiguous() or t.numel() != n:
+            raise FicError(-3, f"device input must be a contiguous {what} CUDA tensor [planes,H,W]")
+        t = capi.aligned_tensor(t, align)
+        capi.check(fn(self._h, C.c_void_p(t.data_ptr())))
+        self._keep = t
+
+    def set_gray(self, gray):
+        """A grey context's input: uint8 [planes,H,W] numpy array (uploaded once), or a torch CUDA uint8 tensor, used in place
+        and read at encode time exactly as Encoder.set_gray's (a misaligned view is cloned here, once)."""
+        L = capi.lib()
+        if hasattr(gray, "data_ptr"):
+            return self._set_device(gray, 1, 8, L.fic_qt_ctx_set_gray_device, "uint8")
+        g = np.ascontiguousarray(gray, np.uint8)
+        if g.size != self.planes * self.height * self.width:
+            raise FicError(-3, f"input has {g.size} pixels, expected {self.planes * self.height * self.width}")
+        capi.check(L.fic_qt_ctx_set_gray_host(self._h, capi.ptr(g, C.c_uint8)))
+
+    def set_argb(self, argb):
+        """int32 ARGB [planes,H,W]: a numpy array (either kind of context; a grey one takes the red channel, as Encoder.set_argb),
+        or for a colour context a torch CUDA int32 tensor, used in place as RgbEncoder.set_argb's."""
+        L = capi.lib()
+        if hasattr(argb, "data_ptr"):
+            return self._set_device(argb, 4, 4, L.fic_qt_ctx_set_argb_device, "int32")
+        a = np.ascontiguousarray(argb, np.int32)
+        if a.size != self.planes * self.height * self.width:
+            raise FicError(-3, "argb has the wrong number of pixels")
+        capi.check(L.fic_qt_ctx_set_argb_host(self._h, capi.ptr(a, C.c_int32)))
+
+    # ---- compute ---------------------------------------------------------------------------
+    def set_option(self, name, value):
+        """"search": "reference" / 0 or "lsq" / 1, the criterion of the per-level codebooks."""
+        if name == "search":
+            value = capi.search_id(value)
+        capi.check(capi.lib().fic_qt_ctx_set_option(self._h, name.encode(), int(value)))
+
+    def _per_plane(self, v, dtype):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            return np.full(self.planes, v, dtype)
+        if a.size != self.planes:
+            raise FicError(-3, f"{a.size} values for {self.planes} planes")
+        return np.ascontiguousarray(a.reshape(-1), dtype)
+
+    def encode(self, threshold=None, max_leaves=None, max_bytes=None, lam=None, max_sse=None, prune="rd", stream=None):
+        """Asynchronous on `stream` (a raw hipStream_t handle / torch stream, None = default).  Exactly one rule, its value a
+        scalar for all planes or one per plane: threshold= (the fixed-threshold rule), lam= / max_sse= (rate-distortion pruning,
+        DESIGN.md 4.23), max_leaves= / max_bytes= (a stream of the context's format) reached by pruning (prune="rd") or by
+        the threshold rule (prune="threshold", DESIGN.md 4.18: the reference criterion only)."""
+        L = capi.lib()
+        if sum(v is not None for v in (threshold, max_leaves, max_bytes, lam, max_sse)) != 1:
+            raise ValueError("pass exactly one of threshold=, max_leaves=, max_bytes=, lam= and max_sse=")
+        if prune not in ("rd", "threshold"):
+            raise ValueError("prune must be 'rd' or 'threshold'")
+        s = C.c_void_p(0 if stream is None else int(getattr(stream, "cuda_stream", stream)))
+        if threshold is not None:
+            t = self._per_plane(threshold, np.float32)
+            capi.check(L.fic_qt_ctx_encode_threshold(self._h, capi.ptr(t, C.c_float), s))
+            self._threshold_rule = True                       # what results() makes of param: set once the encode is accepted
+            return
+        if max_bytes is not None:
+            b = self._per_plane(max_bytes, np.int64)
+            max_leaves = [capi.quadtree_leaves_for_bytes(self.tag, self.n_iso, int(x)) for x in b]
+        if max_leaves is not None and prune == "threshold":
+            m = self._per_plane(max_leaves, np.int64)
+            capi.check(L.fic_qt_ctx_encode_budget(self._h, capi.ptr(m, C.c_int64), s))
+            self._threshold_rule = True
+            return
+        goal, v = (capi.QT_RD_LAMBDA, lam) if lam is not None else ((capi.QT_RD_SSE, max_sse) if max_sse is not None else (capi.QT_RD_LEAVES, max_leaves))
+        vals = [int(x) for x in (np.asarray(v, object).reshape(-1).tolist() if np.ndim(v) else [v] * self.planes)]
+        if len(vals) != self.planes:
+            raise FicError(-3, f"{len(vals)} values for {self.planes} planes")
+        if any(not 0 <= x < 1 << 64 for x in vals):
+            raise FicError(-3, f"{('lam', 'max_leaves', 'max_sse')[goal]}: a value outside 0 .. 2^64 - 1")
+        u = np.array(vals, np.uint64)
+        capi.check(L.fic_qt_ctx_encode_rd(self._h, goal, capi.ptr(u, C.c_uint64), s))
+        self._threshold_rule = False
+
+    def sync(self):
+        capi.check(capi.lib().fic_qt_ctx_sync(self._h))
+
+    # ---- results ---------------------------------------------------------------------------
+    def results_host(self):
+        """(n_leaves int32 [planes], param uint32 [planes], stats uint64 [planes, 4]) of the last encode, one copy
+        (fic_qt_ctx_get_results_host).  param: lambda, or the bits of the float32 threshold in force."""
+        n, prm, st = np.zeros(self.planes, np.int32), np.zeros(self.planes, np.uint32), np.zeros((self.planes, 4), np.uint64)
+        capi.check(capi.lib().fic_qt_ctx_get_results_host(self._h, capi.ptr(n, C.c_int32), capi.ptr(prm, C.c_uint32), capi.ptr(st, C.c_uint64)))
+        return n, prm, st
+
+    def results(self, threshold_rule=None):
+        """[(leaves int32 [n, cols], param, stats uint64 [4])] per plane, as the one-shot entries return them: param is the
+        float32 threshold after an encode under the threshold rule (threshold=, or prune="threshold"), else lambda as an int.
+        threshold_rule: None = what the last encode of this object was."""
+        n, prm, st = self.results_host()
+        if threshold_rule is None:
+            threshold_rule = getattr(self, "_threshold_rule", False)
+        out = []
+        for p in range(self.planes):
+            leaves = np.zeros((max(int(n[p]), 1), self.cols), np.int32)
+            got = C.c_int()
+            capi.check(capi.lib().fic_qt_ctx_get_leaves_host(self._h, p, capi.ptr(leaves, C.c_int32), leaves.shape[0], C.byref(got)))
+            out.append((leaves[:got.value].copy(), prm[p:p + 1].view(np.float32)[0] if threshold_rule else int(prm[p]), st[p].copy()))
+        return out
+
+    def results_device(self):
+        """torch tensors aliasing the context's device results (no copy; the addresses never change): "leaves" int32 [planes,
+        max_leaves, cols] (rows of a plane beyond its n_leaves are unspecified), "n_leaves" int32 [planes], "param" int32 [planes]
+        (lambda, or the threshold's bits: .view(torch.float32)), "stats" int64 [planes, 4]."""
+        import torch
+        p = [C.c_void_p() for _ in range(4)]
+        capi.check(capi.lib().fic_qt_ctx_result_device_ptrs(self._h, *[C.byref(x) for x in p]))
+        dev = torch.device("cuda", self.device)
+
+        def t(ptr, shape, ts):
+            return torch.as_tensor(_DevArray(ptr.value, shape, ts), device=dev)
+
+        P = self.planes
+        return {"leaves": t(p[0], (P, self.max_leaves, self.cols), "<i4"), "n_leaves": t(p[1], (P,), "<i4"),
+                "param": t(p[2], (P,), "<i4"), "stats": t(p[3], (P, 4), "<i8")}
+
+    def write_runs(self):
+        """One stream per plane from the last encode's tables, through the existing writers (tag 2 / tag 6)."""
+        runs = []
+        for leaves, _, _ in self.results():
+            if self.colour:
+                runs.append(capi.write_run_rgb_quadtree_iso(leaves, self.width, self.height, self.B_max, self.B_min, self.wK))
+            else:
+                runs.append(capi.write_run_quadtree(leaves, self.width, self.height, self.B_max, self.B_min, self.wK, self.n_iso))
+        return runs
+
+
 def encode_rgb_per_channel(rgb, B, wK=None, n_iso=1, device=0, sweep=0):
     """BASELINE.json config 5: a batch of colour images encoded as 3 independent grey planes each (NOT the
     reference's joint-RGB fit, which is `capi.encode_rgb`).  rgb: uint8 [N,H,W,3] (or [H,W,3]).

@@ -495,6 +495,51 @@ FIC_API int fic_debug_qt_rd_keys(int device, const uint32_t* sse, int w, int h, 
 FIC_API int fic_debug_qt_select_weighted(int device, const uint32_t* keys, const int64_t* gains, int64_t n, int64_t need,
                                          uint32_t* key_out, int64_t* above_out, int64_t* gain_out);
 
+/* ---- batched quadtree encoder handle ------------------------------------------------------------------------- */
+/* The quadtree encodes above for `planes` images of one geometry at once, as a handle like fic_ctx / fic_rgb_ctx: the context
+ * owns one context per level (created with `planes`) and the device stores of the quadtree layer, reads a caller's device
+ * tensor in place and runs asynchronously on the caller's stream.  Plane p of a batch is, bit for bit, what the one-shot entry
+ * of the same format returns for image p alone; no new stream format: each plane's table goes through the writers above.
+ *   colour   0: grey, leaf rows of 7 ints as fic_encode_gray_quadtree_u8's; 1: joint RGB with the isometry column, rows of 9
+ *            ints as fic_encode_rgb_quadtree_iso_argb's, n_iso 1 or 8 (without its last column a row is
+ *            fic_encode_rgb_quadtree_argb's)
+ * Levels, geometry and window are checked as in the one-shot entries; FIC_E_GEOMETRY also when planes is above 65535 or an
+ * index of the context -- planes * (w / B_min) * (h / B_min) * the ints of a row is the largest -- would pass 2^31 - 1.
+ * Every check comes before any device work. */
+typedef struct fic_qt_ctx fic_qt_ctx;
+FIC_API fic_qt_ctx* fic_qt_ctx_create(int device, int colour, int w, int h, int B_max, int B_min, int wK, int n_iso, int planes);
+FIC_API void fic_qt_ctx_destroy(fic_qt_ctx* ctx);
+/* Input [planes][h][w] under the contract of fic_ctx_set_gray_* / fic_rgb_ctx_set_argb_*: a host image is uploaded once into
+ * the context's copy; a device pointer stays the caller's, is handed to every level, never copied and read by every later
+ * encode at encode time (address a multiple of 8 for bytes, of 4 for ARGB, else FIC_E_ARGUMENT and the input in force stays).
+ * A grey context takes bytes (host or device) or host ARGB; a colour context takes ARGB (host or device). */
+FIC_API int fic_qt_ctx_set_gray_host(fic_qt_ctx* ctx, const uint8_t* gray);
+FIC_API int fic_qt_ctx_set_argb_host(fic_qt_ctx* ctx, const int32_t* argb);
+FIC_API int fic_qt_ctx_set_gray_device(fic_qt_ctx* ctx, const void* dev_gray);
+FIC_API int fic_qt_ctx_set_argb_device(fic_qt_ctx* ctx, const void* dev_argb);
+/* "search": 0 the reference's criterion for the per-level codebooks, 1 least squares (the `search` of the RD entries). */
+FIC_API int fic_qt_ctx_set_option(fic_qt_ctx* ctx, const char* name, int value);
+/* The three encodes: one value per plane (host arrays of `planes` values), asynchronous on `hip_stream` under the stream
+ * rule of fic_ctx_encode.  The values go up from a pinned buffer of the context and every rule's parameter is read from device
+ * memory: the call enqueues everything and returns without waiting for the device.
+ *   threshold   the fixed-threshold rule; a NaN is FIC_E_ARGUMENT
+ *   budget      the threshold chosen on the device for at most max_leaves[p] leaves (>= N_top, else FIC_E_ARGUMENT); on the
+ *               reference's criterion only: FIC_E_ARGUMENT under "search" = 1
+ *   rd          rate-distortion pruning, goal FIC_QT_RD_LAMBDA / _LEAVES / _SSE for all planes, values[p] as `value` above
+ * All ranges are checked for every plane before any launch; FIC_E_STATE without an input. */
+FIC_API int fic_qt_ctx_encode_threshold(fic_qt_ctx* ctx, const float* thresholds, void* hip_stream);
+FIC_API int fic_qt_ctx_encode_budget(fic_qt_ctx* ctx, const int64_t* max_leaves, void* hip_stream);
+FIC_API int fic_qt_ctx_encode_rd(fic_qt_ctx* ctx, int goal, const uint64_t* values, void* hip_stream);
+FIC_API int fic_qt_ctx_sync(fic_qt_ctx* ctx);
+/* Results of the last encode (the host getters wait for it).  n_leaves int32 [planes]; param uint32 [planes]: the bits of the
+ * threshold (threshold and budget rules) or lambda in force; stats uint64 [planes][4] as stats4 above.  Any may be NULL. */
+FIC_API int fic_qt_ctx_get_results_host(fic_qt_ctx* ctx, int32_t* n_leaves, uint32_t* param, uint64_t* stats);
+/* The leaf table of one plane, rows of 7 (grey) or 9 (colour) ints; *n_leaves is set on FIC_E_CAPACITY too. */
+FIC_API int fic_qt_ctx_get_leaves_host(fic_qt_ctx* ctx, int plane, int32_t* leaves, int64_t capacity, int* n_leaves);
+/* Device pointers of the same, stable for the life of the context: leaves int32 [planes][(w / B_min) * (h / B_min)][7 or 9]
+ * (a fixed stride per plane; the rows of a plane beyond its n_leaves are unspecified), n_leaves, param, stats as above. */
+FIC_API int fic_qt_ctx_result_device_ptrs(fic_qt_ctx* ctx, void** leaves, void** n_leaves, void** param, void** stats);
+
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
  *                     group-Fourier form, for 8 isometries at B = 8; k_sweep_fast otherwise)
