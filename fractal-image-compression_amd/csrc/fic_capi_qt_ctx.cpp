@@ -1,15 +1,14 @@
 // fic_capi_qt_ctx.cpp -- C ABI, the batched quadtree encoder handle (fic_qt_ctx_* of include/fic.h): `planes`
 // images of one geometry through the per-level contexts (created with `planes`) and the batched kernels of fic_quadtree.hip,
 // under the device-pointer contract and the stream rule of the other two handles.  An encode enqueues everything
-// on the caller's stream and returns: the per-plane parameters go up from a pinned staging buffer, every rule's parameter is
-// read from device memory by the kernels that need it, and nothing comes back before the caller asks.  Plane p of a batch is
-// what the one-shot entry of the same format (fic_capi_quadtree.cpp) returns for image p.  Host-side orchestration only.
+// on the caller's stream and returns: the per-plane parameters go up from a pinned staging buffer, and nothing comes back before
+// the caller asks.  This file is one of the two front ends of the one encode pipeline: what is its own is the input contract, the
+// staging slots and the level encodes on contexts of `planes`; everything behind them is qt_tree_run (fic_capi_quadtree.cpp),
+// which the one-shot entries of the same format run on a plan of one plane -- so plane p of a batch is what they return for
+// image p.  Host-side orchestration only.
 #include "fic_internal.h"
-#include "fic_qt_batch_plan.h"
 
 using namespace ficd;
-
-static_assert(kQtPlanSelectWords == FIC_QT_SELECT_WORDS && kQtPlanSelectWords == FIC_QT_SELECT_W_WORDS, "the plan's select areas");
 
 // The levels are contexts of their own (grey: fic_ctx, colour: fic_rgb_ctx with the isometry column); `mem` owns the one device
 // store (QtBatchPlan), the pinned staging buffer and a copy of a host input.
@@ -32,8 +31,6 @@ struct fic_qt_ctx : ficd::CtxCore {
 };
 
 namespace {
-
-enum QtRule { kRuleThreshold, kRuleBudget, kRuleRd };
 
 const char* qt_kind(const fic_qt_ctx* c) { return c->colour ? kQtRgbIsoStream.kind : kQtGreyStream.kind; }
 
@@ -59,14 +56,12 @@ int qt_ctx_begin(fic_qt_ctx* c, const char* who, hipStream_t s, int* slot)
 }
 
 // Everything of an encode behind its checks, enqueued on s: the parameters' upload from staging slot `slot` (`up` says which
-// area it fills), the levels, the SSE, the rule's keys and select, the compaction, the statistics.
+// area it fills) and the levels, then the shared pipeline on their device arrays.
 template <typename Dev>
 int qt_ctx_run(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStream_t s)
 {
     const QtBatchPlan& Q = c->plan;
     const QtLevels& L = c->L;
-    const char* kind = qt_kind(c);
-    const FicGeom& top = L.g[0];
     const size_t P = (size_t)c->planes;
     {
         const char* src = c->staging + (size_t)slot * Q.staging_slot + (up == kQtValues ? Q.staging_values : 0);
@@ -83,67 +78,14 @@ int qt_ctx_run(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStr
     // grey: every level reads the top context's scaled copy, made here for all planes (the original, 2:1 scaled: FC:970-1007)
     if (!c->colour && fic_launch_scale(c->grey[0]->b.gray, c->grey[0]->b.scaled, c->grey[0]->g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
 
-    FicQtPlanes B{};
-    B.planes = c->planes;
-    B.nkeys = Q.nkeys;
-    B.sse_stride = Q.a[kQtSse].stride;
-    B.leaf_stride = Q.a[kQtLeaves].stride;
-    B.n_leaves = c->at<int>(kQtNLeaves);
-    B.param = c->at<uint32_t>(kQtParam);
-    B.ranks = c->at<uint32_t>(kQtRanks);
-    B.values = c->at<long long>(kQtValues);
-    const uint32_t* sse[kQtMaxLevels];
-    const int32_t* qrows[kQtMaxLevels];
-    const int32_t* iso[kQtMaxLevels];
-    int Rw[kQtMaxLevels];
+    QtViews<typename Dev::Px> views[kQtMaxLevels];
     for (int l = 0; l < L.nl; l++) {
-        B.Nr[l] = L.g[l].Nr;
-        Rw[l] = L.g[l].Rw;
-        uint32_t* d_sse = c->at<uint32_t>(kQtSse) + Q.sse_level[l];
-        sse[l] = d_sse;
-        const typename Dev::Px *image, *scaled;
-        if constexpr (sizeof(typename Dev::Px) == 1) {
-            image = c->grey[l]->b.gray;
-            scaled = c->grey[0]->b.scaled;
-            qrows[l] = c->grey[l]->o.qrows;
-            iso[l] = c->n_iso > 1 ? c->grey[l]->o.iso : nullptr;
-        } else {                                    // every level reads its own scaleImageRGB copy, made by its encode
-            image = c->rgb[l]->argb;
-            scaled = c->rgb[l]->scaled;
-            qrows[l] = c->rgb[l]->qrows;
-            iso[l] = c->rgb[l]->iso;                // NULL on n_iso = 1: the identity
-        }
-        if (fic_launch_leaf_sse<Dev>(image, scaled, qrows[l], iso[l], d_sse, L.g[l], s, &B)) return fail(FIC_E_HIP, "k_leaf_sse launch failed");
+        if constexpr (sizeof(typename Dev::Px) == 1)
+            views[l] = {c->grey[l]->b.gray, c->grey[0]->b.scaled, c->grey[l]->o.qrows, c->n_iso > 1 ? c->grey[l]->o.iso : nullptr};
+        else    // every level reads its own scaleImageRGB copy, made by its encode; iso NULL on n_iso = 1: the identity
+            views[l] = {c->rgb[l]->argb, c->rgb[l]->scaled, c->rgb[l]->qrows, c->rgb[l]->iso};
     }
-    uint32_t* d_keys = c->at<uint32_t>(kQtKeys);
-    if (rule == kRuleBudget) {
-        if (fic_launch_qt_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, s, &B) ||
-            fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, 0, c->at<uint32_t>(kQtSelect), s, &B, 1))
-            return fail(FIC_E_HIP, "%s budget select launch failed", kind);
-    } else if (rule == kRuleRd) {
-        long long* d_gains = c->at<long long>(kQtGains);
-        unsigned long long* d_top = c->at<unsigned long long>(kQtTopSum);
-        if (fic_launch_qt_rd_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, d_gains, d_top, s, &B))
-            return fail(FIC_E_HIP, "%s pruning keys launch failed", kind);
-        int bad = 0;
-        if (goal == FIC_QT_RD_LEAVES) bad = fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, 0, c->at<uint32_t>(kQtSelect), s, &B, 0);
-        else if (goal == FIC_QT_RD_SSE) bad = fic_launch_qt_select_w(d_keys, d_gains, (uint32_t)Q.nkeys, d_top, 0, c->at<unsigned long long>(kQtSelect), s, &B);
-        if (bad) return fail(FIC_E_HIP, "%s pruning select launch failed", kind);
-    }
-    int *d_cnt = c->at<int>(kQtCounts), *d_offs = c->at<int>(kQtOffs);
-    int32_t* d_leaves = c->at<int32_t>(kQtLeaves);
-    unsigned long long* d_stats = c->at<unsigned long long>(kQtStats);
-    if (rule == kRuleRd) {
-        if (fic_launch_qt_compact_rd<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_cnt, d_offs, d_leaves, s, &B))
-            return fail(FIC_E_HIP, "%s compaction launch failed", kind);
-        if (fic_launch_qt_tree_stats_rd(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_stats, s, &B))
-            return fail(FIC_E_HIP, "%s tree statistics launch failed", kind);
-    } else {
-        if (fic_launch_qt_compact<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, 0.0f, d_cnt, d_offs, d_leaves, s, &B))
-            return fail(FIC_E_HIP, "%s compaction launch failed", kind);
-        if (fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, 0.0f, d_stats, s, &B))
-            return fail(FIC_E_HIP, "%s tree statistics launch failed", kind);
-    }
+    if (int rc = qt_tree_run<Dev>(qt_kind(c), Q, c->store, L, views, rule, goal, true, s)) return rc;
     c->encoded_any = true;
     return FIC_OK;
 }
@@ -151,13 +93,6 @@ int qt_ctx_run(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStr
 int qt_ctx_run_any(fic_qt_ctx* c, QtRule rule, int goal, QtArea up, int slot, hipStream_t s)
 {
     return c->colour ? qt_ctx_run<QtRgbIso>(c, rule, goal, up, slot, s) : qt_ctx_run<QtGrey>(c, rule, goal, up, slot, s);
-}
-
-// the rank of the select for a budget of M leaves: S = (M - Ntop) / 3 blocks may split, the block of rank S must not
-uint32_t qt_rank(uint64_t M, const QtBatchPlan& Q)
-{
-    const uint64_t S = (M - (uint64_t)Q.Ntop) / 3;
-    return (uint32_t)(S < (uint64_t)Q.nkeys ? S : (uint64_t)Q.nkeys);
 }
 
 void qt_ctx_free(fic_qt_ctx* c)

@@ -1,22 +1,85 @@
-// fic_capi_quadtree.cpp -- C ABI, quadtree (variable block size) codec, grey and joint RGB: encode every level with the
-// one-shot machinery, collage SSE + split + compaction on the device (fic_quadtree.hip), and the decoders of leaves of mixed
-// size on the decode job (fic_internal.h).  The tag-2 (grey), tag-3 (colour) and tag-6 (colour with an isometry column) stream
-// writers and parsers are in fic_stream.cpp.  Host-side orchestration only.  Semantics: DESIGN.md sections 4.13 (grey), 4.14
-// (colour), 4.17 (colour with the 8 isometries) and 4.18 (encode to a leaf budget).
+// fic_capi_quadtree.cpp -- C ABI, quadtree (variable block size) codec, grey and joint RGB.  The encode is one pipeline with two
+// front ends: qt_tree_run below -- collage SSE, the split rule's keys and select, compaction and statistics on the device
+// (fic_quadtree.hip), every area where the plan of fic_qt_batch_plan.h puts it, every parameter read from device memory -- runs
+// behind the level encodes of the one-shot entries here (qt_encode: idle-cached one-shot contexts, a plan of one plane, the null
+// stream, results copied back at the end) and of the batched handle (fic_capi_qt_ctx.cpp).  Also here: the decoders of leaves of
+// mixed size on the decode job (fic_internal.h).  The tag-2 (grey), tag-3 (colour) and tag-6 (colour with an isometry column)
+// stream writers and parsers are in fic_stream.cpp.  Host-side orchestration only.  Semantics: DESIGN.md sections 4.13 (grey),
+// 4.14 (colour), 4.17 (colour with the 8 isometries), 4.18 (encode to a leaf budget), 4.23 (pruning) and 4.24 (the pipeline).
 #include "fic_internal.h"
 
 using namespace ficd;
+
+static_assert(kQtPlanSelectWords == FIC_QT_SELECT_WORDS && kQtPlanSelectWords == FIC_QT_SELECT_W_WORDS, "the plan's select areas");
+
+namespace ficd {
+
+template <typename Dev>
+int qt_tree_run(const char* kind, const QtBatchPlan& Q, char* store, const QtLevels& L, const QtViews<typename Dev::Px>* views, QtRule rule,
+                int goal, bool stats, hipStream_t s)
+{
+    auto at = [&](QtArea a) { return (void*)(store + Q.a[a].off); };
+    const FicGeom& top = L.g[0];
+    FicQtPlanes B{};
+    B.planes = Q.planes;
+    B.nkeys = Q.nkeys;
+    B.sse_stride = Q.a[kQtSse].stride;
+    B.leaf_stride = Q.a[kQtLeaves].stride;
+    B.n_leaves = (int*)at(kQtNLeaves);
+    B.param = (uint32_t*)at(kQtParam);
+    B.ranks = (const uint32_t*)at(kQtRanks);
+    B.values = (const long long*)at(kQtValues);
+    const uint32_t* sse[kQtMaxLevels];
+    const int32_t* qrows[kQtMaxLevels];
+    const int32_t* iso[kQtMaxLevels];
+    int Rw[kQtMaxLevels];
+    for (int l = 0; l < L.nl; l++) {
+        const auto& v = views[l];
+        uint32_t* d_sse = (uint32_t*)at(kQtSse) + Q.sse_level[l];
+        B.Nr[l] = L.g[l].Nr;
+        Rw[l] = L.g[l].Rw;
+        sse[l] = d_sse;
+        qrows[l] = v.qrows;
+        iso[l] = v.iso;
+        if (fic_launch_leaf_sse<Dev>(v.image, v.scaled, v.qrows, v.iso, d_sse, L.g[l], s, B)) return fail(FIC_E_HIP, "k_leaf_sse launch failed");
+    }
+    uint32_t* d_keys = (uint32_t*)at(kQtKeys);
+    if (rule == kRuleBudget) {            // the threshold's bits to param
+        if (fic_launch_qt_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, s, B) ||
+            fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, (uint32_t*)at(kQtSelect), s, B, 1))
+            return fail(FIC_E_HIP, "%s budget select launch failed", kind);
+    } else if (rule == kRuleRd) {         // lambda to param, unless it is there already (FIC_QT_RD_LAMBDA)
+        long long* d_gains = (long long*)at(kQtGains);
+        unsigned long long* d_top = (unsigned long long*)at(kQtTopSum);
+        if (fic_launch_qt_rd_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, Q.n1, d_keys, d_gains, d_top, s, B))
+            return fail(FIC_E_HIP, "%s pruning keys launch failed", kind);
+        int bad = 0;
+        if (goal == FIC_QT_RD_LEAVES) bad = fic_launch_qt_select(d_keys, (uint32_t)Q.nkeys, (uint32_t*)at(kQtSelect), s, B, 0);
+        else if (goal == FIC_QT_RD_SSE) bad = fic_launch_qt_select_w(d_keys, d_gains, (uint32_t)Q.nkeys, d_top, (unsigned long long*)at(kQtSelect), s, B);
+        if (bad) return fail(FIC_E_HIP, "%s pruning select launch failed", kind);
+    }
+    int *d_cnt = (int*)at(kQtCounts), *d_offs = (int*)at(kQtOffs);
+    int32_t* d_leaves = (int32_t*)at(kQtLeaves);
+    unsigned long long* d_stats = (unsigned long long*)at(kQtStats);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stats4");
+    if (rule == kRuleRd ? fic_launch_qt_compact_rd<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_cnt, d_offs, d_leaves, s, B)
+                        : fic_launch_qt_compact<Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_cnt, d_offs, d_leaves, s, B))
+        return fail(FIC_E_HIP, "%s compaction launch failed", kind);
+    if (stats && (rule == kRuleRd ? fic_launch_qt_tree_stats_rd(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, B.param, d_stats, s, B)
+                                  : fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_stats, s, B)))
+        return fail(FIC_E_HIP, "%s tree statistics launch failed", kind);
+    return FIC_OK;
+}
+template int qt_tree_run<QtGrey>(const char*, const QtBatchPlan&, char*, const QtLevels&, const QtViews<uint8_t>*, QtRule, int, bool, hipStream_t);
+template int qt_tree_run<QtRgb>(const char*, const QtBatchPlan&, char*, const QtLevels&, const QtViews<int32_t>*, QtRule, int, bool, hipStream_t);
+template int qt_tree_run<QtRgbIso>(const char*, const QtBatchPlan&, char*, const QtLevels&, const QtViews<int32_t>*, QtRule, int, bool, hipStream_t);
+
+}  // namespace ficd
 
 namespace {
 
 // ---- the host side of a pixel format (QtGrey / QtRgb / QtRgbIso, fic_launch.h) --------------------------------------------
 // The one-shot contexts an encode runs its levels through, their device buffers and the stream format (fic_stream.h).
-template <typename Px>
-struct QtViews {
-    const Px *image, *scaled;         // the input [H][W] and the 2:1 copy [Hs][Ws] the rows refer to
-    const int32_t *qrows, *iso;
-};
-
 struct QtGreyHost : QtGrey {
     using Dev = QtGrey;               // the tag of the launchers
     using Ctx = fic_ctx;
@@ -131,127 +194,81 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     if (rd && rd->goal == FIC_QT_RD_LEAVES && rd->value < (uint64_t)L.g[0].Nr)
         return fail(FIC_E_ARGUMENT, "%s encode: max_leaves = %llu, the image has %d blocks of side %d", Fmt::kStream.kind,
                     (unsigned long long)rd->value, L.g[0].Nr, B_max);
-    size_t sse_total = 0;
-    for (int l = 0; l < L.nl; l++) sse_total += (size_t)L.g[l].Nr;
+    int Nr[kQtMaxLevels] = {0, 0, 0};
+    for (int l = 0; l < L.nl; l++) Nr[l] = L.g[l].Nr;
+    QtBatchPlan Q;                   // one plane: takes every image qt_levels takes (tests/cpp/qt_oneshot_plan_test.cpp)
+    const char* why = "";
+    if (qt_batch_plan(1, L.nl, Nr, Fmt::kLeafInts, &Q, &why))
+        return fail(FIC_E_GEOMETRY, "%s encode: %dx%d, %d -> %d: %s would pass 2^31 - 1", Fmt::kStream.kind, w, h, B_max, B_min, why);
+    const size_t sse_total = Q.a[kQtSse].stride;
     if (sse_out && sse_capacity < (int64_t)sse_total)
         return fail(FIC_E_CAPACITY, "%s SSE: need %zu values, have %lld", Fmt::kStream.kind, sse_total, (long long)sse_capacity);
     rc = check_device(device);
     if (rc) return rc;
 
     typename Fmt::Ctx* c[kQtMaxLevels] = {nullptr, nullptr, nullptr};
-    DevMem mem(device);              // the scratch of this call: freed on every way out
-    char* scratch = nullptr;
+    DevMem mem(device);              // the store of this call: freed on every way out
+    char* store = nullptr;
     for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
         c[l] = Fmt::take(device, L.g[l]);
         if (!c[l]) { rc = g_err_code ? g_err_code : FIC_E_HIP; break; }
         rc = Fmt::encode(c[l], gray, argb, search);
     }
-    // scratch: SSE per level, counts / offsets per top-level block, the leaf table (room for every block of B_min)
-    const FicGeom& top = L.g[0];
-    const size_t max_leaves = (size_t)L.g[L.nl - 1].Nr;
-    size_t o_sse[kQtMaxLevels], off = 0;
-    for (int l = 0; l < L.nl; l++) { o_sse[l] = off; off += align256((size_t)L.g[l].Nr * 4); }
-    const size_t o_cnt = off, o_offs = o_cnt + align256((size_t)top.Nr * 4), o_leaves = o_offs + align256(((size_t)top.Nr + 1) * 4);
-    // a budget: the split keys of every block above B_min, the select's histograms and result, the tree's statistics
-    const int n1 = L.nl == 3 ? L.g[1].Nr : 0, nkeys = top.Nr + n1;
-    // pruning: the same and the gains G_v; the statistics' 256 bytes also hold the top-level SSE sum (+64) and a given lambda (+128)
-    static_assert(FIC_QT_SELECT_W_WORDS * 8 >= FIC_QT_SELECT_WORDS * 4, "one select area for both selects");
-    const size_t o_keys = o_leaves + align256(max_leaves * Fmt::kLeafInts * 4), o_gains = o_keys + (budget || rd ? align256((size_t)nkeys * 4) : 0),
-                 o_sel = o_gains + (rd ? align256((size_t)nkeys * 8) : 0),
-                 o_stats = o_sel + (rd ? align256(FIC_QT_SELECT_W_WORDS * 8) : (budget ? align256(FIC_QT_SELECT_WORDS * 4) : 0)),
-                 total = o_stats + (budget || rd ? 256 : 0);
-    if (rc == FIC_OK) rc = mem.alloc(scratch, total);
+    if (rc == FIC_OK) rc = mem.alloc(store, Q.total);
     if (rc == FIC_OK && Fmt::prepare(c[0])) rc = fail(FIC_E_HIP, "k_scale launch failed");
-    const uint32_t* sse[kQtMaxLevels];
-    const int32_t* qrows[kQtMaxLevels];
-    const int32_t* iso[kQtMaxLevels];
-    int Rw[kQtMaxLevels];
-    for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
-        const auto v = Fmt::views(c[l], c[0]);
-        sse[l] = (const uint32_t*)(scratch + o_sse[l]);
-        qrows[l] = v.qrows;
-        iso[l] = v.iso;
-        Rw[l] = L.g[l].Rw;
-        if (fic_launch_leaf_sse<typename Fmt::Dev>(v.image, v.scaled, v.qrows, v.iso, (uint32_t*)(scratch + o_sse[l]), L.g[l], nullptr))
-            rc = fail(FIC_E_HIP, "k_leaf_sse launch failed");
+    // the rule's parameter into the store, where the kernels read it: the threshold's bits or a given lambda, the rank of a leaf
+    // budget, or the summed gain an SSE target asks for (sum S_top - max_sse; the sum is the device's)
+    QtArea up = kQtParam;
+    uint64_t word = 0;
+    if (budget || (rd && rd->goal == FIC_QT_RD_LEAVES)) {
+        up = kQtRanks;
+        word = qt_rank(budget ? (uint64_t)budget->max_leaves : rd->value, Q);
+    } else if (rd && rd->goal == FIC_QT_RD_SSE) {
+        up = kQtValues;
+        word = rd->value < (uint64_t)INT64_MAX ? rd->value : (uint64_t)INT64_MAX;
+    } else if (rd) {
+        word = (uint32_t)rd->value;
+    } else {
+        uint32_t bits;
+        memcpy(&bits, &threshold, sizeof(bits));
+        word = bits;
     }
-    if (rc == FIC_OK && budget) {
-        // rank S = (M - Ntop) / 3 in descending order: the S blocks of larger key may split, the block of rank S must not
-        const int64_t S = (budget->max_leaves - top.Nr) / 3;
-        uint32_t* d_sel = (uint32_t*)(scratch + o_sel);
-        if (fic_launch_qt_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, n1, (uint32_t*)(scratch + o_keys), nullptr) ||
-            fic_launch_qt_select((const uint32_t*)(scratch + o_keys), (uint32_t)nkeys, (uint32_t)(S < nkeys ? S : nkeys), d_sel, nullptr))
-            rc = fail(FIC_E_HIP, "%s budget select launch failed", Fmt::kStream.kind);
-        if (rc == FIC_OK) {     // by value into the compaction, like n below; the caller gets it anyway
-            hipError_t e = hipMemcpy(&threshold, d_sel + 4 * 256 + 1, sizeof(float), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
-            else *budget->threshold_out = threshold;
-        }
-    }
-    const uint32_t *d_keys = (const uint32_t*)(scratch + o_keys), *d_lambda = nullptr;
-    if (rc == FIC_OK && rd) {
-        unsigned long long* d_top = (unsigned long long*)(scratch + o_stats + 64);
-        if (fic_launch_qt_rd_keys(sse, Rw, L.nl, top.B, top.Rw, top.Nr, n1, (uint32_t*)(scratch + o_keys), (long long*)(scratch + o_gains), d_top, nullptr))
-            rc = fail(FIC_E_HIP, "%s pruning keys launch failed", Fmt::kStream.kind);
-        uint32_t lambda = (uint32_t)rd->value;
-        if (rc == FIC_OK && rd->goal == FIC_QT_RD_LAMBDA) {
-            d_lambda = (const uint32_t*)(scratch + o_stats + 128);
-            hipError_t e = hipMemsetD32Async((hipDeviceptr_t)(scratch + o_stats + 128), (int)lambda, 1, nullptr);
-            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
-        } else if (rc == FIC_OK) {
-            int bad;
-            if (rd->goal == FIC_QT_RD_LEAVES) {       // the select of 4.18 on the new keys, rank S = (M - Ntop) / 3
-                const uint64_t S = (rd->value - (uint64_t)top.Nr) / 3;
-                uint32_t* d_sel = (uint32_t*)(scratch + o_sel);
-                bad = fic_launch_qt_select(d_keys, (uint32_t)nkeys, (uint32_t)(S < (uint64_t)nkeys ? S : (uint64_t)nkeys), d_sel, nullptr);
-                d_lambda = d_sel + 4 * 256;
-            } else {                                  // the summed gain has to reach sum S_top - max_sse
-                unsigned long long* d_sel = (unsigned long long*)(scratch + o_sel);
-                const uint64_t cap = (uint64_t)INT64_MAX;
-                bad = fic_launch_qt_select_w(d_keys, (const long long*)(scratch + o_gains), (uint32_t)nkeys, d_top,
-                                             (long long)(rd->value < cap ? rd->value : cap), d_sel, nullptr);
-                d_lambda = (const uint32_t*)(d_sel + 4 * 256);
-            }
-            if (bad) rc = fail(FIC_E_HIP, "%s pruning select launch failed", Fmt::kStream.kind);
-            if (rc == FIC_OK) {     // the caller's copy; the walkers read it where it is
-                hipError_t e = hipMemcpy(&lambda, d_lambda, sizeof(uint32_t), hipMemcpyDeviceToHost);
-                if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
-            }
-        }
-        if (rc == FIC_OK) *rd->lambda_out = lambda;
-    }
-    int* d_offs = (int*)(scratch + o_offs);
-    if (rc == FIC_OK && (rd ? fic_launch_qt_compact_rd<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, d_lambda,
-                                                                          (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr)
-                            : fic_launch_qt_compact<typename Fmt::Dev>(sse, qrows, iso, Rw, L.nl, top.B, top.Rw, top.Nr, threshold,
-                                                                       (int*)(scratch + o_cnt), d_offs, (int32_t*)(scratch + o_leaves), nullptr)))
-        rc = fail(FIC_E_HIP, "%s compaction launch failed", Fmt::kStream.kind);
-    int n = 0;
-    if (rc == FIC_OK) {
-        hipError_t e = hipMemcpy(&n, d_offs + top.Nr, sizeof(int), hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < Q.a[up].elem / 4 && rc == FIC_OK; i++) {
+        hipError_t e = hipMemsetD32Async((hipDeviceptr_t)(store + Q.a[up].off + 4 * i), (int)(uint32_t)(word >> (32 * i)), 1, nullptr);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
-    if (rc == FIC_OK && n_leaves) *n_leaves = n;
     uint64_t* stats4 = budget ? budget->stats4 : (rd ? rd->stats4 : nullptr);
-    if (rc == FIC_OK && stats4) {
-        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stats4");
-        if (rd ? fic_launch_qt_tree_stats_rd(sse, Rw, L.nl, top.B, top.Rw, top.Nr, d_keys, d_lambda, (unsigned long long*)(scratch + o_stats), nullptr)
-               : fic_launch_qt_tree_stats(sse, Rw, L.nl, top.B, top.Rw, top.Nr, threshold, (unsigned long long*)(scratch + o_stats), nullptr))
-            rc = fail(FIC_E_HIP, "%s tree statistics launch failed", Fmt::kStream.kind);
+    if (rc == FIC_OK) {
+        QtViews<typename Fmt::Px> views[kQtMaxLevels];
+        for (int l = 0; l < L.nl; l++) views[l] = Fmt::views(c[l], c[0]);
+        rc = qt_tree_run<typename Fmt::Dev>(Fmt::kStream.kind, Q, store, L, views, rd ? kRuleRd : (budget ? kRuleBudget : kRuleThreshold), rd ? rd->goal : 0,
+                                            stats4 != nullptr, nullptr);
+    }
+    // Everything is enqueued; what the caller asked for comes back now.  n_leaves, param and stats are neighbours in the store.
+    int n = 0;
+    if (rc == FIC_OK) {
+        const size_t first = Q.a[kQtNLeaves].off;
+        std::vector<char> res(Q.a[kQtStats].off + 4 * sizeof(uint64_t) - first);
+        const char *param = res.data() + (Q.a[kQtParam].off - first), *stats = res.data() + (Q.a[kQtStats].off - first);
+        hipError_t e = hipMemcpy(res.data(), store + first, res.size(), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
         else {
-            hipError_t e = hipMemcpy(stats4, scratch + o_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
+            memcpy(&n, res.data(), sizeof(n));
+            if (n_leaves) *n_leaves = n;
+            if (budget) memcpy(budget->threshold_out, param, sizeof(float));
+            if (rd) memcpy(rd->lambda_out, param, sizeof(uint32_t));
+            if (stats4) memcpy(stats4, stats, 4 * sizeof(uint64_t));
         }
     }
     if (rc == FIC_OK && leaves) {
         if (capacity < n) rc = fail(FIC_E_CAPACITY, "%s encode: %d leaves, room for %lld", Fmt::kStream.kind, n, (long long)capacity);
         else {
-            hipError_t e = hipMemcpy(leaves, scratch + o_leaves, (size_t)n * Fmt::kLeafInts * 4, hipMemcpyDeviceToHost);
+            hipError_t e = hipMemcpy(leaves, store + Q.a[kQtLeaves].off, (size_t)n * Fmt::kLeafInts * 4, hipMemcpyDeviceToHost);
             if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s encode: %s", Fmt::kStream.kind, hipGetErrorString(e));
         }
     }
-    for (int l = 0, o = 0; rc == FIC_OK && sse_out && l < L.nl; o += L.g[l].Nr, l++) {
-        hipError_t e = hipMemcpy(sse_out + o, scratch + o_sse[l], (size_t)L.g[l].Nr * 4, hipMemcpyDeviceToHost);
+    if (rc == FIC_OK && sse_out) {   // the levels of a plane lie one behind the other, as the caller gets them
+        hipError_t e = hipMemcpy(sse_out, store + Q.a[kQtSse].off, sse_total * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s SSE: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
     ErrKeep keep;
@@ -350,14 +367,22 @@ int fic_debug_qt_select(int device, const uint32_t* keys, int64_t n, int64_t ran
     if (rc) return rc;
     DevMem mem(device);
     char* scratch = nullptr;
-    const size_t o_sel = align256((size_t)n * 4);
-    rc = mem.alloc(scratch, o_sel + FIC_QT_SELECT_WORDS * 4);
+    // the keys, the select's area, then the one plane's rank and parameter word
+    const size_t keys_bytes = align256((size_t)n * 4);
+    rc = mem.alloc(scratch, keys_bytes + (FIC_QT_SELECT_WORDS + 2) * 4);
     if (rc) return rc;
+    uint32_t *d_work = (uint32_t*)(scratch + keys_bytes), *d_rank = d_work + FIC_QT_SELECT_WORDS;
+    FicQtPlanes P{};
+    P.planes = 1;
+    P.ranks = d_rank;
+    P.param = d_rank + 1;
+    const uint32_t r = (uint32_t)(rank < n ? rank : n);
     uint32_t res[4] = {0, 0, 0, 0};
     hipError_t e = hipMemcpy(scratch, keys, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && fic_launch_qt_select((const uint32_t*)scratch, (uint32_t)n, (uint32_t)(rank < n ? rank : n), (uint32_t*)(scratch + o_sel), nullptr))
+    if (e == hipSuccess) e = hipMemcpy(d_rank, &r, sizeof(r), hipMemcpyHostToDevice);
+    if (e == hipSuccess && fic_launch_qt_select((const uint32_t*)scratch, (uint32_t)n, d_work, nullptr, P, 1))
         return fail(FIC_E_HIP, "fic_debug_qt_select: launch failed");
-    if (e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 4, sizeof(res), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(res, d_work + 4 * 256, sizeof(res), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_qt_select: %s", hipGetErrorString(e));
     *key_out = res[0];
     memcpy(threshold_out, &res[1], sizeof(float));
@@ -528,24 +553,30 @@ int fic_debug_qt_rd_keys(int device, const uint32_t* sse, int w, int h, int B_ma
     int rc = check_device(device);
     if (rc) return rc;
     int nl = 0, Rw[kQtMaxLevels], Nr[kQtMaxLevels];
-    size_t o_sse[kQtMaxLevels], off = 0;
+    size_t sum = 0;                     // the SSE of all levels, concatenated like the caller's: one copy
     for (int B = B_max; B >= B_min; B /= 2, nl++) {
         Rw[nl] = w / B;
         Nr[nl] = (w / B) * (h / B);
-        o_sse[nl] = off;
-        off += (size_t)Nr[nl] * 4;      // concatenated, like the caller's: one copy
+        sum += (size_t)Nr[nl];
     }
     const int n1 = nl == 3 ? Nr[1] : 0, nkeys = Nr[0] + n1;
-    const size_t o_keys = align256(off), o_gains = o_keys + align256((size_t)nkeys * 4), o_top = o_gains + align256((size_t)nkeys * 8);
+    const size_t o_keys = align256(sum * 4), o_gains = o_keys + align256((size_t)nkeys * 4), o_top = o_gains + align256((size_t)nkeys * 8);
     DevMem mem(device);
     char* scratch = nullptr;
     rc = mem.alloc(scratch, o_top + 256);
     if (rc) return rc;
     const uint32_t* lv[kQtMaxLevels] = {nullptr, nullptr, nullptr};
-    for (int l = 0; l < nl; l++) lv[l] = (const uint32_t*)(scratch + o_sse[l]);
-    hipError_t e = hipMemcpy(scratch, sse, off, hipMemcpyHostToDevice);
+    FicQtPlanes P{};                    // one plane of these levels; the key kernel takes no parameter
+    P.planes = 1;
+    P.nkeys = nkeys;
+    P.sse_stride = sum;
+    for (int l = 0; l < nl; l++) {
+        lv[l] = l ? lv[l - 1] + Nr[l - 1] : (const uint32_t*)scratch;
+        P.Nr[l] = Nr[l];
+    }
+    hipError_t e = hipMemcpy(scratch, sse, sum * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && fic_launch_qt_rd_keys(lv, Rw, nl, B_max, Rw[0], Nr[0], n1, (uint32_t*)(scratch + o_keys), (long long*)(scratch + o_gains),
-                                                 (unsigned long long*)(scratch + o_top), nullptr))
+                                                 (unsigned long long*)(scratch + o_top), nullptr, P))
         return fail(FIC_E_HIP, "fic_debug_qt_rd_keys: launch failed");
     if (e == hipSuccess) e = hipMemcpy(keys, scratch + o_keys, (size_t)nkeys * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(gains, scratch + o_gains, (size_t)nkeys * 8, hipMemcpyDeviceToHost);
@@ -564,16 +595,23 @@ int fic_debug_qt_select_weighted(int device, const uint32_t* keys, const int64_t
     static_assert(sizeof(long long) == sizeof(int64_t), "gains");
     DevMem mem(device);
     char* scratch = nullptr;
-    const size_t o_gains = align256((size_t)n * 4), o_sel = o_gains + align256((size_t)n * 8);
-    rc = mem.alloc(scratch, o_sel + FIC_QT_SELECT_W_WORDS * 8);
+    // the keys, the gains, the select's area, then the one plane's {total, value} = {need, 0} and its parameter word
+    const size_t o_gains = align256((size_t)n * 4), o_work = o_gains + align256((size_t)n * 8);
+    rc = mem.alloc(scratch, o_work + (FIC_QT_SELECT_W_WORDS + 3) * 8);
     if (rc) return rc;
+    unsigned long long *d_work = (unsigned long long*)(scratch + o_work), *d_need = d_work + FIC_QT_SELECT_W_WORDS;
+    FicQtPlanes P{};
+    P.planes = 1;
+    P.values = (const long long*)d_need + 1;
+    P.param = (uint32_t*)(d_need + 2);
+    const int64_t tv[2] = {need, 0};
     uint64_t res[4] = {0, 0, 0, 0};
     hipError_t e = hipMemcpy(scratch, keys, (size_t)n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(scratch + o_gains, gains, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && fic_launch_qt_select_w((const uint32_t*)scratch, (const long long*)(scratch + o_gains), (uint32_t)n, nullptr,
-                                                  (long long)need, (unsigned long long*)(scratch + o_sel), nullptr))
+    if (e == hipSuccess) e = hipMemcpy(d_need, tv, sizeof(tv), hipMemcpyHostToDevice);
+    if (e == hipSuccess && fic_launch_qt_select_w((const uint32_t*)scratch, (const long long*)(scratch + o_gains), (uint32_t)n, d_need, d_work, nullptr, P))
         return fail(FIC_E_HIP, "fic_debug_qt_select_weighted: launch failed");
-    if (e == hipSuccess) e = hipMemcpy(res, scratch + o_sel + 4 * 256 * 8, sizeof(res), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(res, d_work + 4 * 256, sizeof(res), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(FIC_E_HIP, "fic_debug_qt_select_weighted: %s", hipGetErrorString(e));
     *key_out = (uint32_t)res[0];
     *above_out = (int64_t)res[1];

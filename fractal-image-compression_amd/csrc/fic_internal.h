@@ -20,6 +20,7 @@
 #include "fic_launch.h"
 #include "fic_stream.h"
 #include "fic_devmem.h"
+#include "fic_qt_batch_plan.h"
 
 struct fic_rgb_ctx;
 
@@ -141,6 +142,28 @@ struct DecodeJob {
 // The encode of a colour context under "search" = 1 (fic_capi_rgb_lsq.cpp); the caller holds the context's lock, has made its
 // device current and taken the stream (take_stream)
 int rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s);
+
+// The quadtree encode behind the level encodes (fic_capi_quadtree.cpp), one pipeline for the one-shot entries
+// (a plan of one plane) and the batched handle: the per-level SSE, the rule's keys and select, the compaction and, if asked
+// for, the tree statistics, all enqueued on s.  Every area lies in `store` where the plan Q says, and every parameter of the
+// rule is read there by the kernels: the threshold's bits or a given lambda in kQtParam, the rank of a leaf budget (qt_rank) in
+// kQtRanks, an SSE target in kQtValues; the caller has put it there on s.  Results: kQtLeaves, kQtNLeaves, kQtParam, kQtStats.
+// views [L.nl]: the device arrays of every level's encode, whoever made them.  goal: FIC_QT_RD_* under kRuleRd.
+enum QtRule { kRuleThreshold, kRuleBudget, kRuleRd };
+template <typename Px>
+struct QtViews {
+    const Px *image, *scaled;         // the input [planes][H][W] and the 2:1 copy [planes][Hs][Ws] the rows refer to
+    const int32_t *qrows, *iso;
+};
+template <typename Dev>
+int qt_tree_run(const char* kind, const QtBatchPlan& Q, char* store, const QtLevels& L, const QtViews<typename Dev::Px>* views, QtRule rule,
+                int goal, bool stats, hipStream_t s);
+// the rank of the select for a budget of M >= Ntop leaves: S = (M - Ntop) / 3 blocks may split, the block of rank S must not
+inline uint32_t qt_rank(uint64_t M, const QtBatchPlan& Q)
+{
+    const uint64_t S = (M - (uint64_t)Q.Ntop) / 3;
+    return (uint32_t)(S < (uint64_t)Q.nkeys ? S : (uint64_t)Q.nkeys);
+}
 
 // what fic_release_cache() frees besides the idle contexts
 void release_decoder_arenas();     // fic_capi_decode.cpp

@@ -314,12 +314,12 @@ struct QtRgbIso {
     static constexpr bool kIso = true;
     static constexpr int kLeafInts = 3 + QW + 1;
 };
-// A batch of planes behind the launchers below (NULL: one plane, the one-shot entries).  The plane is a grid
-// dimension of every kernel and no workgroup spans two planes.  Every array gets the plane as its slowest index: image [planes]
-// [H][W], scaled [planes][Hs][Ws], qrows [planes][Nr_l][QW], iso [planes][Nr_l], keys / gains [planes][nkeys], top_sum [planes],
-// counts [planes][Ntop], offs [planes][Ntop + 1], stats [planes][4], the select areas [planes][FIC_QT_SELECT(_W)_WORDS]; the SSE
-// of level l starts at the pointer given for it and plane p's sse_stride u32 further; the leaves of plane p leaf_stride ints
-// behind those of plane 0.  The rules' parameters are read from device memory: the threshold of plane p is the float in
+// The batch of planes behind the launchers below (the one-shot entries run the batch of one plane).  The plane is
+// a grid dimension of every kernel and no workgroup spans two planes.  Every array gets the plane as its slowest index: image
+// [planes][H][W], scaled [planes][Hs][Ws], qrows [planes][Nr_l][QW], iso [planes][Nr_l], keys / gains [planes][nkeys], top_sum
+// [planes], counts [planes][Ntop], offs [planes][Ntop + 1], stats [planes][4], the select areas [planes][FIC_QT_SELECT(_W)_WORDS];
+// the SSE of level l starts at the pointer given for it and plane p's sse_stride u32 further; the leaves of plane p leaf_stride
+// ints behind those of plane 0.  The rules' parameters are read from device memory: the threshold of plane p is the float in
 // param[p], lambda is param[p] (the pointer handed to the _rd launchers), the selects take ranks[p] / values[p] and leave
 // their result in param[p] as well.
 struct FicQtPlanes {
@@ -333,49 +333,49 @@ struct FicQtPlanes {
     const uint32_t* ranks;   // [planes]: fic_launch_qt_select
     const long long* values; // [planes]: fic_launch_qt_select_w
 };
-// sse u32 [g.Nr]: collage SSE (colour: over the three channels) of every range block of one level from its quantised rows
-// [N_r][Fmt::QW]; image the original [H][W], scaled its 2:1 copy [Hs][Ws] (k_scale / scaleImageRGB); iso: formats with kIso only
+// sse u32 [g.Nr] per plane: collage SSE (colour: over the three channels) of every range block of one level from its quantised
+// rows [N_r][Fmt::QW]; image the original [H][W], scaled its 2:1 copy [Hs][Ws] (k_scale / scaleImageRGB); iso: formats with kIso only
 template <typename Fmt>
 int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* scaled, const int32_t* qrows, const int32_t* iso,
-                        uint32_t* sse, const FicGeom& g, hipStream_t s, const FicQtPlanes* P = nullptr);
-// split + compaction over nl levels (B_max >> l): counts int [Ntop], offs int [Ntop + 1] (offs[Ntop] = leaves), leaves int32
-// [leaves][Fmt::kLeafInts] (NULL: count only); room for the largest possible count is the caller's.  iso: formats with kIso only
+                        uint32_t* sse, const FicGeom& g, hipStream_t s, const FicQtPlanes& P);
+// split + compaction over nl levels (B_max >> l) under the thresholds in P.param: counts int [Ntop], offs int [Ntop + 1]
+// (offs[Ntop] = leaves), leaves int32 [leaves][Fmt::kLeafInts] (NULL: count only); room for the largest possible count is the
+// caller's.  iso: formats with kIso only
 template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
-                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s, const FicQtPlanes* P = nullptr);
+                          int nl, int B_max, int Rw_top, int Ntop, int* counts, int* offs, int32_t* leaves, hipStream_t s,
+                          const FicQtPlanes& P);
 // Encode to a leaf budget, on the same per-level SSE arrays.  keys u32 [Ntop + n1]: the split key e(v) of every
 // block above B_min, level 0 first; n1 = N_r of level 1 with three levels, else 0.
 int fic_launch_qt_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                       hipStream_t s, const FicQtPlanes* P = nullptr);
+                       hipStream_t s, const FicQtPlanes& P);
 // Radix select over n < 2^31 keys: work u32 [FIC_QT_SELECT_WORDS] = four 256-bin histograms, then {K, bits of the threshold,
-// #{keys > K}, 0}, K the key of rank `rank` <= n in descending order (0 past the last key), the threshold the smallest float >= K / 256
+// #{keys > K}, 0}, K the key of rank P.ranks[p] <= n in descending order (0 past the last key), the threshold the smallest float
+// >= K / 256; P.param[p] = word `param_word` of plane p's result (0: K, 1: the threshold's bits)
 constexpr int FIC_QT_SELECT_WORDS = 4 * 256 + 4;
-// A batch: param[p] = word `param_word` of plane p's result (0: K, 1: the threshold's bits)
-int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s, const FicQtPlanes* P = nullptr,
-                         int param_word = 1);
-// stats u64 [4] = {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4} of the tree under `threshold`
-int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
-                             unsigned long long* stats, hipStream_t s, const FicQtPlanes* P = nullptr);
+int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t* work, hipStream_t s, const FicQtPlanes& P, int param_word);
+// stats u64 [4] = {collage SSE of the leaves, leaves of side B_max, B_max / 2, B_max / 4} of the tree under the thresholds in P.param
+int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop,
+                             unsigned long long* stats, hipStream_t s, const FicQtPlanes& P);
 // Encode by rate-distortion pruning, on the same per-level SSE arrays.  keys u32 / gains i64 [Ntop + n1]: e(v)
 // and G_v of every block above B_min in the order of fic_launch_qt_keys; *top_sum = the sum of the SSE of the top-level blocks.
 int fic_launch_qt_rd_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                          long long* gains, unsigned long long* top_sum, hipStream_t s, const FicQtPlanes* P = nullptr);
+                          long long* gains, unsigned long long* top_sum, hipStream_t s, const FicQtPlanes& P);
 // Weighted radix select over n < 2^31 (key, gain) pairs: work u64 [FIC_QT_SELECT_W_WORDS] = four 256-bin gain sums, then {b in the
 // low 32 bits, #{keys > b}, their summed gain, 0}: b the largest of the keys and 0 with sum_{key > b} gain >= need, 0 when there is
-// none; need = *total - value (total a device pointer), or value when total is NULL.  The cumulated gain over descending distinct
-// keys must not fall.
+// none, and P.param[p] = b; need = (int64) total[p] - P.values[p], both on the device.  The cumulated gain over descending
+// distinct keys must not fall.
 constexpr int FIC_QT_SELECT_W_WORDS = 4 * 256 + 4;
-int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total, long long value,
-                           unsigned long long* work, hipStream_t s, const FicQtPlanes* P = nullptr);
-// fic_launch_qt_compact / _tree_stats with the split rule "e(v) > *lambda": keys as fic_launch_qt_rd_keys writes them, lambda a
+int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total,
+                           unsigned long long* work, hipStream_t s, const FicQtPlanes& P);
+// fic_launch_qt_compact / _tree_stats with the split rule "e(v) > lambda[p]": keys as fic_launch_qt_rd_keys writes them, lambda a
 // device pointer (where a select left it)
 template <typename Fmt>
 int fic_launch_qt_compact_rd(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                              int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys, const uint32_t* lambda, int* counts,
-                             int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes* P = nullptr);
+                             int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes& P);
 int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys,
-                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s, const FicQtPlanes* P = nullptr);
+                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s, const FicQtPlanes& P);
 // one paint (decodeGreyScale / decodeRGB) of the n leaves of side g.B (one plane; g = that level's geometry)
 template <typename Fmt>
 int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,

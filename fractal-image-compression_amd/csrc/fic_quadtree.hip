@@ -23,7 +23,9 @@
 //                            and the select of the key at which the summed gain reaches an SSE target
 // The walkers (k_qt_count, k_qt_scatter, k_qt_tree_stats) take the split rule as a type: QtByThreshold (4.13) or QtByKey (4.23).
 // Every encoder kernel takes a batch of planes (FicQtPlanes in fic_launch.h): the plane is a grid dimension, so no
-// workgroup spans two planes, and the one-shot entries are the batch of one plane.
+// workgroup spans two planes, and every parameter of a split rule -- threshold, rank, SSE target, lambda -- is read per plane
+// from device memory.  That is the only mode: one host pipeline (qt_tree_run, fic_capi_quadtree.cpp) drives these kernels for
+// its two front ends, the one-shot entries (a batch of one plane) and the batched handle (fic_capi_qt_ctx.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
@@ -175,9 +177,9 @@ __global__ __launch_bounds__(256) void k_leaf_sse(const typename Fmt::Px* __rest
 // the rows at its offset: {x, y, B} and the level's quantised row, {idx_local, qa, qb, iso} (grey) or {idx_local, q1, q2, q3,
 // q4} (colour; QtRgbIso: + iso).
 // ---------------------------------------------------------------------------------------------
-// A batch of planes (blockIdx.y of the walkers and the key kernels; one plane: all strides unused): the arrays of plane p start
-// p strides behind those of plane 0 -- sse_stride u32 for the SSE of every level, Nr[l] rows for qrows and iso -- and the
-// threshold rule reads its threshold from thr[p] (device memory: given by the caller or left there by the budget's select).
+// A batch of planes (blockIdx.y of the walkers and the key kernels): the arrays of plane p start p strides behind those of
+// plane 0 -- sse_stride u32 for the SSE of every level, Nr[l] rows for qrows and iso -- and the threshold rule reads its
+// threshold from thr[p] (device memory: put there by the host or left there by the budget's select).
 struct FicQtLevels {
     const uint32_t* sse[3];
     const int32_t* qrows[3];     // QW ints per range block (k_qt_scatter)
@@ -189,8 +191,8 @@ struct FicQtLevels {
     int Rw_top, Ntop;
     int QW;                      // ints per row of qrows (0: none given)
     size_t sse_stride;
-    float threshold;             // thr == NULL: the threshold, by value
-    const float* thr;            // [planes]
+    const float* thr;            // [planes], the threshold rule's; NULL for the kernels that do not split by threshold
+    float threshold;             // of the plane: qt_plane's copy of thr[p]
 };
 
 // Entry l of a per-level array by selection, not by address: the walkers' l is a run-time value, and the levels of a plane
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(256) void k_qt_count(FicQtLevels L0, Split split0, 
 
 // Exclusive scan of counts[0 .. n) into offs[0 .. n), offs[n] = the total.  One workgroup: every thread sums a contiguous
 // slice, the slice sums are scanned in LDS, then every thread writes its slice's offsets.  A batch: one workgroup per plane
-// (blockIdx.x) on counts [planes][n] and offs [planes][n + 1]; totals (NULL or [planes]) gets every plane's total once more.
+// (blockIdx.x) on counts [planes][n] and offs [planes][n + 1]; totals [planes] gets every plane's total once more.
 #define FIC_QT_SCAN_THREADS 1024
 __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __restrict__ counts, int* __restrict__ offs, int n,
                                                                  int* __restrict__ totals)
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(FIC_QT_SCAN_THREADS) void k_qt_scan(const int* __re
     }
     if (t == FIC_QT_SCAN_THREADS - 1) {
         offs[n] = part[t];
-        if (totals) totals[blockIdx.x] = part[t];
+        totals[blockIdx.x] = part[t];
     }
 }
 
@@ -413,15 +415,15 @@ __device__ __forceinline__ void qt_select_resolve(const uint32_t* __restrict__ b
 // One pass: 256 threads per workgroup with a grid stride over the keys, a 256-bin histogram in LDS, one global atomic per
 // non-empty bin.
 // A batch is P independent selects, blockIdx.y the plane: keys [planes][n], work [planes][FIC_QT_SELECT_WORDS] (bins, then the
-// result), and the rank of plane p is ranks[p], read from device memory (ranks NULL: `rank`).
-__global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t rank, const uint32_t* __restrict__ ranks,
+// result), and the rank of plane p is ranks[p], read from device memory.
+__global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ ranks,
                                                         uint32_t* __restrict__ work, int pass)
 {
     __shared__ uint32_t hist[256];
     hist[threadIdx.x] = 0;
     keys += (size_t)blockIdx.y * n;
     uint32_t* bins = work + (size_t)blockIdx.y * FIC_QT_SELECT_WORDS;
-    if (ranks) rank = ranks[blockIdx.y];
+    const uint32_t rank = ranks[blockIdx.y];
     uint32_t prefix, rem;
     qt_select_resolve(bins, pass, rank, prefix, rem);       // its barriers also cover hist's zeroes
     const int shift = 24 - 8 * pass;
@@ -436,13 +438,13 @@ __global__ __launch_bounds__(256) void k_qt_select_hist(const uint32_t* __restri
 
 // One workgroup: resolves the last pass.  out = {K, the bits of the threshold, #{keys > K}, 0}; the threshold is the smallest
 // float >= K / 256: K rounded up to a float, times 2^-8 (exact).
-// One workgroup per plane (blockIdx.x); param (NULL or [planes]) gets word `param_word` of the plane's result: the rule's parameter.
-__global__ __launch_bounds__(256) void k_qt_select_final(uint32_t* __restrict__ work, uint32_t rank, const uint32_t* __restrict__ ranks,
+// One workgroup per plane (blockIdx.x); param [planes] gets word `param_word` of the plane's result: the rule's parameter.
+__global__ __launch_bounds__(256) void k_qt_select_final(uint32_t* __restrict__ work, const uint32_t* __restrict__ ranks,
                                                          uint32_t* __restrict__ param, int param_word)
 {
     const uint32_t* bins = work + (size_t)blockIdx.x * FIC_QT_SELECT_WORDS;
     uint32_t* out = work + (size_t)blockIdx.x * FIC_QT_SELECT_WORDS + 4 * 256;
-    if (ranks) rank = ranks[blockIdx.x];
+    const uint32_t rank = ranks[blockIdx.x];
     uint32_t K, rem;
     qt_select_resolve(bins, 4, rank, K, rem);
     if (threadIdx.x == 0) {
@@ -450,7 +452,7 @@ __global__ __launch_bounds__(256) void k_qt_select_final(uint32_t* __restrict__ 
         out[1] = __float_as_uint(__fmul_rn(__uint2float_ru(K), 0x1p-8f));
         out[2] = rank - rem;
         out[3] = 0;
-        if (param) param[blockIdx.x] = out[param_word];
+        param[blockIdx.x] = out[param_word];
     }
 }
 
@@ -566,8 +568,8 @@ __global__ __launch_bounds__(256) void k_qt_rd_keys(FicQtLevels L0, int n1, uint
 // Then "A(x) < need" is monotone in x, and x0 = min{x : A(x) < need} (2^32 when there is none, i.e. need <= 0) comes out of
 // the radix select of 4.18 with int64 gain sums in the bins: per pass, with `acc` the gain above the prefix, the digit is the
 // smallest d with acc + #{gain of digits > d} < need -- every larger digit passes too, none smaller does -- and acc grows by
-// that sum.  x0 is a key or 0, and b = the largest key < x0.  need = *total - value (an SSE target: the top-level sum minus
-// max_sse, both on the device) or, total NULL, value itself.
+// that sum.  x0 is a key or 0, and b = the largest key < x0.  need = (int64) *total - value, both on the device (an SSE target:
+// the top-level sum minus max_sse).
 //
 // qt_select_w_resolve: x0's prefix and acc after `npass` passes from their final bins (i64 [4][256]), by all 256 threads: an
 // inclusive suffix scan of the pass's 256 sums in LDS, then the smallest passing digit through an LDS atomicMin.
@@ -605,28 +607,22 @@ __device__ __forceinline__ void qt_select_w_resolve(const long long* __restrict_
     prefix = s_prefix;
 }
 
-__device__ __forceinline__ long long qt_select_w_need(const unsigned long long* __restrict__ total, long long value)
-{
-    return total ? (long long)*total - value : value;
-}
-
 // One pass: k_qt_select_hist with the gains summed per bin (64-bit LDS adds, one global atomic per bin with a non-zero sum).
-// A batch, as k_qt_select_hist: blockIdx.y the plane, keys and gains [planes][n], total [planes], work [planes]
-// [FIC_QT_SELECT_W_WORDS], and the value of plane p is values[p] (values NULL: `value`).
+// A batch, as k_qt_select_hist: blockIdx.y the plane, keys and gains [planes][n], total and values [planes], work [planes]
+// [FIC_QT_SELECT_W_WORDS].
 __global__ __launch_bounds__(256) void k_qt_select_hist_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
-                                                          const unsigned long long* __restrict__ total, long long value,
-                                                          const long long* __restrict__ values, long long* __restrict__ work, int pass)
+                                                          const unsigned long long* __restrict__ total, const long long* __restrict__ values,
+                                                          long long* __restrict__ work, int pass)
 {
     __shared__ unsigned long long hist[256];
     hist[threadIdx.x] = 0;
     keys += (size_t)blockIdx.y * n;
     gains += (size_t)blockIdx.y * n;
-    if (total) total += blockIdx.y;
-    if (values) value = values[blockIdx.y];
+    const long long need = (long long)total[blockIdx.y] - values[blockIdx.y];
     long long* bins = work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS;
     uint32_t prefix;
     bool none;
-    qt_select_w_resolve(bins, pass, qt_select_w_need(total, value), prefix, none);      // its barriers also cover hist's zeroes
+    qt_select_w_resolve(bins, pass, need, prefix, none);                                // its barriers also cover hist's zeroes
     if (none) return;                                                                   // uniform
     const int shift = 24 - 8 * pass;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -641,21 +637,19 @@ __global__ __launch_bounds__(256) void k_qt_select_hist_w(const uint32_t* __rest
 // The last step, again over all keys: out u64 [4], zeroed by the launcher = {b in the low 32 bits, #{keys > b}, the sum of
 // their gains (signed), 0}.  b = max{key < x0} or 0; the keys > b are those >= max(x0, 1).  Wave sums, then one atomic
 // each per wave and non-zero value.
-// param (NULL or u32 [planes], zeroed by the launcher) gets every plane's b once more: the lambda its walkers read.
+// param (u32 [planes], zeroed by the launcher) gets every plane's b once more: the lambda its walkers read.
 __global__ __launch_bounds__(256) void k_qt_select_final_w(const uint32_t* __restrict__ keys, const long long* __restrict__ gains, uint32_t n,
-                                                           const unsigned long long* __restrict__ total, long long value,
-                                                           const long long* __restrict__ values, unsigned long long* __restrict__ work,
-                                                           uint32_t* __restrict__ param)
+                                                           const unsigned long long* __restrict__ total, const long long* __restrict__ values,
+                                                           unsigned long long* __restrict__ work, uint32_t* __restrict__ param)
 {
     keys += (size_t)blockIdx.y * n;
     gains += (size_t)blockIdx.y * n;
-    if (total) total += blockIdx.y;
-    if (values) value = values[blockIdx.y];
+    const long long need = (long long)total[blockIdx.y] - values[blockIdx.y];
     const long long* bins = (const long long*)work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS;
     unsigned long long* out = work + (size_t)blockIdx.y * FIC_QT_SELECT_W_WORDS + 4 * 256;
     uint32_t prefix;
     bool none;
-    qt_select_w_resolve(bins, 4, qt_select_w_need(total, value), prefix, none);
+    qt_select_w_resolve(bins, 4, need, prefix, none);
     const unsigned long long x0 = none ? 0x100000000ull : (unsigned long long)prefix, from = x0 ? x0 : 1ull;
     uint32_t b = 0;
     unsigned long long cnt = 0, gain = 0;
@@ -673,7 +667,7 @@ __global__ __launch_bounds__(256) void k_qt_select_final_w(const uint32_t* __res
     }
     if ((threadIdx.x & 63) == 0) {
         if (b) atomicMax((uint32_t*)out, b);
-        if (b && param) atomicMax(param + blockIdx.y, b);
+        if (b) atomicMax(param + blockIdx.y, b);
         if (cnt) atomicAdd(out + 1, cnt);
         if (gain) atomicAdd(out + 2, gain);
     }
@@ -781,25 +775,21 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt:
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
-// planes of a launch and the stride of its SSE arrays (P NULL: one plane)
-static inline int qt_planes(const FicQtPlanes* P) { return P ? P->planes : 1; }
-
 template <typename Fmt>
 int fic_launch_leaf_sse(const typename Fmt::Px* image, const typename Fmt::Px* scaled, const int32_t* qrows, const int32_t* iso,
-                        uint32_t* sse, const FicGeom& g, hipStream_t s, const FicQtPlanes* P)
+                        uint32_t* sse, const FicGeom& g, hipStream_t s, const FicQtPlanes& P)
 {
-    const size_t stride = P ? P->sse_stride : (size_t)g.Nr;
-    if (hipMemset2DAsync(sse, stride * sizeof(uint32_t), 0, (size_t)g.Nr * sizeof(uint32_t), (size_t)qt_planes(P), s) != hipSuccess) return -1;
+    if (hipMemset2DAsync(sse, P.sse_stride * sizeof(uint32_t), 0, (size_t)g.Nr * sizeof(uint32_t), (size_t)P.planes, s) != hipSuccess) return -1;
     auto k = g.B == 4 ? k_leaf_sse<Fmt, 4> : (g.B == 8 ? k_leaf_sse<Fmt, 8> : k_leaf_sse<Fmt, 16>);
-    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256, qt_planes(P)), dim3(256), 0, s, image, scaled, qrows, iso, sse, g, stride);
+    hipLaunchKernelGGL(k, dim3((g.Nr * g.B + 255) / 256, P.planes), dim3(256), 0, s, image, scaled, qrows, iso, sse, g, P.sse_stride);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-// qrows / iso NULL: for the kernels that read the SSE alone.  P: the strides of a batch and, for the threshold rule (by_threshold),
-// its thresholds: P->param as floats
+// qrows / iso NULL: for the kernels that read the SSE alone.  P: the strides of the batch and, for the threshold rule
+// (by_threshold), its thresholds: P.param as floats
 static FicQtLevels qt_levels_arg(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw, int nl,
-                                 int B_max, int Rw_top, int Ntop, float threshold, int QW, const FicQtPlanes* P, bool by_threshold)
+                                 int B_max, int Rw_top, int Ntop, int QW, const FicQtPlanes& P, bool by_threshold)
 {
     FicQtLevels L{};
     for (int l = 0; l < nl; l++) {
@@ -807,39 +797,36 @@ static FicQtLevels qt_levels_arg(const uint32_t* const* sse, const int32_t* cons
         L.qrows[l] = qrows ? qrows[l] : nullptr;
         L.iso[l] = iso ? iso[l] : nullptr;
         L.Rw[l] = Rw[l];
-        L.Nr[l] = P ? P->Nr[l] : 0;
+        L.Nr[l] = P.Nr[l];
     }
     L.nl = nl;
     L.B_max = B_max;
     L.Rw_top = Rw_top;
     L.Ntop = Ntop;
     L.QW = qrows ? QW : 0;
-    L.sse_stride = P ? P->sse_stride : 0;
-    L.threshold = threshold;
-    L.thr = P && by_threshold ? (const float*)P->param : nullptr;
+    L.sse_stride = P.sse_stride;
+    L.thr = by_threshold ? (const float*)P.param : nullptr;
     return L;
 }
 
 int fic_launch_qt_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                       hipStream_t s, const FicQtPlanes* P)
+                       hipStream_t s, const FicQtPlanes& P)
 {
-    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false);
-    hipLaunchKernelGGL(k_qt_keys, dim3((Ntop + n1 + 255) / 256, qt_planes(P)), dim3(256), 0, s, L, n1, keys);
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0, P, false);
+    hipLaunchKernelGGL(k_qt_keys, dim3((Ntop + n1 + 255) / 256, P.planes), dim3(256), 0, s, L, n1, keys);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t rank, uint32_t* work, hipStream_t s, const FicQtPlanes* P, int param_word)
+int fic_launch_qt_select(const uint32_t* keys, uint32_t n, uint32_t* work, hipStream_t s, const FicQtPlanes& P, int param_word)
 {
-    const int planes = qt_planes(P);
-    if (hipMemsetAsync(work, 0, (size_t)planes * FIC_QT_SELECT_WORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
+    if (hipMemsetAsync(work, 0, (size_t)P.planes * FIC_QT_SELECT_WORDS * sizeof(uint32_t), s) != hipSuccess) return -1;
     const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
-    const uint32_t* ranks = P ? P->ranks : nullptr;
     for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_qt_select_hist, dim3(nb, planes), dim3(256), 0, s, keys, n, rank, ranks, work, pass);
+        hipLaunchKernelGGL(k_qt_select_hist, dim3(nb, P.planes), dim3(256), 0, s, keys, n, P.ranks, work, pass);
         FIC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_qt_select_final, dim3(planes), dim3(256), 0, s, work, rank, ranks, P ? P->param : nullptr, param_word);
+    hipLaunchKernelGGL(k_qt_select_final, dim3(P.planes), dim3(256), 0, s, work, P.ranks, P.param, param_word);
     FIC_LAUNCH_CHECK();
     return 0;
 }
@@ -853,29 +840,28 @@ static int qt_tree_stats(const FicQtLevels& L, const Split& split, unsigned long
     return 0;
 }
 
-int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, float threshold,
-                             unsigned long long* stats, hipStream_t s, const FicQtPlanes* P)
+int fic_launch_qt_tree_stats(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop,
+                             unsigned long long* stats, hipStream_t s, const FicQtPlanes& P)
 {
-    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, threshold, 0, P, true), QtByThreshold{}, stats, s, qt_planes(P));
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0, P, true), QtByThreshold{}, stats, s, P.planes);
 }
 
 int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys,
-                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s, const FicQtPlanes* P)
+                                const uint32_t* lambda, unsigned long long* stats, hipStream_t s, const FicQtPlanes& P)
 {
-    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false), QtByKey{keys, lambda, P ? P->nkeys : 0}, stats, s,
-                         qt_planes(P));
+    return qt_tree_stats(qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0, P, false), QtByKey{keys, lambda, P.nkeys}, stats, s, P.planes);
 }
 
 template <typename Fmt, typename Split>
-static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes* P)
+static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes& P)
 {
-    const int nb = (L.Ntop + 255) / 256, planes = qt_planes(P);
-    hipLaunchKernelGGL(k_qt_count<Split>, dim3(nb, planes), dim3(256), 0, s, L, split, counts);
+    const int nb = (L.Ntop + 255) / 256;
+    hipLaunchKernelGGL(k_qt_count<Split>, dim3(nb, P.planes), dim3(256), 0, s, L, split, counts);
     FIC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_qt_scan, dim3(planes), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, L.Ntop, P ? P->n_leaves : nullptr);
+    hipLaunchKernelGGL(k_qt_scan, dim3(P.planes), dim3(FIC_QT_SCAN_THREADS), 0, s, (const int*)counts, offs, L.Ntop, P.n_leaves);
     FIC_LAUNCH_CHECK();
     if (leaves) {
-        hipLaunchKernelGGL((k_qt_scatter<Fmt, Split>), dim3(nb, planes), dim3(256), 0, s, L, split, (const int*)offs, leaves, P ? P->leaf_stride : (size_t)0);
+        hipLaunchKernelGGL((k_qt_scatter<Fmt, Split>), dim3(nb, P.planes), dim3(256), 0, s, L, split, (const int*)offs, leaves, P.leaf_stride);
         FIC_LAUNCH_CHECK();
     }
     return 0;
@@ -883,44 +869,42 @@ static int qt_compact(const FicQtLevels& L, const Split& split, int* counts, int
 
 template <typename Fmt>
 int fic_launch_qt_compact(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
-                          int nl, int B_max, int Rw_top, int Ntop, float threshold, int* counts, int* offs, int32_t* leaves,
-                          hipStream_t s, const FicQtPlanes* P)
+                          int nl, int B_max, int Rw_top, int Ntop, int* counts, int* offs, int32_t* leaves, hipStream_t s,
+                          const FicQtPlanes& P)
 {
-    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, threshold, Fmt::QW, P, true), QtByThreshold{}, counts, offs, leaves, s, P);
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, Fmt::QW, P, true), QtByThreshold{}, counts, offs, leaves, s, P);
 }
 
 template <typename Fmt>
 int fic_launch_qt_compact_rd(const uint32_t* const* sse, const int32_t* const* qrows, const int32_t* const* iso, const int* Rw,
                              int nl, int B_max, int Rw_top, int Ntop, const uint32_t* keys, const uint32_t* lambda, int* counts,
-                             int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes* P)
+                             int* offs, int32_t* leaves, hipStream_t s, const FicQtPlanes& P)
 {
-    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, 0.0f, Fmt::QW, P, false), QtByKey{keys, lambda, P ? P->nkeys : 0},
-                           counts, offs, leaves, s, P);
+    return qt_compact<Fmt>(qt_levels_arg(sse, qrows, iso, Rw, nl, B_max, Rw_top, Ntop, Fmt::QW, P, false), QtByKey{keys, lambda, P.nkeys}, counts, offs,
+                           leaves, s, P);
 }
 
 int fic_launch_qt_rd_keys(const uint32_t* const* sse, const int* Rw, int nl, int B_max, int Rw_top, int Ntop, int n1, uint32_t* keys,
-                          long long* gains, unsigned long long* top_sum, hipStream_t s, const FicQtPlanes* P)
+                          long long* gains, unsigned long long* top_sum, hipStream_t s, const FicQtPlanes& P)
 {
-    if (hipMemsetAsync(top_sum, 0, (size_t)qt_planes(P) * sizeof(unsigned long long), s) != hipSuccess) return -1;
-    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0.0f, 0, P, false);
-    hipLaunchKernelGGL(k_qt_rd_keys, dim3((Ntop + n1 + 255) / 256, qt_planes(P)), dim3(256), 0, s, L, n1, keys, gains, top_sum);
+    if (hipMemsetAsync(top_sum, 0, (size_t)P.planes * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    const FicQtLevels L = qt_levels_arg(sse, nullptr, nullptr, Rw, nl, B_max, Rw_top, Ntop, 0, P, false);
+    hipLaunchKernelGGL(k_qt_rd_keys, dim3((Ntop + n1 + 255) / 256, P.planes), dim3(256), 0, s, L, n1, keys, gains, top_sum);
     FIC_LAUNCH_CHECK();
     return 0;
 }
 
-int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total, long long value,
-                           unsigned long long* work, hipStream_t s, const FicQtPlanes* P)
+int fic_launch_qt_select_w(const uint32_t* keys, const long long* gains, uint32_t n, const unsigned long long* total,
+                           unsigned long long* work, hipStream_t s, const FicQtPlanes& P)
 {
-    const int planes = qt_planes(P);
-    if (hipMemsetAsync(work, 0, (size_t)planes * FIC_QT_SELECT_W_WORDS * sizeof(unsigned long long), s) != hipSuccess) return -1;
-    if (P && hipMemsetAsync(P->param, 0, (size_t)planes * sizeof(uint32_t), s) != hipSuccess) return -1;      // k_qt_select_final_w's atomicMax
+    if (hipMemsetAsync(work, 0, (size_t)P.planes * FIC_QT_SELECT_W_WORDS * sizeof(unsigned long long), s) != hipSuccess) return -1;
+    if (hipMemsetAsync(P.param, 0, (size_t)P.planes * sizeof(uint32_t), s) != hipSuccess) return -1;      // k_qt_select_final_w's atomicMax
     const uint32_t need = (n + 255u) / 256u, nb = need < 1024u ? (need ? need : 1u) : 1024u;      // beyond: the grid stride
-    const long long* values = P ? P->values : nullptr;
     for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_qt_select_hist_w, dim3(nb, planes), dim3(256), 0, s, keys, gains, n, total, value, values, (long long*)work, pass);
+        hipLaunchKernelGGL(k_qt_select_hist_w, dim3(nb, P.planes), dim3(256), 0, s, keys, gains, n, total, P.values, (long long*)work, pass);
         FIC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_qt_select_final_w, dim3(nb, planes), dim3(256), 0, s, keys, gains, n, total, value, values, work, P ? P->param : nullptr);
+    hipLaunchKernelGGL(k_qt_select_final_w, dim3(nb, P.planes), dim3(256), 0, s, keys, gains, n, total, P.values, work, P.param);
     FIC_LAUNCH_CHECK();
     return 0;
 }
@@ -940,12 +924,12 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
 
 #define FIC_QT_INSTANTIATE(Fmt)                                                                                                       \
     template int fic_launch_leaf_sse<Fmt>(const Fmt::Px*, const Fmt::Px*, const int32_t*, const int32_t*, uint32_t*, const FicGeom&,  \
-                                          hipStream_t, const FicQtPlanes*);                                                           \
+                                          hipStream_t, const FicQtPlanes&);                                                           \
     template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \
-                                            int, int, int, float, int*, int*, int32_t*, hipStream_t, const FicQtPlanes*);             \
+                                            int, int, int, int*, int*, int32_t*, hipStream_t, const FicQtPlanes&);                    \
     template int fic_launch_qt_compact_rd<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int, \
                                                int, int, int, const uint32_t*, const uint32_t*, int*, int*, int32_t*, hipStream_t,    \
-                                               const FicQtPlanes*);                                                                   \
+                                               const FicQtPlanes&);                                                                   \
     template int fic_launch_decode_paint_leaves<Fmt>(const Fmt::Px*, Fmt::Px*, const Fmt::Leaf*, int, FicDecodeState*, uint32_t*,     \
                                                      int, const FicGeom&, hipStream_t);
 FIC_QT_INSTANTIATE(QtGrey)
