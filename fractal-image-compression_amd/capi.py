@@ -33,6 +33,50 @@ def declared_symbols():
     return sorted(set(re.findall(r"FIC_API\s+[\w\s\*]+?\b(fic_\w+)\s*\(", text)))
 
 
+_C_TYPES = {"char": C.c_char, "int": C.c_int, "float": C.c_float, "double": C.c_double, "int32_t": C.c_int32, "int64_t": C.c_int64,
+            "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_HANDLE_TYPES = ("void", "fic_ctx", "fic_rgb_ctx", "fic_qt_ctx")       # pointers to these are c_void_p
+
+
+def _ctype(decl, what):
+    """The ctypes type of one C type as include/fic.h spells it, the parameter's name (and an array suffix, which makes it a
+    pointer) included; None for plain void.  A type this does not know is an error, not a default."""
+    words = re.sub(r"\[\d*\]", " * ", decl.replace("*", " * ")).split()
+    stars = words.count("*")
+    base = [x for x in words if x not in ("*", "const")]
+    if not base or len(base) > 2:                       # the type, and perhaps the parameter's name
+        raise FicError(-3, f"include/fic.h: cannot read the type of '{decl}' ({what})")
+    t = base[0]
+    if t in _HANDLE_TYPES:
+        if stars == 0 and t == "void" and len(base) == 1:
+            return None
+        if stars == 1:
+            return C.c_void_p
+        if stars == 2 and t == "void":
+            return C.POINTER(C.c_void_p)
+    elif t in _C_TYPES:
+        if stars == 0:
+            return _C_TYPES[t]
+        if stars == 1:
+            return C.c_char_p if t == "char" else C.POINTER(_C_TYPES[t])
+    raise FicError(-3, f"include/fic.h: no ctypes type for '{decl}' ({what})")
+
+
+def prototypes():
+    """{name: (restype, argtypes)} of every FIC_API declaration of include/fic.h: the header is the one statement of the C ABI,
+    lib() types every entry from it."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER_PATH).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"FIC_API\s+([^;()]*?)\b(fic_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
+        args = [] if params.strip() == "void" else [_ctype(p, name) for p in params.split(",")]
+        if None in args:
+            raise FicError(-3, f"include/fic.h: a void parameter in {name}")
+        out[name] = (_ctype(ret, name), args)
+    if sorted(out) != declared_symbols():
+        raise FicError(-3, "include/fic.h: a FIC_API declaration this parser cannot read: " + ", ".join(sorted(set(declared_symbols()) ^ set(out))))
+    return out
+
+
 _lib = None
 
 
@@ -61,131 +105,7 @@ def lib():
                            "(hipcc --offload-arch=gfx950); there is no fallback path")
     _torch_first()
     L = C.CDLL(so)
-    vp, ip = C.c_void_p, C.POINTER(C.c_int)
-    i32p, f32p, u8p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
-    sig = {
-        "fic_version": (C.c_char_p, []),
-        "fic_last_error": (C.c_char_p, []),
-        "fic_last_error_code": (C.c_int, []),
-        "fic_device_count": (C.c_int, []),
-        "fic_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
-        "fic_is_greyscale_argb": (C.c_int, [i32p, C.c_int, C.c_int]),
-        "fic_encode_gray_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p]),
-        "fic_encode_gray_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p]),
-        "fic_encode_gray_argb_multi": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p]),
-        "fic_encode_gray_u8_multi": (C.c_int, [u8p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p]),
-        "fic_write_run_gray": (C.c_int64, [i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int64]),
-        "fic_ctx_create": (vp, [C.c_int] * 7),
-        "fic_ctx_destroy": (None, [vp]),
-        "fic_ctx_set_gray_host": (C.c_int, [vp, u8p]),
-        "fic_ctx_set_argb_host": (C.c_int, [vp, i32p]),
-        "fic_ctx_set_gray_device": (C.c_int, [vp, vp]),
-        "fic_ctx_encode": (C.c_int, [vp, C.c_int, C.c_int, vp]),
-        "fic_ctx_sync": (C.c_int, [vp]),
-        "fic_ctx_get_results_host": (C.c_int, [vp, i32p, f32p, f32p, i32p, i32p, i32p, f32p]),
-        "fic_ctx_result_device_ptrs": (C.c_int, [vp] + [C.POINTER(vp)] * 7),
-        "fic_ctx_records_device_ptr": (C.c_int, [vp, C.POINTER(vp)]),
-        "fic_ctx_collage_host": (C.c_int, [vp, i32p]),
-        "fic_encode_rgb_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p]),
-        "fic_rgb_ctx_create": (vp, [C.c_int] * 6),
-        "fic_encode_rgb_iso_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p, i32p]),
-        "fic_rgb_ctx_create_iso": (vp, [C.c_int] * 7),
-        "fic_rgb_ctx_get_iso_host": (C.c_int, [vp, i32p]),
-        "fic_rgb_ctx_destroy": (None, [vp]),
-        "fic_rgb_ctx_set_argb_host": (C.c_int, [vp, i32p]),
-        "fic_rgb_ctx_set_argb_device": (C.c_int, [vp, vp]),
-        "fic_rgb_ctx_encode": (C.c_int, [vp, C.c_int, vp]),
-        "fic_rgb_ctx_sync": (C.c_int, [vp]),
-        "fic_rgb_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "fic_rgb_ctx_last_sweep": (C.c_int, [vp]),
-        "fic_rgb_ctx_get_results_host": (C.c_int, [vp, i32p, f32p, f32p, f32p, f32p, i32p, i32p]),
-        "fic_rgb_ctx_decode_host": (C.c_int, [vp, i32p, f32p, ip]),
-        "fic_write_run_rgb": (C.c_int64, [i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int64]),
-        "fic_decode_gray_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_ctx_decode_host": (C.c_int, [vp, u8p, f32p, ip]),
-        "fic_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "fic_ctx_sweep_time": (C.c_int, [vp, C.POINTER(C.c_double), ip, C.c_int]),
-        "fic_ctx_info": (C.c_int, [vp, ip]),
-        "fic_sweep_ranges_per_pool_read": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-        "fic_ctx_last_kernel": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "fic_ctx_sweep_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
-        "fic_debug_rccl_selftest": (C.c_int, [C.c_int]),
-        "fic_debug_gather_fallbacks": (C.c_int, []),
-        "fic_debug_float_sum": (C.c_int, [C.c_int, C.c_float, C.POINTER(C.c_uint32), C.c_int, f32p]),
-        "fic_debug_float_sum_fallbacks": (C.c_int, []),
-        "fic_debug_decode_gray_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, f32p, ip, ip]),
-        "fic_debug_sqrt_f64": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
-        "fic_ctx_debug_pool_host": (C.c_int, [vp, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u8p]),
-        "fic_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
-        "fic_ctx_debug_lsq_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
-        "fic_rgb_ctx_debug_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
-        "fic_rgb_ctx_last_kernel": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "fic_rgb_ctx_debug_lsq_q_host": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]),
-        "fic_rgb_ctx_sweep_time": (C.c_int, [vp, C.POINTER(C.c_double), ip, C.c_int]),
-        "fic_rgb_ctx_last_lsq_chunks": (C.c_int, [vp]),
-        "fic_rgb_ctx_sweep_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
-        "fic_encode_gray_quadtree_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_encode_gray_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_write_run_quadtree": (C.c_int64, [i32p] + [C.c_int] * 7 + [u8p, C.c_int64]),
-        "fic_decode_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_debug_quadtree_sse": (C.c_int, [u8p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
-        "fic_encode_rgb_quadtree_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_write_run_rgb_quadtree": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
-        "fic_decode_rgb_quadtree_run": (C.c_int, [u8p, C.c_int64, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_debug_rgb_quadtree_sse": (C.c_int, [i32p] + [C.c_int] * 6 + [C.POINTER(C.c_uint32), C.c_int64]),
-        "fic_decode_gray_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_decode_rgb_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_decode_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_decode_rgb_quadtree_run_zoom": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_ctx_decode_zoom_host": (C.c_int, [vp, C.c_int, u8p, f32p, ip]),
-        "fic_rgb_ctx_decode_zoom_host": (C.c_int, [vp, C.c_int, i32p, f32p, ip]),
-        "fic_write_run_gray_iso": (C.c_int64, [i32p, i32p] + [C.c_int] * 5 + [u8p, C.c_int64]),
-        "fic_write_run_rgb_iso": (C.c_int64, [i32p, i32p] + [C.c_int] * 5 + [u8p, C.c_int64]),
-        "fic_decode_gray_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, u8p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_decode_rgb_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_encode_rgb_quadtree_iso_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_write_run_rgb_quadtree_iso": (C.c_int64, [i32p] + [C.c_int] * 6 + [u8p, C.c_int64]),
-        "fic_decode_rgb_quadtree_iso_run": (C.c_int, [u8p, C.c_int64, C.c_int, C.c_int, i32p, C.c_int64, ip, ip, f32p, ip]),
-        "fic_debug_rgb_quadtree_iso_sse": (C.c_int, [i32p] + [C.c_int] * 7 + [C.POINTER(C.c_uint32), C.c_int64]),
-        "fic_encode_gray_quadtree_budget_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
-        "fic_encode_gray_quadtree_budget_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
-        "fic_encode_rgb_quadtree_budget_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
-        "fic_encode_rgb_quadtree_iso_budget_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_int64, C.c_int, i32p, C.c_int64, ip, f32p, u64p]),
-        "fic_quadtree_leaves_for_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
-        "fic_ctx_get_lsq_error_host": (C.c_int, [vp, C.POINTER(C.c_int64)]),
-        "fic_encode_gray_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p, C.POINTER(C.c_int64)]),
-        "fic_encode_gray_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, i32p, i32p, C.POINTER(C.c_int64)]),
-        "fic_encode_gray_quadtree_lsq_u8": (C.c_int, [u8p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_encode_gray_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_rgb_ctx_get_lsq_error_host": (C.c_int, [vp, C.POINTER(C.c_int64)]),
-        "fic_encode_rgb_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [i32p, f32p, f32p, f32p, f32p, i32p, i32p, i32p, C.POINTER(C.c_int64)]),
-        "fic_encode_rgb_quadtree_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 5 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_encode_rgb_quadtree_iso_lsq_argb": (C.c_int, [i32p] + [C.c_int] * 6 + [C.c_float, C.c_int, i32p, C.c_int64, ip]),
-        "fic_debug_qt_select": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.POINTER(C.c_uint32), f32p, C.POINTER(C.c_int64)]),
-        "fic_encode_gray_quadtree_rd_u8": (C.c_int, [u8p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
-        "fic_encode_gray_quadtree_rd_argb": (C.c_int, [i32p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
-        "fic_encode_rgb_quadtree_rd_argb": (C.c_int, [i32p] + [C.c_int] * 7 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
-        "fic_encode_rgb_quadtree_iso_rd_argb": (C.c_int, [i32p] + [C.c_int] * 8 + [C.c_uint64, C.c_int, i32p, C.c_int64, ip, C.POINTER(C.c_uint32), u64p]),
-        "fic_debug_qt_rd_keys": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)] + [C.c_int] * 4 + [C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
-        "fic_debug_qt_select_weighted": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.POINTER(C.c_uint32),
-                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "fic_debug_live_memory": (C.c_int, [C.POINTER(C.c_int64)]),
-        "fic_qt_ctx_create": (vp, [C.c_int] * 9),
-        "fic_qt_ctx_destroy": (None, [vp]),
-        "fic_qt_ctx_set_gray_host": (C.c_int, [vp, u8p]),
-        "fic_qt_ctx_set_argb_host": (C.c_int, [vp, i32p]),
-        "fic_qt_ctx_set_gray_device": (C.c_int, [vp, vp]),
-        "fic_qt_ctx_set_argb_device": (C.c_int, [vp, vp]),
-        "fic_qt_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "fic_qt_ctx_encode_threshold": (C.c_int, [vp, f32p, vp]),
-        "fic_qt_ctx_encode_budget": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
-        "fic_qt_ctx_encode_rd": (C.c_int, [vp, C.c_int, u64p, vp]),
-        "fic_qt_ctx_sync": (C.c_int, [vp]),
-        "fic_qt_ctx_get_results_host": (C.c_int, [vp, i32p, C.POINTER(C.c_uint32), u64p]),
-        "fic_qt_ctx_get_leaves_host": (C.c_int, [vp, C.c_int, i32p, C.c_int64, ip]),
-        "fic_qt_ctx_result_device_ptrs": (C.c_int, [vp] + [C.POINTER(vp)] * 4),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in prototypes().items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -238,9 +158,11 @@ def geometry(w, h, B):
     return tuple(x.value for x in v)
 
 
-def _decode_run_zoom(fn, run, header_bytes, what, dtype, device, avg_error_in, zoom):
+def _decode_run(plain, zoomed, run, header_bytes, what, dtype, device, avg_error_in, zoom):
     """One stream decoder of the C ABI at `zoom`: (pixels [zoom*h * zoom*w] of dtype, avgError float32, iterations, zoom*w,
-    zoom*h).  The output is sized from the header; the library checks everything else."""
+    zoom*h).  `zoomed` is the entry that takes the zoom argument, `plain` its twin without one (or None), which serves
+    zoom = 1.  The output is sized from the header; the library checks everything else."""
+    fn = plain if zoom == 1 and plain is not None else zoomed
     buf = np.frombuffer(bytes(run), np.uint8)
     if buf.size < header_bytes:
         raise FicError(-3, f"{what} shorter than its header")
@@ -253,30 +175,18 @@ def _decode_run_zoom(fn, run, header_bytes, what, dtype, device, avg_error_in, z
     out = np.zeros(max(cap, 1), dtype)
     avg = C.c_float(avg_error_in)
     it, wo, ho = C.c_int(), C.c_int(), C.c_int()
-    check(fn(ptr(buf, C.c_uint8), buf.size, z, device, ptr(out, C.c_uint8 if dtype == np.uint8 else C.c_int32), cap, C.byref(wo),
-             C.byref(ho), C.byref(avg), C.byref(it)))
+    check(fn(ptr(buf, C.c_uint8), buf.size, *((z,) if fn is zoomed else ()), device, ptr(out, C.c_uint8 if dtype == np.uint8 else C.c_int32),
+             cap, C.byref(wo), C.byref(ho), C.byref(avg), C.byref(it)))
     return out[:cap], np.float32(avg.value), it.value, wo.value, ho.value
 
 
 def decode_gray_run(run, device=0, avg_error_in=0.0, zoom=1):
-    """FractalCompression.decode on a grey .run stream (FC:547-553, 356-421), on the GPU.
+    """FractalCompression.decode on a grey .run stream (FC:547-553, 356-421), on the GPU (fic_decode_gray_run).
     Returns (gray uint8 [H,W], avgError float32 after the call, iterations).  zoom = 2 / 4: the same loop on the geometry
     (zoom*w, zoom*h, zoom*B, wK), [zoom*H, zoom*W] out (fic_decode_gray_run_zoom)."""
-    if zoom != 1:
-        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_gray_run_zoom, run, 20, "run stream", np.uint8, device, avg_error_in, zoom)
-        return out.reshape(h, w), avg, it
-    buf = np.frombuffer(bytes(run), np.uint8)
-    if buf.size < 20:
-        raise FicError(-3, "run stream shorter than its header")
-    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
-    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
-    cap = max(w, 0) * max(h, 0)
-    out = np.zeros(max(cap, 1), np.uint8)
-    avg = C.c_float(avg_error_in)
-    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
-    check(lib().fic_decode_gray_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_uint8), cap, C.byref(wo),
-                                    C.byref(ho), C.byref(avg), C.byref(it)))
-    return out[:cap].reshape(h, w), np.float32(avg.value), it.value
+    L = lib()
+    out, avg, it, w, h = _decode_run(L.fic_decode_gray_run, L.fic_decode_gray_run_zoom, run, 20, "run stream", np.uint8, device, avg_error_in, zoom)
+    return out.reshape(h, w), avg, it
 
 
 SEARCHES = {"reference": 0, "lsq": 1}
@@ -349,7 +259,6 @@ def encode_gray_multi(gray, B, wK, n_iso=1, n_gpus=1, width=None, height=None):
 
 
 def release_cache():
-    lib().fic_release_cache.restype = None
     lib().fic_release_cache()
 
 
@@ -368,23 +277,7 @@ def decode_rgb_run(run, device=0, avg_error_in=0.0, zoom=1):
     """decodeRGB (FC:430-508) on the GPU.  Returns (argb int32 [H*W], avgError float32, iterations, w, h); zoom = 2 / 4: at the
     zoomed size (fic_decode_rgb_run_zoom)."""
     L = lib()
-    if zoom != 1:
-        return _decode_run_zoom(L.fic_decode_rgb_run_zoom, run, 20, "run stream", np.int32, device, avg_error_in, zoom)
-    L.fic_decode_rgb_run.restype = C.c_int
-    L.fic_decode_rgb_run.argtypes = [C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int64,
-                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    buf = np.frombuffer(bytes(run), np.uint8)
-    if buf.size < 20:
-        raise FicError(-3, "run stream shorter than its header")
-    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
-    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
-    cap = max(w, 0) * max(h, 0)
-    out = np.zeros(max(cap, 1), np.int32)
-    avg = C.c_float(avg_error_in)
-    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
-    check(L.fic_decode_rgb_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_int32), cap, C.byref(wo), C.byref(ho),
-                               C.byref(avg), C.byref(it)))
-    return out[:cap], np.float32(avg.value), it.value, w, h
+    return _decode_run(L.fic_decode_rgb_run, L.fic_decode_rgb_run_zoom, run, 20, "run stream", np.int32, device, avg_error_in, zoom)
 
 
 def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1, search="reference", lsq_engine="valu"):
@@ -429,31 +322,34 @@ def encode_rgb(argb, w, h, B, wK, device=0, want_collage=False, n_iso=1, search=
     return r
 
 
-class RgbEncoder:
-    """Handle API of the joint-RGB path (fic_rgb_ctx_*): `planes` colour images of one geometry, device resident.
-    n_iso = 8: the search tries the 8 isometries of every domain block; results()["iso"] holds the winners and decode()
-    paints through them."""
+class Handle:
+    """What the three handle classes of the C ABI do alike: Encoder and QuadtreeEncoder (host.py) and RgbEncoder
+    derive from it.  A subclass names its entries' prefix (fic_ctx / fic_rgb_ctx / fic_qt_ctx), creates the context and hands it
+    to _open; its encode calls the entries bound there.  A method whose entry the handle type does not have (the quadtree
+    handle has no sweep_time, sweep_stats, last_kernel, lsq_error) raises AttributeError."""
 
-    def __init__(self, width, height, B, wK, planes=1, device=0, n_iso=1):
+    PREFIX = None
+    _h = None
+    SWEEP_STATS_FIELDS = ("tiles", "flagged_tiles", "exact_pairs", "waves", "wave_cycles", "wave_ticks", "waves_sampled")
+
+    def _open(self, handle, *per_encode):
+        """Takes over the context `handle` (NULL: raises what the creator recorded) and binds, once, the entries an encode calls:
+        `per_encode` names them, `sync` comes with them."""
         L = lib()
-        self.width, self.height, self.B, self.wK, self.planes, self.device = width, height, B, wK, planes, device
-        self.n_iso = n_iso
-        Rw, Rh, Dw, Dh = geometry(width, height, B)
-        self.n_ranges = Rw * Rh
-        self._h = L.fic_rgb_ctx_create_iso(device, width, height, B, wK, n_iso, planes)
-        if not self._h:
+        if not handle:
             raise FicError(L.fic_last_error_code() or -3, last_error())
+        self._h = handle
+        self._keep = None                                  # the device tensor in use as input
+        self._sync = self._entry("sync")
+        return [self._entry(name) for name in per_encode]
+
+    def _entry(self, name):
+        return getattr(lib(), f"{self.PREFIX}_{name}")
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().fic_rgb_ctx_destroy(self._h)
+        if self._h:
+            self._entry("destroy")(self._h)
             self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def __del__(self):
         try:
@@ -461,72 +357,114 @@ class RgbEncoder:
         except Exception:
             pass
 
-    def set_argb(self, argb):
-        """int32 [planes, H*W] numpy array (copied) or a torch CUDA int32 tensor of that many elements (used in place and read
-        at encode time; one at an address that is no multiple of 4 is cloned here instead, as Encoder.set_gray does)."""
-        n = self.planes * self.width * self.height
-        if hasattr(argb, "data_ptr"):
-            if not argb.is_cuda or argb.element_size() != 4 or not argb.is_contiguous() or argb.numel() != n:
-                raise FicError(-3, "device input must be a contiguous int32 CUDA tensor [planes,H,W]")
-            argb = aligned_tensor(argb, 4)
-            check(lib().fic_rgb_ctx_set_argb_device(self._h, C.c_void_p(argb.data_ptr())))
-            self._keep = argb
-        else:
-            a = np.ascontiguousarray(argb, np.int32)
-            if a.size != n:
-                raise FicError(-3, "argb has the wrong number of pixels")
-            check(lib().fic_rgb_ctx_set_argb_host(self._h, ptr(a, C.c_int32)))
+    def __enter__(self):
+        return self
 
-    def encode(self, with_collage=False, stream=None):
-        s = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
-        check(lib().fic_rgb_ctx_encode(self._h, 1 if with_collage else 0, C.c_void_p(s)))
-        self._collage = bool(with_collage)
+    def __exit__(self, *a):
+        self.close()
 
-    def sync(self):
-        check(lib().fic_rgb_ctx_sync(self._h))
+    @staticmethod
+    def _stream(stream):
+        """`stream` (a raw hipStream_t handle / torch stream, None = default) as the entries take it."""
+        return C.c_void_p(0 if stream is None else int(getattr(stream, "cuda_stream", stream)))
+
+    def _set_device(self, t, itemsize, align, entry, what):
+        """A torch CUDA tensor of planes * H * W elements as the input, in place; one at an address that is no multiple of
+        `align` bytes is cloned here, once."""
+        n = self.planes * self.height * self.width
+        if not t.is_cuda or t.element_size() != itemsize or not t.is_contiguous() or t.numel() != n:
+            raise FicError(-3, f"device input must be a contiguous {what} CUDA tensor [planes,H,W]")
+        t = aligned_tensor(t, align)
+        check(self._entry(entry)(self._h, C.c_void_p(t.data_ptr())))
+        self._keep = t
 
     def set_option(self, name, value):
-        """"sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search.  "search": 0 / "reference" or 1 / "lsq" (least
-        squares; "sweep" then means 0 auto, 1 generic, 2 fast).  "lsq_tau_widen": 0 (off) or 8..24 --
-        diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value).  "lsq_engine": 0 / "valu"
-        or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_rgb_q, DESIGN.md 4.22: the same codebooks, B = 16 included);
-        "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times 2^-value); "time_sweep": 1
-        brackets the least-squares sweep launch with events (sweep_time)."""
+        """The handle's *_set_option.  "search" also takes "reference" / "lsq", "lsq_engine" also "valu" / "mfma"."""
         if name == "search":
             value = search_id(value)
         if name == "lsq_engine":
             value = lsq_engine_id(value)
             if isinstance(value, str):                       # other numbers: the library refuses them (FIC_E_ARGUMENT)
                 raise FicError(-3, f"lsq_engine must be 'valu', 'mfma', 0 or 1, not {value!r}")
-        check(lib().fic_rgb_ctx_set_option(self._h, name.encode(), int(value)))
+        check(self._entry("set_option")(self._h, name.encode(), int(value)))
 
-    def lsq_error(self):
-        """int64 [planes, N_r]: E of the winners of the last encode under set_option("search", "lsq") -- 10^6 times the squared
-        error of the quantised map over the three channels (fic_rgb_ctx_get_lsq_error_host)."""
-        E = np.zeros((self.planes, self.n_ranges), np.int64)
-        check(lib().fic_rgb_ctx_get_lsq_error_host(self._h, ptr(E, C.c_int64)))
-        return E
+    def sync(self):
+        check(self._sync(self._h))
 
-    def last_sweep(self):
-        return check(lib().fic_rgb_ctx_last_sweep(self._h))
+    def sweep_time(self, reset=True):
+        """(total ms, launches) of the sweep launches since the last reset (set_option("time_sweep", 1))."""
+        ms, n = C.c_double(), C.c_int()
+        check(self._entry("sweep_time")(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
+        return ms.value, n.value
+
+    def sweep_stats(self, reset=True):
+        """Counters of the matrix-core sweep (after set_option("sweep_stats", 1)): tile epilogues, flagged tiles, exact pairs,
+        waves, and of a sample of the waves the shader-clock cycles / 100 MHz ticks they lived."""
+        v = (C.c_uint64 * 8)()
+        check(self._entry("sweep_stats")(self._h, v, 1 if reset else 0))
+        return dict(zip(self.SWEEP_STATS_FIELDS, [int(x) for x in v]))
 
     def last_kernel(self):
         """Name of the sweep kernel the last encode launched, as rocprofv3 prints it (without the argument list)."""
         buf = C.create_string_buffer(96)
-        check(lib().fic_rgb_ctx_last_kernel(self._h, buf, 96))
+        check(self._entry("last_kernel")(self._h, buf, 96))
         return buf.value.decode()
 
-    def sweep_stats(self, reset=True):
-        """Counters of the matrix-core sweep (after set_option("sweep_stats", 1)), as Encoder.sweep_stats."""
-        v = (C.c_uint64 * 8)()
-        check(lib().fic_rgb_ctx_sweep_stats(self._h, v, 1 if reset else 0))
-        return dict(zip(["tiles", "flagged_tiles", "exact_pairs", "waves", "wave_cycles", "wave_ticks", "waves_sampled"], [int(x) for x in v]))
+    def lsq_error(self):
+        """int64 [planes, N_r]: E of the winners of the last encode under set_option("search", "lsq") -- the squared error of
+        the quantised map times 10^4 (grey, fic_ctx_get_lsq_error_host) or, over the three channels, times 10^6 (colour,
+        fic_rgb_ctx_get_lsq_error_host)."""
+        E = np.zeros((self.planes, self.n_ranges), np.int64)
+        check(self._entry("get_lsq_error_host")(self._h, ptr(E, C.c_int64)))
+        return E
 
-    def sweep_time(self, reset=True):
-        """(total ms, launches) of the least-squares sweep launches since the last reset (set_option("time_sweep", 1))."""
-        ms, n = C.c_double(), C.c_int()
-        check(lib().fic_rgb_ctx_sweep_time(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
-        return ms.value, n.value
+    def _debug_store(self, entry, names, which):
+        """Raw bytes (uint8 array) of store `which` of `names` through a *_debug_*_host entry: the size is asked first."""
+        fn, i = self._entry(entry), names.index(which)
+        size = C.c_int64()
+        check(fn(self._h, i, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        check(fn(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
+        return out
+
+
+class RgbEncoder(Handle):
+    """Handle API of the joint-RGB path (fic_rgb_ctx_*): `planes` colour images of one geometry, device resident.
+    n_iso = 8: the search tries the 8 isometries of every domain block; results()["iso"] holds the winners and decode()
+    paints through them.
+
+    Options (set_option): "sweep": 0 auto, 1 the VALU sweeps, 2 the matrix-core full search.  "search": 0 / "reference" or 1 / "lsq" (least
+    squares; "sweep" then means 0 auto, 1 generic, 2 fast).  "lsq_tau_widen": 0 (off) or 8..24 --
+    diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value).  "lsq_engine": 0 / "valu"
+    or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_rgb_q, DESIGN.md 4.22: the same codebooks, B = 16 included);
+    "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times 2^-value); "time_sweep": 1
+    brackets the least-squares sweep launch with events (sweep_time)."""
+
+    PREFIX = "fic_rgb_ctx"
+
+    def __init__(self, width, height, B, wK, planes=1, device=0, n_iso=1):
+        self.width, self.height, self.B, self.wK, self.planes, self.device = width, height, B, wK, planes, device
+        self.n_iso = n_iso
+        Rw, Rh, Dw, Dh = geometry(width, height, B)
+        self.n_ranges = Rw * Rh
+        self._encode, = self._open(lib().fic_rgb_ctx_create_iso(device, width, height, B, wK, n_iso, planes), "encode")
+
+    def set_argb(self, argb):
+        """int32 [planes, H*W] numpy array (copied) or a torch CUDA int32 tensor of that many elements (used in place and read
+        at encode time; one at an address that is no multiple of 4 is cloned here instead, as Encoder.set_gray does)."""
+        if hasattr(argb, "data_ptr"):
+            return self._set_device(argb, 4, 4, "set_argb_device", "int32")
+        a = np.ascontiguousarray(argb, np.int32)
+        if a.size != self.planes * self.width * self.height:
+            raise FicError(-3, "argb has the wrong number of pixels")
+        check(lib().fic_rgb_ctx_set_argb_host(self._h, ptr(a, C.c_int32)))
+
+    def encode(self, with_collage=False, stream=None):
+        check(self._encode(self._h, 1 if with_collage else 0, self._stream(stream)))
+        self._collage = bool(with_collage)
+
+    def last_sweep(self):
+        return check(lib().fic_rgb_ctx_last_sweep(self._h))
 
     def last_lsq_chunks(self):
         """Pool chunks of the last least-squares sweep (0: the last encode was none)."""
@@ -538,12 +476,7 @@ class RgbEncoder:
         """Raw bytes (uint8 array) of one store of k_lsq_rgb_q_prep after an encode through k_sweep_lsq_rgb_q ("lsq_engine" = 1):
         "A" / "B" the fragments, "Er" the per-range allowance (f32), "R" (u32) (fic_rgb_ctx_debug_lsq_q_host;
         tests/rgblsqqmodel.py decodes them)."""
-        i = self.LSQ_Q_STORES.index(which)
-        size = C.c_int64()
-        check(lib().fic_rgb_ctx_debug_lsq_q_host(self._h, i, None, 0, C.byref(size)))
-        out = np.zeros(size.value, np.uint8)
-        check(lib().fic_rgb_ctx_debug_lsq_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
-        return out
+        return self._debug_store("debug_lsq_q_host", self.LSQ_Q_STORES, which)
 
     Q_STORES = ("pool", "flat", "rng", "E", "rng_st", "amax")
 
@@ -551,12 +484,7 @@ class RgbEncoder:
         """Raw bytes (uint8 array) of one store of the matrix-core RGB sweep for the last plane encoded ("sweep" = 2):
         "pool" / "rng" the A / B fragments, "flat" the flat-tile flags, "E" the per-range error bounds, "rng_st" {0,
         varianzRange} per range, "amax" the largest domain-operand norm (fic_rgb_ctx_debug_q_host; tests/qmodel.py decodes them)."""
-        i = self.Q_STORES.index(which)
-        size = C.c_int64()
-        check(lib().fic_rgb_ctx_debug_q_host(self._h, i, None, 0, C.byref(size)))
-        out = np.zeros(size.value, np.uint8)
-        check(lib().fic_rgb_ctx_debug_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
-        return out
+        return self._debug_store("debug_q_host", self.Q_STORES, which)
 
     def results(self):
         P, N = self.planes, self.n_ranges
@@ -662,22 +590,10 @@ def write_run_quadtree(leaves, w, h, B_max, B_min, wK, n_iso):
 def decode_quadtree_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a quadtree stream on the GPU (fic_decode_quadtree_run).  Returns (gray uint8 [H,W], avgError float32 after the
     call, iterations).  zoom = 2 / 4: every leaf {x, y, B} painted as {zoom*x, zoom*y, zoom*B} (fic_decode_quadtree_run_zoom)."""
-    if zoom != 1:
-        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_quadtree_run_zoom, run, 32, "quadtree stream", np.uint8, device,
-                                              avg_error_in, zoom)
-        return out.reshape(h, w), avg, it
-    buf = np.frombuffer(bytes(run), np.uint8)
-    if buf.size < 32:
-        raise FicError(-3, "quadtree stream shorter than its header")
-    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
-    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
-    cap = max(w, 0) * max(h, 0)
-    out = np.zeros(max(cap, 1), np.uint8)
-    avg = C.c_float(avg_error_in)
-    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
-    check(lib().fic_decode_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_uint8), cap, C.byref(wo),
-                                        C.byref(ho), C.byref(avg), C.byref(it)))
-    return out[:cap].reshape(h, w), np.float32(avg.value), it.value
+    L = lib()
+    out, avg, it, w, h = _decode_run(L.fic_decode_quadtree_run, L.fic_decode_quadtree_run_zoom, run, 32, "quadtree stream", np.uint8, device,
+                                     avg_error_in, zoom)
+    return out.reshape(h, w), avg, it
 
 
 QT_RGB_LEAF_FIELDS = ("x", "y", "B", "idx_local", "q1", "q2", "q3", "q4")
@@ -732,22 +648,10 @@ def write_run_rgb_quadtree(leaves, w, h, B_max, B_min, wK):
 def decode_rgb_quadtree_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a colour quadtree stream on the GPU (fic_decode_rgb_quadtree_run).  Returns (argb int32 [H, W], avgError
     float32 after the call, iterations).  zoom = 2 / 4: at the zoomed size (fic_decode_rgb_quadtree_run_zoom)."""
-    if zoom != 1:
-        out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_rgb_quadtree_run_zoom, run, 32, "colour quadtree stream", np.int32,
-                                              device, avg_error_in, zoom)
-        return out.reshape(h, w), avg, it
-    buf = np.frombuffer(bytes(run), np.uint8)
-    if buf.size < 32:
-        raise FicError(-3, "colour quadtree stream shorter than its header")
-    w = int.from_bytes(bytes(run[4:8]), "big", signed=True)
-    h = int.from_bytes(bytes(run[8:12]), "big", signed=True)
-    cap = max(w, 0) * max(h, 0)
-    out = np.zeros(max(cap, 1), np.int32)
-    avg = C.c_float(avg_error_in)
-    it, wo, ho = C.c_int(), C.c_int(), C.c_int()
-    check(lib().fic_decode_rgb_quadtree_run(ptr(buf, C.c_uint8), buf.size, device, ptr(out, C.c_int32), cap, C.byref(wo),
-                                            C.byref(ho), C.byref(avg), C.byref(it)))
-    return out[:cap].reshape(h, w), np.float32(avg.value), it.value
+    L = lib()
+    out, avg, it, w, h = _decode_run(L.fic_decode_rgb_quadtree_run, L.fic_decode_rgb_quadtree_run_zoom, run, 32, "colour quadtree stream",
+                                     np.int32, device, avg_error_in, zoom)
+    return out.reshape(h, w), avg, it
 
 
 # ---- streams with an isometry column (DESIGN.md 4.17): tags 4 and 5 (fixed B), tag 6 (colour quadtree) --------------------------
@@ -777,14 +681,14 @@ def write_run_rgb_iso(qrows5, iso, w, h, B, wK):
 def decode_gray_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a tag-4 stream on the GPU (fic_decode_gray_iso_run): (gray uint8 [zoom*H, zoom*W], avgError float32 after the
     call, iterations)."""
-    out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_gray_iso_run, run, 24, "run stream", np.uint8, device, avg_error_in, zoom)
+    out, avg, it, w, h = _decode_run(None, lib().fic_decode_gray_iso_run, run, 24, "run stream", np.uint8, device, avg_error_in, zoom)
     return out.reshape(h, w), avg, it
 
 
 def decode_rgb_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a tag-5 stream on the GPU (fic_decode_rgb_iso_run): (argb int32 [zoom*H * zoom*W], avgError float32, iterations,
     zoom*w, zoom*h) like decode_rgb_run."""
-    return _decode_run_zoom(lib().fic_decode_rgb_iso_run, run, 24, "run stream", np.int32, device, avg_error_in, zoom)
+    return _decode_run(None, lib().fic_decode_rgb_iso_run, run, 24, "run stream", np.int32, device, avg_error_in, zoom)
 
 
 QT_RGB_ISO_LEAF_FIELDS = QT_RGB_LEAF_FIELDS + ("iso",)
@@ -830,8 +734,8 @@ def write_run_rgb_quadtree_iso(leaves, w, h, B_max, B_min, wK):
 def decode_rgb_quadtree_iso_run(run, device=0, avg_error_in=0.0, zoom=1):
     """Decoder of a tag-6 stream on the GPU (fic_decode_rgb_quadtree_iso_run): (argb int32 [zoom*H, zoom*W], avgError float32
     after the call, iterations)."""
-    out, avg, it, w, h = _decode_run_zoom(lib().fic_decode_rgb_quadtree_iso_run, run, 32, "colour quadtree stream", np.int32, device,
-                                          avg_error_in, zoom)
+    out, avg, it, w, h = _decode_run(None, lib().fic_decode_rgb_quadtree_iso_run, run, 32, "colour quadtree stream", np.int32, device,
+                                     avg_error_in, zoom)
     return out.reshape(h, w), avg, it
 
 

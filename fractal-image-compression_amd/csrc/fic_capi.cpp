@@ -229,7 +229,7 @@ int q_sweep(fic_ctx* c, int tile0, int tile1, hipStream_t s, int* nchunks_out, b
         if (rc) return rc;
     }
     if (fic_launch_sweep_q(c->b, c->q_pool, c->q_flat, c->q_rng, c->q_rngC, c->q_E, c->q_thg, g, ct_begin, ct_end, q.ndtiles, q.ndtiles_alloc,
-                           q.nct_alloc, tiles_per_chunk, nchunks, s, c->q_stats, c->opt_noflag, fused_fin ? &c->o : nullptr, c->q_fin,
+                           q.nct_alloc, tiles_per_chunk, nchunks, s, c->sweep_stats, c->opt_noflag, fused_fin ? &c->o : nullptr, c->q_fin,
                            r_begin, r_count))
         return fail(FIC_E_HIP, "k_sweep_q launch failed");
     *nchunks_out = nchunks;
@@ -278,8 +278,9 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     }
     int rc = c->mem.ensure_zeroed(c->lsq.pool, P * g.Nd_pad * 16, s);      // the tail the prefetch over-reads
     if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.rng, P * g.Nr_pad * 8);
-    if (rc == FIC_OK) rc = c->mem.ensure(c->lsq.E, P * g.Nr * 8);
+    if (rc == FIC_OK) rc = c->mem.ensure(c->lsq_E, P * g.Nr * 8);
     if (rc) return rc;
+    c->lsq.E = c->lsq_E;
     rc = grow_lsq_slots(c, c->lsq.slotE, c->lsq.slotC, (size_t)nslots, P * nslots * g.Nr_pad * 8, P * nslots * g.Nr_pad);
     if (rc) return rc;
     if (fic_launch_scale(c->b.gray, c->b.scaled, g, s)) return fail(FIC_E_HIP, "k_scale launch failed");
@@ -291,21 +292,22 @@ int lsq_encode(fic_ctx* c, int range_begin, int range_count, hipStream_t s)
     if (fic_launch_lsq_stat(c->b, c->lsq, g, s)) return fail(FIC_E_HIP, "k_lsq_stat launch failed");
     if (kind == 7) {                                   // fragment prep belongs to pool build / range prep: not timed
         const size_t NK = (size_t)g.n / 16;
-        rc = c->mem.ensure(c->lsqq.poolQ, P * c->lsqq.ndtiles * NK * 64 * 16);
-        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngQ, P * c->lsqq.nct_alloc * NK * 64 * 16);
-        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngE, P * g.Nr_pad * sizeof(float));
-        if (rc == FIC_OK) rc = c->mem.ensure(c->lsqq.rngR, P * g.Nr_pad * sizeof(uint32_t));
+        rc = c->mem.ensure(c->lsq_q[0], P * c->lsqq.ndtiles * NK * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsq_q[1], P * c->lsqq.nct_alloc * NK * 64 * 16);
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsq_q[2], P * g.Nr_pad * sizeof(float));
+        if (rc == FIC_OK) rc = c->mem.ensure(c->lsq_q[3], P * g.Nr_pad * sizeof(uint32_t));
         if (rc) return rc;
+        c->lsqq.poolQ = c->lsq_q[0], c->lsqq.rngQ = c->lsq_q[1], c->lsqq.rngE = c->lsq_q[2], c->lsqq.rngR = c->lsq_q[3];
         if (fic_launch_lsq_q_prep(c->b, c->lsq, c->lsqq, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_q_prep launch failed");
     }
     rc = c->timer.begin(s);
     if (rc) return rc;
     if (kind == 7) {
-        if (fic_launch_sweep_lsq_q(c->b, c->lsq, c->lsqq, g, ct_begin, ct_end, tiles_per_chunk, nchunks, s, c->q_stats, c->opt_lsq_widen))
+        if (fic_launch_sweep_lsq_q(c->b, c->lsq, c->lsqq, g, ct_begin, ct_end, tiles_per_chunk, nchunks, s, c->sweep_stats, c->opt_lsq_widen))
             return fail(FIC_E_HIP, "k_sweep_lsq_q launch failed");
     } else if (kind == 1) {
         if (fic_launch_sweep_lsq_generic(c->b, c->lsq, g, range_begin, range_count, s)) return fail(FIC_E_HIP, "k_sweep_lsq_generic launch failed");
-    } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->q_stats, c->opt_lsq_widen)) {
+    } else if (fic_launch_sweep_lsq_fast(c->b, c->lsq, g, tile0, ntiles, chunk_len, nchunks, s, c->sweep_stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_fast launch failed");
     }
     rc = c->timer.end(s);
@@ -420,13 +422,8 @@ int fic_ctx_set_gray_host(fic_ctx* c, const uint8_t* gray)
 {
     if (!c || !gray) return fail(FIC_E_ARGUMENT, "fic_ctx_set_gray_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    size_t bytes = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (int rc = c->mem.ensure(c->gray_own, bytes)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));   // a previous encode on a non-blocking stream may still read gray_own
-    HIP_TRY(hipMemcpy(c->gray_own, gray, bytes, hipMemcpyHostToDevice));
+    if (int rc = upload_input(c, c->gray_own, gray, (size_t)c->g.planes * c->g.W * c->g.H)) return rc;
     c->b.gray = c->gray_own;
-    c->have_input = true;
     return FIC_OK;
 }
 
@@ -434,16 +431,8 @@ int fic_ctx_set_argb_host(fic_ctx* c, const int32_t* argb)
 {
     if (!c || !argb) return fail(FIC_E_ARGUMENT, "fic_ctx_set_argb_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (int rc = c->mem.ensure(c->gray_own, npix)) return rc;
-    if (int rc = c->mem.ensure(c->argb_stage, npix)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(c->argb_stage, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (fic_launch_argb_to_gray(c->argb_stage, c->gray_own, npix, nullptr)) return fail(FIC_E_HIP, "k_argb_to_gray launch failed");
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (int rc = upload_argb_as_gray(c, c->argb_stage, c->gray_own, argb, (size_t)c->g.planes * c->g.W * c->g.H)) return rc;
     c->b.gray = c->gray_own;
-    c->have_input = true;
     return FIC_OK;
 }
 
@@ -452,8 +441,7 @@ int fic_ctx_set_gray_device(fic_ctx* c, const void* dev_gray)
     if (!c || !dev_gray) return fail(FIC_E_ARGUMENT, "fic_ctx_set_gray_device: null argument");
     // the range preps read the caller's bytes in words of up to 8 bytes (k_prep_q8 / k_range_q8: uint2 rows at B = 8); plane
     // and row offsets keep the base's alignment (W, H multiples of B >= 4; W a multiple of 8 wherever the 8-byte load runs)
-    if ((uintptr_t)dev_gray % 8 != 0)
-        return fail(FIC_E_ARGUMENT, "fic_ctx_set_gray_device: alignment: address %p is not a multiple of 8 bytes (the input in force stays)", dev_gray);
+    if (int rc = check_input_alignment("fic_ctx_set_gray_device", dev_gray, 8)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     c->b.gray = (uint8_t*)dev_gray;
     c->have_input = true;
@@ -643,60 +631,40 @@ int fic_ctx_collage_host(fic_ctx* c, int32_t* argb_out)
 int fic_ctx_set_option(fic_ctx* c, const char* name, int value)
 {
     if (!c || !name) return fail(FIC_E_ARGUMENT, "fic_ctx_set_option: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    // this handle's own options; every other name is the core's (fic_ctx_options.h)
     if (!strcmp(name, "sweep")) {
         if (c->opt_search == 1 && (value < 0 || value > 2))
             return fail(FIC_E_ARGUMENT, "sweep must be 0 (auto), 1 (generic) or 2 (fast) under the least-squares search (\"search\" = 1)");
         if (value < 0 || value > 6)
             return fail(FIC_E_ARGUMENT, "sweep must be 0 (auto), 1 (generic), 2 (fast, VALU), 3 (matrix-core, exact covariances), 4 (matrix-core, i8 operands), 5 (VALU, group-Fourier isometries) or 6 (matrix-core, normalised f16 prune GEMM)");
         c->opt_sweep = value;
-    } else if (!strcmp(name, "search")) {
-        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "search must be 0 (the reference's criterion) or 1 (least squares)");
-        if (value == 1 && c->opt_sweep > 2)
-            return fail(FIC_E_ARGUMENT, "the least-squares search (\"search\" = 1) has sweeps 0 (auto), 1 (generic) and 2 (fast), not %d", c->opt_sweep);
-        c->opt_search = value;
-    } else if (!strcmp(name, "chunks")) {
-        if (value < 0) return fail(FIC_E_ARGUMENT, "chunks must be >= 0");
-        c->opt_chunks = value;
-    } else if (!strcmp(name, "q_shape")) {             // MFMA shape of the 1-isometry k_sweep_q at B = 8 / 16 (tests, A/B runs)
+        return FIC_OK;
+    }
+    if (!strcmp(name, "q_shape")) {                    // MFMA shape of the 1-isometry k_sweep_q at B = 8 / 16 (tests, A/B runs)
         if (value < 0 || value > 2) return fail(FIC_E_ARGUMENT, "q_shape must be 0 (by pool size), 1 (16x16x32) or 2 (32x32x16)");
         c->g.q_shape = value;
-    } else if (!strcmp(name, "q_eshift")) {            // diagnostic: k_sweep_q's E_r times 2^-value (> 0: below the derivation, WRONG codebooks)
-        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "q_eshift must be in -12..4");
-        c->g.q_eshift = value;
-    } else if (!strcmp(name, "lsq_tau_widen")) {       // diagnostic: k_sweep_lsq_fast's tau times 1 + 2^-value (> 0: above the derivation, WRONG codebooks)
-        if (value != 0 && (value < 8 || value > 24)) return fail(FIC_E_ARGUMENT, "lsq_tau_widen must be 0 (off) or in 8..24");
-        c->opt_lsq_widen = value;
-    } else if (!strcmp(name, "lsq_engine")) {          // which sweep runs where k_sweep_lsq_fast would: 0 that one, 1 k_sweep_lsq_q (matrix cores)
-        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "lsq_engine must be 0 (VALU, k_sweep_lsq_fast) or 1 (matrix cores, k_sweep_lsq_q)");
-        c->opt_lsq_engine = value;
-    } else if (!strcmp(name, "lsq_q_eshift")) {        // diagnostic: k_sweep_lsq_q's Er times 2^-value (> 0: below the derivation, WRONG codebooks)
-        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "lsq_q_eshift must be in -12..4");
-        c->opt_lsq_q_eshift = value;
-    } else if (!strcmp(name, "q_noflag")) {            // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
-        c->opt_noflag = value ? 1 : 0;
-    } else if (!strcmp(name, "time_sweep")) {
-        c->timer.on = value ? 1 : 0;
-    } else if (!strcmp(name, "sweep_stats")) {
-        return sweep_stats_option(c, c->q_stats, value);
-    } else {
-        return fail(FIC_E_ARGUMENT, "unknown option '%s'", name);
+        return FIC_OK;
     }
-    return FIC_OK;
+    if (!strcmp(name, "q_noflag")) {                   // diagnostic: k_sweep_q without any flagged tile (wrong codebooks): its floor
+        c->opt_noflag = value ? 1 : 0;
+        return FIC_OK;
+    }
+    if (!strcmp(name, "search") && value == 1 && c->opt_sweep > 2)
+        return fail(FIC_E_ARGUMENT, "the least-squares search (\"search\" = 1) has sweeps 0 (auto), 1 (generic) and 2 (fast), not %d", c->opt_sweep);
+    return set_core_option(c, kOptGrey, "", name, value);
 }
 
 int fic_ctx_sweep_time(fic_ctx* c, double* total_ms, int* launches, int reset)
 {
     if (!c) return fail(FIC_E_ARGUMENT, "fic_ctx_sweep_time: null context");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    return c->timer.read(total_ms, launches, reset);
+    return ctx_sweep_time(c, total_ms, launches, reset);
 }
 
 int fic_ctx_sweep_stats(fic_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_ctx_sweep_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    return sweep_stats_read(c, "fic_ctx_sweep_stats", c->q_stats, out8, reset);
+    return ctx_sweep_stats(c, "fic_ctx_sweep_stats", out8, reset);
 }
 
 int fic_ctx_info(fic_ctx* c, int* out10)
@@ -797,30 +765,24 @@ int fic_ctx_debug_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int
 int fic_ctx_debug_lsq_q_host(fic_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
 {
     if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_ctx_debug_lsq_q_host: null argument");
-    if (!c->encoded_any || !c->lsqq.poolQ)
-        return fail(FIC_E_STATE, "fic_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
-    const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
-    return debug_store_host(c, "fic_ctx_debug_lsq_q_host", stores, 4, which, out, capacity, size);
+    return ctx_debug_lsq_q(c, "fic_ctx_debug_lsq_q_host", which, out, capacity, size);
 }
 
 }  // extern "C"
 
 int ficd::encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device,
-                          int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows)
+                          int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows, int64_t* E, int search)
 {
-    if ((!gray && !argb) || !idx_local || !a || !b) return fail(FIC_E_ARGUMENT, "fic_encode_gray: null argument");
+    if ((!gray && !argb) || !idx_local || !a || !b) return fail(FIC_E_ARGUMENT, "%s: null argument", search ? "fic_encode_gray_lsq" : "fic_encode_gray");
     // The GUI calls encode once per slider move with the same geometry (CTL:125-145): keep the last few
     // working sets instead of paying ~18 device allocations and frees per call.
-    fic_ctx* c = g_idle_grey.take(device, w, h, B, wK, n_iso);
-    if (!c) c = fic_ctx_create(device, w, h, B, wK, n_iso, 1);
-    if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_ctx_create recorded why
-    int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
-    if (rc == FIC_OK) rc = fic_ctx_encode(c, 0, -1, nullptr);
-    if (rc == FIC_OK) rc = fic_ctx_get_results_host(c, idx_local, a, b, iso, qrows, nullptr, nullptr);
-    ErrKeep keep;
-    if (rc == FIC_OK) g_idle_grey.give(c);
-    else fic_ctx_destroy(c);
-    return rc;
+    Lease<fic_ctx> L;
+    int rc = L.open(device, w, h, B, wK, n_iso, search);
+    if (rc == FIC_OK) rc = gray ? fic_ctx_set_gray_host(L.c, gray) : fic_ctx_set_argb_host(L.c, argb);
+    if (rc == FIC_OK) rc = fic_ctx_encode(L.c, 0, -1, nullptr);
+    if (rc == FIC_OK) rc = fic_ctx_get_results_host(L.c, idx_local, a, b, iso, qrows, nullptr, nullptr);
+    if (rc == FIC_OK && E) rc = fic_ctx_get_lsq_error_host(L.c, E);
+    return L.close(rc);
 }
 
 extern "C" {

@@ -25,7 +25,6 @@ struct fic_qt_ctx : ficd::CtxCore {
     int next_slot = 0;
     uint8_t* gray_own = nullptr;         // a host input's device copy (grey), the staging of an ARGB upload to a grey context
     int32_t* argb_own = nullptr;
-    int opt_search = 0;
     template <typename T>
     T* at(QtArea a) const { return (T*)(store + plan.a[a].off); }
 };
@@ -174,11 +173,7 @@ int fic_qt_ctx_set_gray_host(fic_qt_ctx* c, const uint8_t* gray)
     if (!c || !gray) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_host: null argument");
     if (c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_host: a colour context takes ARGB input");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->planes * c->g.W * c->g.H;
-    if (int rc = c->mem.ensure(c->gray_own, bytes)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));     // an earlier encode may still read the copy
-    HIP_TRY(hipMemcpy(c->gray_own, gray, bytes, hipMemcpyHostToDevice));
+    if (int rc = upload_input(c, c->gray_own, gray, (size_t)c->planes * c->g.W * c->g.H)) return rc;
     return qt_ctx_input(c, c->gray_own);
 }
 
@@ -186,25 +181,17 @@ int fic_qt_ctx_set_argb_host(fic_qt_ctx* c, const int32_t* argb)
 {
     if (!c || !argb) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
     const size_t npix = (size_t)c->planes * c->g.W * c->g.H;
-    if (int rc = c->mem.ensure(c->argb_own, npix)) return rc;
-    if (!c->colour)
-        if (int rc = c->mem.ensure(c->gray_own, npix)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(c->argb_own, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (c->colour) return qt_ctx_input(c, c->argb_own);
-    if (fic_launch_argb_to_gray(c->argb_own, c->gray_own, npix, nullptr)) return fail(FIC_E_HIP, "k_argb_to_gray launch failed");
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return qt_ctx_input(c, c->gray_own);
+    if (int rc = c->colour ? upload_input(c, c->argb_own, argb, npix) : upload_argb_as_gray(c, c->argb_own, c->gray_own, argb, npix)) return rc;
+    return qt_ctx_input(c, c->colour ? (const void*)c->argb_own : (const void*)c->gray_own);
 }
 
 int fic_qt_ctx_set_gray_device(fic_qt_ctx* c, const void* dev_gray)
 {
     if (!c || !dev_gray) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: null argument");
     if (c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: a colour context takes ARGB input");
-    if ((uintptr_t)dev_gray % 8 != 0)                  // fic_ctx_set_gray_device's rule, refused here before any level has taken the pointer
-        return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_gray_device: alignment: address %p is not a multiple of 8 bytes (the input in force stays)", dev_gray);
+    // fic_ctx_set_gray_device's rule, refused here before any level has taken the pointer
+    if (int rc = check_input_alignment("fic_qt_ctx_set_gray_device", dev_gray, 8)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     return qt_ctx_input(c, dev_gray);
 }
@@ -213,8 +200,7 @@ int fic_qt_ctx_set_argb_device(fic_qt_ctx* c, const void* dev_argb)
 {
     if (!c || !dev_argb) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: null argument");
     if (!c->colour) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: a grey context takes device input as bytes (fic_qt_ctx_set_gray_device)");
-    if ((uintptr_t)dev_argb % 4 != 0)
-        return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_argb_device: alignment: address %p is not a multiple of 4 bytes (the input in force stays)", dev_argb);
+    if (int rc = check_input_alignment("fic_qt_ctx_set_argb_device", dev_argb, 4)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     return qt_ctx_input(c, dev_argb);
 }
@@ -223,12 +209,7 @@ int fic_qt_ctx_set_option(fic_qt_ctx* c, const char* name, int value)
 {
     if (!c || !name) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!strcmp(name, "search")) {
-        if (value < 0 || value > 1) return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: search must be 0 (the reference's criterion) or 1 (least squares)");
-        c->opt_search = value;
-        return FIC_OK;
-    }
-    return fail(FIC_E_ARGUMENT, "fic_qt_ctx_set_option: unknown option '%s'", name);
+    return set_core_option(c, kOptQt, "fic_qt_ctx_set_option: ", name, value);     // "search": the levels get it at encode time
 }
 
 int fic_qt_ctx_encode_threshold(fic_qt_ctx* c, const float* thresholds, void* hip_stream)

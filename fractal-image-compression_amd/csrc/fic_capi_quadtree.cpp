@@ -85,23 +85,11 @@ struct QtGreyHost : QtGrey {
     using Ctx = fic_ctx;
     static constexpr const QtFormat& kStream = kQtGreyStream;
     static constexpr const DecodeKind& kDecode = kDecodeGrey;
-    static Ctx* take(int device, const FicGeom& g)
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb)   // exactly the one-shot encode of this level
     {
-        Ctx* c = g_idle_grey.take(device, g.W, g.H, g.B, g.wK, g.n_iso);
-        return c ? c : fic_ctx_create(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
+        const int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
+        return rc ? rc : fic_ctx_encode(c, 0, -1, nullptr);
     }
-    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int search)   // exactly the one-shot encode of this level
-    {
-        int rc = gray ? fic_ctx_set_gray_host(c, gray) : fic_ctx_set_argb_host(c, argb);
-        if (rc || !search) return rc ? rc : fic_ctx_encode(c, 0, -1, nullptr);
-        // least squares: the cached context goes back in the reference's mode whatever happens
-        rc = fic_ctx_set_option(c, "search", search);
-        if (rc == FIC_OK) rc = fic_ctx_encode(c, 0, -1, nullptr);
-        ErrKeep keep;
-        (void)fic_ctx_set_option(c, "search", 0);
-        return rc;
-    }
-    static void give(Ctx* c, bool ok) { ok ? g_idle_grey.give(c) : fic_ctx_destroy(c); }
     // every level reads the top context's scaled copy, made here: the original, 2:1 scaled (FC:970-1007)
     static int prepare(Ctx* top) { return fic_launch_scale(top->b.gray, top->b.scaled, top->g, nullptr); }
     static QtViews<Px> views(const Ctx* c, const Ctx* top) { return {c->b.gray, top->b.scaled, c->o.qrows, c->g.n_iso > 1 ? c->o.iso : nullptr}; }
@@ -113,23 +101,11 @@ struct QtRgbHost : QtRgb {
     using Ctx = fic_rgb_ctx;
     static constexpr const QtFormat& kStream = kQtRgbStream;
     static constexpr const DecodeKind& kDecode = kDecodeRgb;
-    static Ctx* take(int device, const FicGeom& g)
+    static int encode(Ctx* c, const uint8_t*, const int32_t* argb)   // exactly the one-shot RGB encode of this level (n_iso = 1)
     {
-        Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, 1);
-        return c ? c : fic_rgb_ctx_create(device, g.W, g.H, g.B, g.wK, 1);
+        const int rc = fic_rgb_ctx_set_argb_host(c, argb);
+        return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
     }
-    static int encode(Ctx* c, const uint8_t*, const int32_t* argb, int search = 0)   // exactly the one-shot RGB encode of this level
-    {
-        int rc = fic_rgb_ctx_set_argb_host(c, argb);
-        if (rc || !search) return rc ? rc : fic_rgb_ctx_encode(c, 0, nullptr);
-        // least squares: the cached context goes back in the reference's mode whatever happens
-        rc = fic_rgb_ctx_set_option(c, "search", search);
-        if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c, 0, nullptr);
-        ErrKeep keep;
-        (void)fic_rgb_ctx_set_option(c, "search", 0);
-        return rc;
-    }
-    static void give(Ctx* c, bool ok) { ok ? g_idle_rgb.give(c) : fic_rgb_ctx_destroy(c); }
     static int prepare(Ctx*) { return 0; }
     // every level reads its own scaleImageRGB copy, made by its encode (image 0 of the context)
     static QtViews<Px> views(const Ctx* c, const Ctx*) { return {c->argb, c->scaled, c->qrows, nullptr}; }
@@ -143,13 +119,7 @@ struct QtRgbIsoHost : QtRgbIso {
     using Ctx = fic_rgb_ctx;
     static constexpr const QtFormat& kStream = kQtRgbIsoStream;
     static constexpr const DecodeKind& kDecode = kDecodeRgb;
-    static Ctx* take(int device, const FicGeom& g)
-    {
-        Ctx* c = g_idle_rgb.take(device, g.W, g.H, g.B, g.wK, g.n_iso);
-        return c ? c : fic_rgb_ctx_create_iso(device, g.W, g.H, g.B, g.wK, g.n_iso, 1);
-    }
-    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb, int search = 0) { return QtRgbHost::encode(c, gray, argb, search); }   // = fic_encode_rgb_iso_argb's / _lsq_argb's
-    static void give(Ctx* c, bool ok) { QtRgbHost::give(c, ok); }
+    static int encode(Ctx* c, const uint8_t* gray, const int32_t* argb) { return QtRgbHost::encode(c, gray, argb); }   // = fic_encode_rgb_iso_argb's / _lsq_argb's
     static int prepare(Ctx*) { return 0; }
     static QtViews<Px> views(const Ctx* c, const Ctx*) { return {c->argb, c->scaled, c->qrows, c->iso}; }   // iso NULL on n_iso = 1: the identity
     static int scale(const Px* image, Px* scaled, const FicGeom& g) { return fic_launch_scale_rgb(image, scaled, g, nullptr); }
@@ -206,13 +176,16 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
     rc = check_device(device);
     if (rc) return rc;
 
+    // one lease per level, under `search` for the call (least squares: DESIGN.md 4.19 / 4.20): parked again after success only
+    Lease<typename Fmt::Ctx> lease[kQtMaxLevels];
     typename Fmt::Ctx* c[kQtMaxLevels] = {nullptr, nullptr, nullptr};
     DevMem mem(device);              // the store of this call: freed on every way out
     char* store = nullptr;
     for (int l = 0; l < L.nl && rc == FIC_OK; l++) {
-        c[l] = Fmt::take(device, L.g[l]);
-        if (!c[l]) { rc = g_err_code ? g_err_code : FIC_E_HIP; break; }
-        rc = Fmt::encode(c[l], gray, argb, search);
+        const FicGeom& g = L.g[l];
+        rc = lease[l].open(device, g.W, g.H, g.B, g.wK, g.n_iso, search);
+        c[l] = lease[l].c;
+        if (rc == FIC_OK) rc = Fmt::encode(c[l], gray, argb);
     }
     if (rc == FIC_OK) rc = mem.alloc(store, Q.total);
     if (rc == FIC_OK && Fmt::prepare(c[0])) rc = fail(FIC_E_HIP, "k_scale launch failed");
@@ -271,9 +244,7 @@ int qt_encode(const uint8_t* gray, const int32_t* argb, int w, int h, int B_max,
         hipError_t e = hipMemcpy(sse_out, store + Q.a[kQtSse].off, sse_total * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(FIC_E_HIP, "%s SSE: %s", Fmt::kStream.kind, hipGetErrorString(e));
     }
-    ErrKeep keep;
-    for (int l = 0; l < L.nl; l++)
-        if (c[l]) Fmt::give(c[l], rc == FIC_OK);
+    for (Lease<typename Fmt::Ctx>& l : lease) l.close(rc);
     return rc;
 }
 

@@ -130,21 +130,15 @@ int fic_rgb_ctx_set_argb_host(fic_rgb_ctx* c, const int32_t* argb)
 {
     if (!c || !argb) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_argb_host: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->g.planes * c->g.W * c->g.H;
-    if (int rc = c->mem.ensure(c->argb_own, npix)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->last_stream));     // an earlier encode may still read the copy
-    HIP_TRY(hipMemcpy(c->argb_own, argb, npix * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = upload_input(c, c->argb_own, argb, (size_t)c->g.planes * c->g.W * c->g.H)) return rc;
     c->argb = c->argb_own;
-    c->have_input = true;
     return FIC_OK;
 }
 
 int fic_rgb_ctx_set_argb_device(fic_rgb_ctx* c, const void* dev_argb)
 {
     if (!c || !dev_argb) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_argb_device: null argument");
-    if ((uintptr_t)dev_argb % 4 != 0)                  // every kernel loads the pixels as int32_t, none wider
-        return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_argb_device: alignment: address %p is not a multiple of 4 bytes (the input in force stays)", dev_argb);
+    if (int rc = check_input_alignment("fic_rgb_ctx_set_argb_device", dev_argb, 4)) return rc;   // every kernel loads the pixels as int32_t, none wider
     std::lock_guard<std::mutex> lk(c->mu);
     c->argb = (const int32_t*)dev_argb;
     c->have_input = true;
@@ -198,47 +192,11 @@ int fic_rgb_ctx_set_option(fic_rgb_ctx* c, const char* name, int value)
         c->opt_sweep = value;
         return FIC_OK;
     }
-    if (!strcmp(name, "search")) {                     // 0: the reference's criterion, 1: least squares; "sweep" then
-        if (value < 0 || value > 1)                    // means 0 (auto), 1 (generic), 2 (fast): the same three values either way
-            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: search must be 0 (the reference's criterion) or 1 (least squares)");
-        c->opt_search = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "chunks")) {
-        if (value < 0) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: chunks must be >= 0");
-        c->opt_chunks = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "q_eshift")) {                   // diagnostic: the matrix-core sweep's E_r times 2^-value (> 0: WRONG codebooks)
-        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: q_eshift must be in -12..4");
-        c->g.q_eshift = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "lsq_tau_widen")) {              // diagnostic: k_sweep_lsq_rgb_fast's tau times 1 + 2^-value (> 0: WRONG codebooks)
-        if (value != 0 && (value < 8 || value > 24))
-            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_tau_widen must be 0 (off) or in 8..24");
-        c->opt_lsq_widen = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "lsq_engine")) {                 // which sweep a full least-squares search runs: 0 VALU, 1 k_sweep_lsq_rgb_q (matrix cores)
-        if (value < 0 || value > 1)
-            return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_engine must be 0 (VALU sweeps) or 1 (matrix cores, k_sweep_lsq_rgb_q)");
-        c->opt_lsq_engine = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "lsq_q_eshift")) {               // diagnostic: k_sweep_lsq_rgb_q's Er times 2^-value (> 0: below the derivation, WRONG codebooks)
-        if (value < -12 || value > 4) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: lsq_q_eshift must be in -12..4");
-        c->opt_lsq_q_eshift = value;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "time_sweep")) {                 // event pairs around the least-squares sweep launch (fic_rgb_ctx_sweep_time)
-        c->timer.on = value ? 1 : 0;
-        return FIC_OK;
-    }
-    if (!strcmp(name, "sweep_stats")) {                // test hook: counters of the matrix-core sweep (fic_rgb_ctx_sweep_stats)
-        return sweep_stats_option(c, c->q.stats, value);
-    }
-    return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_set_option: unknown option '%s'", name);
+    // the core's options (fic_ctx_options.h).  Under "search" = 1 "sweep" means 0 (auto), 1 (generic), 2 (fast):
+    // the same three values either way
+    const int rc = set_core_option(c, kOptRgb, "fic_rgb_ctx_set_option: ", name, value);
+    c->q.stats = c->sweep_stats;                       // the launchers' view of the "sweep_stats" counters
+    return rc;
 }
 
 int fic_rgb_ctx_debug_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
@@ -261,8 +219,7 @@ int fic_rgb_ctx_last_sweep(fic_rgb_ctx* c)
 int fic_rgb_ctx_sweep_stats(fic_rgb_ctx* c, uint64_t* out8, int reset)
 {
     if (!c || !out8) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    return sweep_stats_read(c, "fic_rgb_ctx_sweep_stats", c->q.stats, out8, reset);
+    return ctx_sweep_stats(c, "fic_rgb_ctx_sweep_stats", out8, reset);
 }
 
 int fic_rgb_ctx_last_kernel(fic_rgb_ctx* c, char* out, int capacity)
@@ -376,10 +333,6 @@ int fic_rgb_ctx_decode_host(fic_rgb_ctx* c, int32_t* argb_out, float* avg_error_
     return fic_rgb_ctx_decode_zoom_host(c, 1, argb_out, avg_error_out, iterations_out);
 }
 
-}  // extern "C"
-
-extern "C" {
-
 int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK, int device, int32_t* idx_local, float* a,
                         float* bR, float* bG, float* bB, int32_t* qrows5, int32_t* collage_argb)
 {
@@ -387,23 +340,37 @@ int fic_encode_rgb_argb(const int32_t* argb, int w, int h, int B, int wK, int de
     return fic_encode_rgb_iso_argb(argb, w, h, B, wK, 1, device, idx_local, a, bR, bG, bB, nullptr, qrows5, collage_argb);
 }
 
+}  // extern "C"
+
+// the one-shot joint-RGB encode behind fic_encode_rgb_iso_argb (search 0) and fic_encode_rgb_lsq_argb (search 1, with E)
+static int rgb_oneshot(const char* entry, int search, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local,
+                       float* a, float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb, int64_t* E)
+{
+    if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "%s: null argument", entry);
+    if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso);
+    // the GUI re-encodes the same image on every slider move (CTL:125-145): keep the last few working sets
+    Lease<fic_rgb_ctx> L;
+    int rc = L.open(device, w, h, B, wK, n_iso, search);
+    if (rc == FIC_OK) rc = fic_rgb_ctx_set_argb_host(L.c, argb);
+    if (rc == FIC_OK) rc = fic_rgb_ctx_encode(L.c, collage_argb ? 1 : 0, nullptr);
+    if (rc == FIC_OK) rc = fic_rgb_ctx_get_results_host(L.c, idx_local, a, bR, bG, bB, qrows5, collage_argb);
+    if (rc == FIC_OK && iso) rc = fic_rgb_ctx_get_iso_host(L.c, iso);
+    if (rc == FIC_OK && E) rc = fic_rgb_ctx_get_lsq_error_host(L.c, E);
+    return L.close(rc);
+}
+
+extern "C" {
+
 int fic_encode_rgb_iso_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local, float* a,
                             float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb)
 {
-    if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_iso_argb: null argument");
-    if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso);
-    // the GUI re-encodes the same image on every slider move (CTL:125-145): keep the last few working sets
-    fic_rgb_ctx* c = g_idle_rgb.take(device, w, h, B, wK, n_iso);
-    if (!c) c = fic_rgb_ctx_create_iso(device, w, h, B, wK, n_iso, 1);
-    if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_rgb_ctx_create recorded why
-    int rc = fic_rgb_ctx_set_argb_host(c, argb);
-    if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c, collage_argb ? 1 : 0, nullptr);
-    if (rc == FIC_OK) rc = fic_rgb_ctx_get_results_host(c, idx_local, a, bR, bG, bB, qrows5, collage_argb);
-    if (rc == FIC_OK && iso) rc = fic_rgb_ctx_get_iso_host(c, iso);
-    ErrKeep keep;
-    if (rc == FIC_OK) g_idle_rgb.give(c);
-    else fic_rgb_ctx_destroy(c);
-    return rc;
+    return rgb_oneshot("fic_encode_rgb_iso_argb", 0, argb, w, h, B, wK, n_iso, device, idx_local, a, bR, bG, bB, iso, qrows5, collage_argb, nullptr);
+}
+
+int fic_encode_rgb_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local, float* a,
+                            float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb, int64_t* E)
+{
+    return rgb_oneshot("fic_encode_rgb_lsq_argb", 1, argb, w, h, B, wK, n_iso, device, idx_local, a, bR, bG, bB, iso, qrows5, collage_argb, E);
 }
 
 }  // extern "C"

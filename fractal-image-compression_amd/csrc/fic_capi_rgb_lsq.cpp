@@ -1,6 +1,6 @@
 // fic_capi_rgb_lsq.cpp -- C ABI of the least-squares domain search of the joint-RGB path: the encode
-// of a colour context under "search" = 1 (kernels in fic_lsq_rgb.hip), the winners' errors and the one-shot entry over the
-// cached contexts.  The quadtree entries are in fic_capi_quadtree.cpp.  Host-side orchestration only.
+// of a colour context under "search" = 1 (kernels in fic_lsq_rgb.hip) and the winners' errors.  The one-shot entry is
+// fic_capi_rgb.cpp's on a lease under "search" = 1; the quadtree entries are in fic_capi_quadtree.cpp.  Host-side orchestration only.
 #include "fic_internal.h"
 #include "fic_lsq_q_chunks.h"
 #include "fic_sweep_chunks.h"
@@ -48,8 +48,9 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s)
     if (rc == FIC_OK) rc = m.ensure_zeroed(q.pool_st, P * g.Nd_pad * 32, s);
     if (rc == FIC_OK) rc = m.ensure_zeroed(q.rng3, P * nrp * g.n_iso * 3 * g.n, s);      // the lanes past N_r of the last tile read zeros
     if (rc == FIC_OK) rc = m.ensure_zeroed(q.rng_st, P * nrp * 16, s);
-    if (rc == FIC_OK) rc = m.ensure(q.E, P * g.Nr * 8);
+    if (rc == FIC_OK) rc = m.ensure(c->lsq_E, P * g.Nr * 8);
     if (rc) return rc;
+    q.E = c->lsq_E;
     rc = grow_lsq_slots(c, q.slotE, q.slotC, (size_t)nslots, P * nslots * nrp * 8, P * nslots * nrp);
     if (rc) return rc;
     FicRgbOutputs o;                                   // image 0 of the batch: the kernels take the image from their grid
@@ -60,21 +61,22 @@ int ficd::rgb_lsq_encode(fic_rgb_ctx* c, int with_collage, hipStream_t s)
     if (kind == 7) {                                   // fragment prep belongs to the stores: not timed
         const size_t NK = 3 * (size_t)g.n / 16;
         FicLsqRgbQ& f = c->lsqq;
-        rc = m.ensure(f.poolQ, P * f.ndtiles * NK * 64 * 16);
-        if (rc == FIC_OK) rc = m.ensure(f.rngQ, P * f.nct * NK * 64 * 16);
-        if (rc == FIC_OK) rc = m.ensure(f.rngE, P * nrp * sizeof(float));
-        if (rc == FIC_OK) rc = m.ensure(f.rngR, P * nrp * sizeof(uint32_t));
+        rc = m.ensure(c->lsq_q[0], P * f.ndtiles * NK * 64 * 16);
+        if (rc == FIC_OK) rc = m.ensure(c->lsq_q[1], P * f.nct * NK * 64 * 16);
+        if (rc == FIC_OK) rc = m.ensure(c->lsq_q[2], P * nrp * sizeof(float));
+        if (rc == FIC_OK) rc = m.ensure(c->lsq_q[3], P * nrp * sizeof(uint32_t));
         if (rc) return rc;
+        f.poolQ = c->lsq_q[0], f.rngQ = c->lsq_q[1], f.rngE = c->lsq_q[2], f.rngR = c->lsq_q[3];
         if (fic_launch_lsq_rgb_q_prep(q, f, g, c->opt_lsq_q_eshift, s)) return fail(FIC_E_HIP, "k_lsq_rgb_q_prep launch failed");
     }
     rc = c->timer.begin(s);
     if (rc) return rc;
     if (kind == 7) {
-        if (fic_launch_sweep_lsq_rgb_q(q, c->lsqq, g, plan.tiles_per_chunk, plan.nchunks, s, c->q.stats, c->opt_lsq_widen))
+        if (fic_launch_sweep_lsq_rgb_q(q, c->lsqq, g, plan.tiles_per_chunk, plan.nchunks, s, c->sweep_stats, c->opt_lsq_widen))
             return fail(FIC_E_HIP, "k_sweep_lsq_rgb_q launch failed");
     } else if (kind == 1) {
         if (fic_launch_sweep_lsq_rgb_generic(q, g, s)) return fail(FIC_E_HIP, "k_sweep_lsq_rgb_generic launch failed");
-    } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->q.stats, c->opt_lsq_widen)) {
+    } else if (fic_launch_sweep_lsq_rgb_fast(q, g, chunk_len, nchunks, s, c->sweep_stats, c->opt_lsq_widen)) {
         return fail(FIC_E_HIP, "k_sweep_lsq_rgb_fast launch failed");
     }
     rc = c->timer.end(s);
@@ -95,22 +97,13 @@ extern "C" {
 int fic_rgb_ctx_get_lsq_error_host(fic_rgb_ctx* c, int64_t* E)
 {
     if (!c || !E) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_get_lsq_error_host: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->encoded_any || c->last_search != 1 || !c->lsq.E)
-        return fail(FIC_E_STATE, "fic_rgb_ctx_get_lsq_error_host: the last encode was not a least-squares search (\"search\" = 1)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    static_assert(sizeof(long long) == sizeof(int64_t), "E");
-    HIP_TRY(hipMemcpy(E, c->lsq.E, (size_t)c->g.planes * c->g.Nr * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return FIC_OK;
+    return ctx_get_lsq_error(c, "fic_rgb_ctx_get_lsq_error_host", E);
 }
 
 int fic_rgb_ctx_sweep_time(fic_rgb_ctx* c, double* total_ms, int* launches, int reset)
 {
     if (!c) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_sweep_time: null context");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    return c->timer.read(total_ms, launches, reset);
+    return ctx_sweep_time(c, total_ms, launches, reset);
 }
 
 int fic_rgb_ctx_last_lsq_chunks(fic_rgb_ctx* c)
@@ -122,32 +115,7 @@ int fic_rgb_ctx_last_lsq_chunks(fic_rgb_ctx* c)
 int fic_rgb_ctx_debug_lsq_q_host(fic_rgb_ctx* c, int which, void* out, int64_t capacity, int64_t* size)
 {
     if (!c || !size) return fail(FIC_E_ARGUMENT, "fic_rgb_ctx_debug_lsq_q_host: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->encoded_any || !c->lsqq.poolQ)
-        return fail(FIC_E_STATE, "fic_rgb_ctx_debug_lsq_q_host: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet");
-    const void* const stores[4] = {c->lsqq.poolQ, c->lsqq.rngQ, c->lsqq.rngE, c->lsqq.rngR};
-    return debug_store_host(c, "fic_rgb_ctx_debug_lsq_q_host", stores, 4, which, out, capacity, size);
-}
-
-int fic_encode_rgb_lsq_argb(const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device, int32_t* idx_local, float* a,
-                            float* bR, float* bG, float* bB, int32_t* iso, int32_t* qrows5, int32_t* collage_argb, int64_t* E)
-{
-    if (!argb || !idx_local || !a || !bR || !bG || !bB) return fail(FIC_E_ARGUMENT, "fic_encode_rgb_lsq_argb: null argument");
-    if (n_iso != 1 && n_iso != 8) return fail(FIC_E_ARGUMENT, "n_iso=%d: the joint-RGB path has 1 or 8 isometries", n_iso);
-    fic_rgb_ctx* c = g_idle_rgb.take(device, w, h, B, wK, n_iso);
-    if (!c) c = fic_rgb_ctx_create_iso(device, w, h, B, wK, n_iso, 1);
-    if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // fic_rgb_ctx_create_iso recorded why
-    int rc = fic_rgb_ctx_set_option(c, "search", 1);
-    if (rc == FIC_OK) rc = fic_rgb_ctx_set_argb_host(c, argb);
-    if (rc == FIC_OK) rc = fic_rgb_ctx_encode(c, collage_argb ? 1 : 0, nullptr);
-    if (rc == FIC_OK) rc = fic_rgb_ctx_get_results_host(c, idx_local, a, bR, bG, bB, qrows5, collage_argb);
-    if (rc == FIC_OK && iso) rc = fic_rgb_ctx_get_iso_host(c, iso);
-    if (rc == FIC_OK && E) rc = fic_rgb_ctx_get_lsq_error_host(c, E);
-    ErrKeep keep;
-    // the cached contexts serve the reference entries too: never parked in least-squares mode
-    if (rc == FIC_OK && fic_rgb_ctx_set_option(c, "search", 0) == FIC_OK) g_idle_rgb.give(c);
-    else fic_rgb_ctx_destroy(c);
-    return rc;
+    return ctx_debug_lsq_q(c, "fic_rgb_ctx_debug_lsq_q_host", which, out, capacity, size);
 }
 
 }  // extern "C"

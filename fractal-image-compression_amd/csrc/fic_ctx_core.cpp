@@ -1,6 +1,7 @@
-// fic_ctx_core.cpp -- what fic_ctx and fic_rgb_ctx do alike, over the core they share (ficd::CtxCore, fic_internal.h): the
-// stream rule, the sweep timer, the growth of the least-squares slot stores, the read-out of a debug store, the sync entry and
-// the "sweep_stats" counter block.  Host-side orchestration only.
+// fic_ctx_core.cpp -- what fic_ctx, fic_rgb_ctx and fic_qt_ctx do alike, over the core they share (ficd::CtxCore,
+// fic_internal.h), once: the stream rule, the sweep timer, the growth of the least-squares slot stores, the read-out of a debug
+// store, the sync entry, the shared options (their rules: fic_ctx_options.h) with the "sweep_stats" counter block, the getters
+// that differ only in the handle type, and the upload of a host input.  Host-side orchestration only.
 #include "fic_internal.h"
 
 namespace ficd {
@@ -100,31 +101,103 @@ int debug_store_host(CtxCore* c, const char* who, const void* const* stores, int
     return FIC_OK;
 }
 
-int sweep_stats_option(CtxCore* c, unsigned long long*& stats, int on)
+// "sweep_stats": the counter block is switched on (zeroed) or off
+static int sweep_stats_option(CtxCore* c, int on)
 {
     HIP_TRY(hipSetDevice(c->device));
-    if (on && !stats) {
-        int rc = c->mem.ensure_zeroed(stats, 8, nullptr);
+    if (on && !c->sweep_stats) {
+        int rc = c->mem.ensure_zeroed(c->sweep_stats, 8, nullptr);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));            // the fill is only enqueued (null stream); sweeps run on other streams
-    } else if (!on && stats) {
+    } else if (!on && c->sweep_stats) {
         HIP_TRY(hipStreamSynchronize(c->last_stream));
-        c->mem.release(stats);
+        c->mem.release(c->sweep_stats);
     }
     return FIC_OK;
 }
 
-int sweep_stats_read(CtxCore* c, const char* who, unsigned long long* stats, uint64_t* out8, int reset)
+int set_core_option(CtxCore* c, int handle, const char* prefix, const char* name, int value)
 {
-    if (!stats) return fail(FIC_E_STATE, "%s: set the option \"sweep_stats\" first", who);
+    const OptionRule* r = find_option(name, handle);
+    if (!r) return fail(FIC_E_ARGUMENT, "%sunknown option '%s'", prefix, name);
+    if (!option_value_ok(*r, value)) return fail(FIC_E_ARGUMENT, "%s%s %s", prefix, r->name, r->must);
+    switch (r->id) {
+    case kOptSearch: c->opt_search = value; break;
+    case kOptChunks: c->opt_chunks = value; break;
+    case kOptQEshift: c->g.q_eshift = value; break;
+    case kOptLsqTauWiden: c->opt_lsq_widen = value; break;
+    case kOptLsqEngine: c->opt_lsq_engine = value; break;
+    case kOptLsqQEshift: c->opt_lsq_q_eshift = value; break;
+    case kOptTimeSweep: c->timer.on = value ? 1 : 0; break;
+    case kOptSweepStats: return sweep_stats_option(c, value);
+    }
+    return FIC_OK;
+}
+
+int ctx_get_lsq_error(CtxCore* c, const char* who, int64_t* E)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any || c->last_search != 1 || !c->lsq_E)
+        return fail(FIC_E_STATE, "%s: the last encode was not a least-squares search (\"search\" = 1)", who);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out8, stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    static_assert(sizeof(long long) == sizeof(int64_t), "E");
+    HIP_TRY(hipMemcpy(E, c->lsq_E, (size_t)c->g.planes * c->g.Nr * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return FIC_OK;
+}
+
+int ctx_sweep_time(CtxCore* c, double* total_ms, int* launches, int reset)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    return c->timer.read(total_ms, launches, reset);
+}
+
+int ctx_sweep_stats(CtxCore* c, const char* who, uint64_t* out8, int reset)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->sweep_stats) return fail(FIC_E_STATE, "%s: set the option \"sweep_stats\" first", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    HIP_TRY(hipMemcpy(out8, c->sweep_stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (reset) {
-        HIP_TRY(hipMemset(stats, 0, 8 * sizeof(uint64_t)));
+        HIP_TRY(hipMemset(c->sweep_stats, 0, 8 * sizeof(uint64_t)));
         HIP_TRY(hipStreamSynchronize(nullptr));
     }
     return FIC_OK;
+}
+
+int ctx_debug_lsq_q(CtxCore* c, const char* who, int which, void* out, int64_t capacity, int64_t* size)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->encoded_any || !c->lsq_q[0])
+        return fail(FIC_E_STATE, "%s: no encode through the matrix-core least-squares sweep (\"lsq_engine\" = 1) yet", who);
+    return debug_store_host(c, who, c->lsq_q, 4, which, out, capacity, size);
+}
+
+int upload_bytes(CtxCore* c, void* own, const void* host, size_t bytes)
+{
+    HIP_TRY(hipStreamSynchronize(c->last_stream));     // an earlier encode on a non-blocking stream may still read the copy
+    HIP_TRY(hipMemcpy(own, host, bytes, hipMemcpyHostToDevice));
+    return FIC_OK;
+}
+
+int upload_argb_as_gray(CtxCore* c, int32_t*& stage, uint8_t*& gray_own, const int32_t* argb, size_t npix)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = c->mem.ensure(gray_own, npix)) return rc;
+    if (int rc = c->mem.ensure(stage, npix)) return rc;
+    if (int rc = upload_bytes(c, stage, argb, npix * sizeof(int32_t))) return rc;
+    if (fic_launch_argb_to_gray(stage, gray_own, npix, nullptr)) return fail(FIC_E_HIP, "k_argb_to_gray launch failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    c->have_input = true;
+    return FIC_OK;
+}
+
+int check_input_alignment(const char* entry, const void* dev, int align)
+{
+    if ((uintptr_t)dev % (uintptr_t)align == 0) return FIC_OK;
+    return fail(FIC_E_ARGUMENT, "%s: alignment: address %p is not a multiple of %d bytes (the input in force stays)", entry, dev, align);
 }
 
 }  // namespace ficd

@@ -1,5 +1,6 @@
-// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the two context types and the
-// core they share (fic_ctx_core.cpp), the idle-context caches of the one-shot entries, the "sweep_stats" counter block, the decode job and the release hooks; error
+// fic_internal.h -- shared by the translation units of the C ABI that call HIP (fic_capi*.cpp): the context types and the core
+// they share (fic_ctx_core.cpp: stream rule, options, host input, the getters that differ only in the handle type), the
+// idle-context caches of the one-shot entries and the lease on them, the decode job and the release hooks; error
 // reporting, geometry validation and the stream formats come with fic_stream.h, the ownership of device memory with
 // fic_devmem.h (the HIP runtime's allocation calls are made in fic_devmem.cpp and nowhere else).  Not part of the public
 // interface.
@@ -21,6 +22,7 @@
 #include "fic_stream.h"
 #include "fic_devmem.h"
 #include "fic_qt_batch_plan.h"
+#include "fic_ctx_options.h"
 
 struct fic_rgb_ctx;
 
@@ -47,7 +49,7 @@ int check_device(int device);
 bool create_device_ok(int device);
 
 int encode_oneshot(const uint8_t* gray, const int32_t* argb, int w, int h, int B, int wK, int n_iso, int device,
-                   int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows);
+                   int32_t* idx_local, float* a, float* b, int32_t* iso, int32_t* qrows, int64_t* E = nullptr, int search = 0);
 
 // "time_sweep": event pairs bracket the sweep launch on its stream and are read later (fic_*_ctx_sweep_time).
 struct SweepTimer {
@@ -61,8 +63,8 @@ struct SweepTimer {
     int read(double* total_ms, int* launches, int reset);
 };
 
-// What a context is apart from its pixels: fic_ctx and fic_rgb_ctx derive from it, the helpers below (fic_ctx_core.cpp) are
-// written once for both.
+// What a context is apart from its pixels: fic_ctx, fic_rgb_ctx and fic_qt_ctx derive from it, the helpers below
+// (fic_ctx_core.cpp) are written once for all of them.
 struct CtxCore {
     int device = 0;
     FicGeom g;
@@ -73,6 +75,16 @@ struct CtxCore {
     bool stream_used = false;        // an encode was issued on last_stream (take_stream orders a stream switch after it)
     SweepTimer timer;
     size_t lsq_slots = 0;            // slots per plane the least-squares slot stores have room for
+    // the shared options (fic_ctx_options.h; "q_eshift" is g.q_eshift, "time_sweep" timer.on) and what the last encode ran
+    int opt_search = 0, last_search = 0;
+    int opt_chunks = 0;              // pool chunks of the sweep (0 = automatic)
+    int opt_lsq_widen = 0;           // "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
+    int opt_lsq_engine = 0;          // "lsq_engine": 1 the matrix-core least-squares sweep wherever the fast VALU one would run
+    int opt_lsq_q_eshift = 0;        // "lsq_q_eshift" (-12..4): diagnostic, that sweep's Er times 2^-value; > 0 gives WRONG codebooks
+    unsigned long long* sweep_stats = nullptr;   // "sweep_stats" = 1: 8 u64 device counters of the matrix-core sweeps
+    // stores of a least-squares search the shared getters read; a context's FicLsq* / FicLsq*Q structs view them for the launchers
+    void* lsq_E = nullptr;           // the winners' E, i64 [planes][Nr]
+    void* lsq_q[4] = {};             // "lsq_engine" = 1: poolQ, rngQ, rngE, rngR
     ~CtxCore();                      // the pending events; the memory goes with `mem`
 };
 
@@ -88,10 +100,31 @@ int ctx_sync(CtxCore* c);
 int grow_lsq_slots(CtxCore* c, void*& slotE, uint32_t*& slotC, size_t nslots, size_t sizeE, size_t sizeC);
 // The fic_*_debug_*_host entries behind their own preconditions: store `which` of `stores` exactly as the owner holds it
 int debug_store_host(CtxCore* c, const char* who, const void* const* stores, int nstores, int which, void* out, int64_t capacity, int64_t* size);
-// The "sweep_stats" counter block of either context: 8 u64 device counters of k_sweep_q, held by the context's owner.  The
-// option switches it on (zeroed) or off; the read entry copies it out and may reset it.
-int sweep_stats_option(CtxCore* c, unsigned long long*& stats, int on);
-int sweep_stats_read(CtxCore* c, const char* who, unsigned long long* stats, uint64_t* out8, int reset);
+// One of the shared options (fic_ctx_options.h) of handle kind `handle` (OptHandle): range check and effect; a name the table
+// does not list for that handle is the unknown option.  `prefix` opens every message ("" for the grey entry).  The caller
+// holds c->mu.
+int set_core_option(CtxCore* c, int handle, const char* prefix, const char* name, int value);
+// The getters that differ only in the handle type, behind the entry's null check (`who`: the entry's name); they take c->mu.
+int ctx_get_lsq_error(CtxCore* c, const char* who, int64_t* E);
+int ctx_sweep_time(CtxCore* c, double* total_ms, int* launches, int reset);
+int ctx_sweep_stats(CtxCore* c, const char* who, uint64_t* out8, int reset);
+int ctx_debug_lsq_q(CtxCore* c, const char* who, int which, void* out, int64_t capacity, int64_t* size);
+// Host input: upload_input ensures the context's copy `own`, waits until last_stream no longer reads it, copies `count`
+// elements from `host` (upload_bytes) and sets have_input; upload_argb_as_gray does the same for an ARGB image's red channel,
+// through the staging copy `stage` and k_argb_to_gray on the null stream.  The caller holds c->mu.
+int upload_bytes(CtxCore* c, void* own, const void* host, size_t bytes);
+int upload_argb_as_gray(CtxCore* c, int32_t*& stage, uint8_t*& gray_own, const int32_t* argb, size_t npix);
+template <typename T>
+int upload_input(CtxCore* c, T*& own, const T* host, size_t count)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = c->mem.ensure(own, count)) return rc;
+    if (int rc = upload_bytes(c, own, host, count * sizeof(T))) return rc;
+    c->have_input = true;
+    return FIC_OK;
+}
+// Device input: FIC_OK, or the refusal of an address that is no multiple of `align` bytes (nothing of the context has changed)
+int check_input_alignment(const char* entry, const void* dev, int align);
 
 
 // device arena of a decode (fic_capi_decode.cpp): one allocation kept between calls, taken and given back by a DecodeJob
@@ -194,17 +227,12 @@ struct fic_ctx : ficd::CtxCore {
     void* q_E = nullptr;
     void* q_thg = nullptr;
     unsigned int* q_fin = nullptr;           // fused finalise of small launches: finished workgroups per (plane, column group)
-    unsigned long long* q_stats = nullptr;   // "sweep_stats" = 1: device counters of k_sweep_q (fic_ctx_sweep_stats)
     uint32_t* d4_rng = nullptr;      // k_sweep_d4: range / domain slots of the group-Fourier form (n_iso = 8, B = 8 / 16)
     uint32_t* d4_pool = nullptr;
     FicLsq lsq{};                    // least-squares search ("search" = 1): statistics, per-chunk slots, the winners' E (on first use)
-    int opt_search = 0, last_search = 0;
-    int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
-    FicLsqQ lsqq{};                  // the matrix-core least-squares sweep ("lsq_engine" = 1): fragments, Er, R (on first use)
-    int opt_lsq_engine = 0;          // option "lsq_engine": 0 k_sweep_lsq_fast, 1 k_sweep_lsq_q wherever the former would run
-    int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, k_sweep_lsq_q's Er times 2^-value; > 0 gives WRONG codebooks
+    FicLsqQ lsqq{};                  // the matrix-core least-squares sweep k_sweep_lsq_q ("lsq_engine" = 1): fragments, Er, R (on first use)
     hipStream_t own_stream = nullptr; // non-blocking stream of the multi-device entry (created on demand)
-    int opt_sweep = 0, opt_chunks = 0, opt_noflag = 0;
+    int opt_sweep = 0, opt_noflag = 0;
     int last_chunks = 0, last_kind = 0, last_fused = 0, last_tiles_per_chunk = 0;
     ~fic_ctx();                      // the own stream (fic_capi.cpp)
 };
@@ -231,15 +259,10 @@ struct fic_rgb_ctx : ficd::CtxCore {
     uint32_t* dec_sq = nullptr;
     FicRgbQ q;                       // matrix-core full search (allocated on first use; one image at a time, stream-ordered)
     int opt_sweep = 0;               // 0 auto, 1 VALU sweeps, 2 matrix-core full search
-    int opt_chunks = 0;              // pool chunks of the matrix-core sweep (0 = automatic)
     int last_sweep = 0;              // what the last encode ran: 1 / 2
     FicLsqRgb lsq;                   // least-squares search ("search" = 1): byte stores, sums, per-chunk slots, the winners' E (on first use)
-    int opt_search = 0, last_search = 0;
-    int opt_lsq_widen = 0;           // option "lsq_tau_widen" (0 or 8..24): diagnostic, > 0 gives WRONG codebooks
     int last_lsq_kind = 0;           // the least-squares sweep the last encode ran: 1 generic, 2 fast, 7 matrix cores (k_sweep_lsq_rgb_q)
-    FicLsqRgbQ lsqq{};               // the matrix-core least-squares sweep ("lsq_engine" = 1): fragments, Er, R (on first use)
-    int opt_lsq_engine = 0;          // option "lsq_engine": 0 the VALU sweeps, 1 k_sweep_lsq_rgb_q where the full-search sweep would run
-    int opt_lsq_q_eshift = 0;        // option "lsq_q_eshift" (-12..4): diagnostic, that sweep's Er times 2^-value; > 0 gives WRONG codebooks
+    FicLsqRgbQ lsqq{};               // the matrix-core least-squares sweep k_sweep_lsq_rgb_q ("lsq_engine" = 1): fragments, Er, R (on first use)
     int last_lsq_chunks = 0;         // pool chunks of the last least-squares sweep
     bool have_collage = false;
 };
@@ -295,5 +318,47 @@ private:
 };
 extern IdleCache<fic_ctx, 16> g_idle_grey;       // fic_capi.cpp
 extern IdleCache<fic_rgb_ctx, 4> g_idle_rgb;     // fic_capi_rgb.cpp
+inline IdleCache<fic_ctx, 16>& idle_cache(fic_ctx*) { return g_idle_grey; }
+inline IdleCache<fic_rgb_ctx, 4>& idle_cache(fic_rgb_ctx*) { return g_idle_rgb; }
+inline fic_ctx* create_ctx(fic_ctx*, int device, int w, int h, int B, int wK, int n_iso) { return fic_ctx_create(device, w, h, B, wK, n_iso, 1); }
+inline fic_rgb_ctx* create_ctx(fic_rgb_ctx*, int device, int w, int h, int B, int wK, int n_iso) { return fic_rgb_ctx_create_iso(device, w, h, B, wK, n_iso, 1); }
+
+// The lease of a one-shot entry on a single-image context: open() takes an idle one of the geometry or creates it, and may put
+// it under "search" = 1 for the call.  close(rc) ends it: the context is back in the reference's mode -- the cached contexts
+// serve the reference entries too -- and goes to the cache if rc is FIC_OK, else it is destroyed, as is one whose lease goes out
+// of scope open.  The calling thread's error stays what it was across that clean-up.
+template <typename Ctx>
+class Lease {
+public:
+    Ctx* c = nullptr;
+    Lease() = default;
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    int open(int device, int w, int h, int B, int wK, int n_iso, int search = 0)
+    {
+        c = idle_cache(c).take(device, w, h, B, wK, n_iso);
+        if (!c) c = create_ctx(c, device, w, h, B, wK, n_iso);
+        if (!c) return g_err_code ? g_err_code : FIC_E_HIP;   // the creator recorded why
+        c->opt_search = search;
+        return FIC_OK;
+    }
+    int close(int rc)                // ends the lease with what the entry returns: the context is kept after success only
+    {
+        finish(rc == FIC_OK);
+        return rc;
+    }
+    ~Lease() { finish(false); }
+
+private:
+    void finish(bool ok)
+    {
+        if (!c) return;
+        ErrKeep keep;
+        c->opt_search = 0;
+        if (ok) idle_cache(c).give(c);
+        else destroy_ctx(c);
+        c = nullptr;
+    }
+};
 
 }  // namespace ficd

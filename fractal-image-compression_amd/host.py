@@ -47,10 +47,18 @@ class _DevArray:
                                          "version": 2, "strides": None}
 
 
-class Encoder:
+class Encoder(capi.Handle):
     """Handle API (fic_ctx_*): the working set for `planes` grey images of one geometry on one
     device.  Inputs may be numpy arrays (copied to the device) or torch CUDA tensors (used in
-    place: this is what bench.py times)."""
+    place: this is what bench.py times).
+
+    Options (set_option, fic_ctx_set_option): "search" also takes "reference" / "lsq" (least squares).
+    "lsq_tau_widen": 0 (off) or 8..24 -- diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times
+    1 + 2^-value).  "lsq_engine": 0 / "valu" (k_sweep_lsq_fast) or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_q, DESIGN.md
+    4.21: the same codebooks); "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times
+    2^-value)."""
+
+    PREFIX = "fic_ctx"
 
     def __init__(self, width, height, B, wK=None, n_iso=1, planes=1, device=0):
         L = capi.lib()
@@ -63,49 +71,21 @@ class Encoder:
         self.wK = wK
         self.Rw, self.Rh, self.Dw, self.Dh = Rw, Rh, Dw, Dh
         self.n_ranges, self.n_domains = Rw * Rh, Dw * Dh
-        self._h = L.fic_ctx_create(device, width, height, B, wK, n_iso, planes)
-        if not self._h:
-            raise FicError(L.fic_last_error_code() or -3, capi.last_error())
-        self._keep = None
-        info = (C.c_int * 10)()
-        capi.check(L.fic_ctx_info(self._h, info))
-        self.ranges_per_tile = 64 * info[6]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.lib().fic_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        self._encode, = self._open(L.fic_ctx_create(device, width, height, B, wK, n_iso, planes), "encode")
+        self.ranges_per_tile = 64 * self.info()["NR"]
 
     # ---- input -----------------------------------------------------------------------------
     def set_gray(self, gray):
         """gray: uint8 [planes,H,W] / [H,W] numpy array (copied), or a torch CUDA uint8 tensor of that shape.  A tensor whose
         address is a multiple of 8 is used in place and read by every later encode, at encode time; any other one (a view at
         an odd offset) is cloned here, once, into a fresh allocation: later writes to it are not seen."""
-        L = capi.lib()
-        n = self.planes * self.height * self.width
         if hasattr(gray, "data_ptr"):                                  # torch tensor, device resident
-            if not gray.is_cuda or gray.dtype.itemsize != 1 or not gray.is_contiguous() or gray.numel() != n:
-                raise FicError(-3, "device input must be a contiguous uint8 CUDA tensor [planes,H,W]")
-            gray = capi.aligned_tensor(gray, 8)
-            capi.check(L.fic_ctx_set_gray_device(self._h, C.c_void_p(gray.data_ptr())))
-            self._keep = gray
-        else:
-            g = np.ascontiguousarray(gray, np.uint8)
-            if g.size != n:
-                raise FicError(-3, f"input has {g.size} pixels, expected {n}")
-            capi.check(L.fic_ctx_set_gray_host(self._h, capi.ptr(g, C.c_uint8)))
+            return self._set_device(gray, 1, 8, "set_gray_device", "uint8")
+        g = np.ascontiguousarray(gray, np.uint8)
+        n = self.planes * self.height * self.width
+        if g.size != n:
+            raise FicError(-3, f"input has {g.size} pixels, expected {n}")
+        capi.check(capi.lib().fic_ctx_set_gray_host(self._h, capi.ptr(g, C.c_uint8)))
 
     def set_argb(self, argb):
         a = np.ascontiguousarray(argb, np.int32)
@@ -114,53 +94,16 @@ class Encoder:
         capi.check(capi.lib().fic_ctx_set_argb_host(self._h, capi.ptr(a, C.c_int32)))
 
     # ---- compute ---------------------------------------------------------------------------
-    def set_option(self, name, value):
-        """fic_ctx_set_option.  "search" also takes "reference" / "lsq" (least squares).  "lsq_tau_widen": 0
-        (off) or 8..24 -- diagnostic, > 0 gives WRONG codebooks (the fast least-squares sweep's bound times 1 + 2^-value).
-        "lsq_engine": 0 / "valu" (k_sweep_lsq_fast) or 1 / "mfma" (the matrix-core sweep k_sweep_lsq_q, DESIGN.md 4.21: the same
-        codebooks); "lsq_q_eshift": -12..4, diagnostic, > 0 gives WRONG codebooks (that sweep's allowance times 2^-value)."""
-        if name == "search":
-            value = capi.search_id(value)
-        if name == "lsq_engine":
-            value = capi.lsq_engine_id(value)
-            if isinstance(value, str):
-                raise FicError(-3, f"lsq_engine must be 'valu', 'mfma', 0 or 1, not {value!r}")
-        capi.check(capi.lib().fic_ctx_set_option(self._h, name.encode(), int(value)))
-
-    def lsq_error(self):
-        """int64 [planes, N_r]: E of the winners of the last encode under set_option("search", "lsq") -- 10^4 times the squared
-        error of the quantised map (fic_ctx_get_lsq_error_host)."""
-        E = np.zeros((self.planes, self.n_ranges), np.int64)
-        capi.check(capi.lib().fic_ctx_get_lsq_error_host(self._h, capi.ptr(E, C.c_int64)))
-        return E
-
     def encode(self, range_begin=0, range_count=-1, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle / torch stream, None = default)."""
-        s = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))
-        capi.check(capi.lib().fic_ctx_encode(self._h, range_begin, range_count, C.c_void_p(s)))
-
-    def sync(self):
-        capi.check(capi.lib().fic_ctx_sync(self._h))
-
-    def sweep_time(self, reset=True):
-        ms, n = C.c_double(), C.c_int()
-        capi.check(capi.lib().fic_ctx_sweep_time(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
-        return ms.value, n.value
+        capi.check(self._encode(self._h, range_begin, range_count, self._stream(stream)))
 
     def sweep_stats(self, reset=True):
         """k_sweep_q counters (after set_option("sweep_stats", 1)): tile epilogues, flagged tiles, exact pairs, waves,
         and of a sample of the waves the shader-clock cycles / 100 MHz ticks they lived (`clock_ghz` = their ratio)."""
-        v = (C.c_uint64 * 8)()
-        capi.check(capi.lib().fic_ctx_sweep_stats(self._h, v, 1 if reset else 0))
-        d = dict(zip(["tiles", "flagged_tiles", "exact_pairs", "waves", "wave_cycles", "wave_ticks", "waves_sampled"], [int(x) for x in v]))
+        d = super().sweep_stats(reset)
         d["clock_ghz"] = d["wave_cycles"] / d["wave_ticks"] / 10.0 if d["wave_ticks"] else None
         return d
-
-    def last_kernel(self):
-        """Name of the sweep kernel the last encode launched, as rocprofv3 prints it (without the argument list)."""
-        buf = C.create_string_buffer(96)
-        capi.check(capi.lib().fic_ctx_last_kernel(self._h, buf, 96))
-        return buf.value.decode()
 
     def info(self):
         v = (C.c_int * 10)()
@@ -245,98 +188,55 @@ class Encoder:
     def debug_lsq_q(self, which):
         """Raw bytes (uint8 array) of one store of k_lsq_q_prep after an encode through k_sweep_lsq_q ("lsq_engine" = 1): "A" /
         "B" the fragments, "Er" the per-range allowance (f32), "R" (u32) (fic_ctx_debug_lsq_q_host; tests/lsqqmodel.py decodes them)."""
-        i = self.LSQ_Q_STORES.index(which)
-        size = C.c_int64()
-        capi.check(capi.lib().fic_ctx_debug_lsq_q_host(self._h, i, None, 0, C.byref(size)))
-        out = np.zeros(size.value, np.uint8)
-        capi.check(capi.lib().fic_ctx_debug_lsq_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
-        return out
+        return self._debug_store("debug_lsq_q_host", self.LSQ_Q_STORES, which)
 
     def debug_q(self, which):
         """Raw bytes (uint8 array) of one store of k_sweep_q after an encode through it ("sweep" = 6): "pool" / "rng" the
         A / B fragments, "flat" the flat-tile flags, "E" the per-range error bounds, "rng_st" {rM, rem} per range, "rngC" the
         columns' copies as bytes (fic_ctx_debug_q_host; tests/qmodel.py decodes them)."""
-        i = self.Q_STORES.index(which)
-        size = C.c_int64()
-        capi.check(capi.lib().fic_ctx_debug_q_host(self._h, i, None, 0, C.byref(size)))
-        out = np.zeros(size.value, np.uint8)
-        capi.check(capi.lib().fic_ctx_debug_q_host(self._h, i, out.ctypes.data_as(C.c_void_p), out.size, C.byref(size)))
-        return out
+        return self._debug_store("debug_q_host", self.Q_STORES, which)
 
 
-class QuadtreeEncoder:
+class QuadtreeEncoder(capi.Handle):
     """Handle API of the quadtree codec (fic_qt_ctx_*): `planes` images of one geometry, every split rule, device
     resident and asynchronous like Encoder.  colour=False: grey, leaf rows of 7 ints (write_run_quadtree); colour=True: joint RGB
     with the isometry column, rows of 9 ints (write_run_rgb_quadtree_iso), n_iso 1 or 8.  wK = 0: full search at every level.
-    Plane p's results are those of the one-shot entry (encode_gray_quadtree*, encode_rgb_quadtree_iso*) on image p."""
+    Plane p's results are those of the one-shot entry (encode_gray_quadtree*, encode_rgb_quadtree_iso*) on image p.
+    set_option: "search", "reference" / 0 or "lsq" / 1, the criterion of the per-level codebooks."""
+
+    PREFIX = "fic_qt_ctx"
 
     def __init__(self, width, height, B_max, B_min, wK=0, n_iso=1, planes=1, colour=False, device=0):
-        L = capi.lib()
         self.width, self.height, self.B_max, self.B_min, self.wK, self.n_iso = width, height, B_max, B_min, wK, n_iso
         self.planes, self.colour, self.device = planes, bool(colour), device
         self.cols = 9 if colour else 7
         self.tag = 6 if colour else 2
-        self._keep = None
-        self._h = L.fic_qt_ctx_create(device, 1 if colour else 0, width, height, B_max, B_min, wK, n_iso, planes)
-        if not self._h:
-            raise FicError(L.fic_last_error_code() or -3, capi.last_error())
+        h = capi.lib().fic_qt_ctx_create(device, 1 if colour else 0, width, height, B_max, B_min, wK, n_iso, planes)
+        self._encode_threshold, self._encode_budget, self._encode_rd = self._open(h, "encode_threshold", "encode_budget", "encode_rd")
         self.max_leaves = (width // B_min) * (height // B_min)      # rows per plane of the device leaf table
 
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.lib().fic_qt_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # ---- input -----------------------------------------------------------------------------
-    def _set_device(self, t, itemsize, align, fn, what):
-        n = self.planes * self.height * self.width
-        if not t.is_cuda or t.element_size() != itemsize or not t.is_contiguous() or t.numel() != n:
-            raise FicError(-3, f"device input must be a contiguous {what} CUDA tensor [planes,H,W]")
-        t = capi.aligned_tensor(t, align)
-        capi.check(fn(self._h, C.c_void_p(t.data_ptr())))
-        self._keep = t
-
     def set_gray(self, gray):
         """A grey context's input: uint8 [planes,H,W] numpy array (uploaded once), or a torch CUDA uint8 tensor, used in place
         and read at encode time exactly as Encoder.set_gray's (a misaligned view is cloned here, once)."""
-        L = capi.lib()
         if hasattr(gray, "data_ptr"):
-            return self._set_device(gray, 1, 8, L.fic_qt_ctx_set_gray_device, "uint8")
+            return self._set_device(gray, 1, 8, "set_gray_device", "uint8")
         g = np.ascontiguousarray(gray, np.uint8)
         if g.size != self.planes * self.height * self.width:
             raise FicError(-3, f"input has {g.size} pixels, expected {self.planes * self.height * self.width}")
-        capi.check(L.fic_qt_ctx_set_gray_host(self._h, capi.ptr(g, C.c_uint8)))
+        capi.check(capi.lib().fic_qt_ctx_set_gray_host(self._h, capi.ptr(g, C.c_uint8)))
 
     def set_argb(self, argb):
         """int32 ARGB [planes,H,W]: a numpy array (either kind of context; a grey one takes the red channel, as Encoder.set_argb),
         or for a colour context a torch CUDA int32 tensor, used in place as RgbEncoder.set_argb's."""
-        L = capi.lib()
         if hasattr(argb, "data_ptr"):
-            return self._set_device(argb, 4, 4, L.fic_qt_ctx_set_argb_device, "int32")
+            return self._set_device(argb, 4, 4, "set_argb_device", "int32")
         a = np.ascontiguousarray(argb, np.int32)
         if a.size != self.planes * self.height * self.width:
             raise FicError(-3, "argb has the wrong number of pixels")
-        capi.check(L.fic_qt_ctx_set_argb_host(self._h, capi.ptr(a, C.c_int32)))
+        capi.check(capi.lib().fic_qt_ctx_set_argb_host(self._h, capi.ptr(a, C.c_int32)))
 
     # ---- compute ---------------------------------------------------------------------------
-    def set_option(self, name, value):
-        """"search": "reference" / 0 or "lsq" / 1, the criterion of the per-level codebooks."""
-        if name == "search":
-            value = capi.search_id(value)
-        capi.check(capi.lib().fic_qt_ctx_set_option(self._h, name.encode(), int(value)))
-
     def _per_plane(self, v, dtype):
         a = np.asarray(v)
         if a.ndim == 0:
@@ -350,15 +250,14 @@ class QuadtreeEncoder:
         scalar for all planes or one per plane: threshold= (the fixed-threshold rule), lam= / max_sse= (rate-distortion pruning,
         DESIGN.md 4.23), max_leaves= / max_bytes= (a stream of the context's format) reached by pruning (prune="rd") or by
         the threshold rule (prune="threshold", DESIGN.md 4.18: the reference criterion only)."""
-        L = capi.lib()
         if sum(v is not None for v in (threshold, max_leaves, max_bytes, lam, max_sse)) != 1:
             raise ValueError("pass exactly one of threshold=, max_leaves=, max_bytes=, lam= and max_sse=")
         if prune not in ("rd", "threshold"):
             raise ValueError("prune must be 'rd' or 'threshold'")
-        s = C.c_void_p(0 if stream is None else int(getattr(stream, "cuda_stream", stream)))
+        s = self._stream(stream)
         if threshold is not None:
             t = self._per_plane(threshold, np.float32)
-            capi.check(L.fic_qt_ctx_encode_threshold(self._h, capi.ptr(t, C.c_float), s))
+            capi.check(self._encode_threshold(self._h, capi.ptr(t, C.c_float), s))
             self._threshold_rule = True                       # what results() makes of param: set once the encode is accepted
             return
         if max_bytes is not None:
@@ -366,7 +265,7 @@ class QuadtreeEncoder:
             max_leaves = [capi.quadtree_leaves_for_bytes(self.tag, self.n_iso, int(x)) for x in b]
         if max_leaves is not None and prune == "threshold":
             m = self._per_plane(max_leaves, np.int64)
-            capi.check(L.fic_qt_ctx_encode_budget(self._h, capi.ptr(m, C.c_int64), s))
+            capi.check(self._encode_budget(self._h, capi.ptr(m, C.c_int64), s))
             self._threshold_rule = True
             return
         goal, v = (capi.QT_RD_LAMBDA, lam) if lam is not None else ((capi.QT_RD_SSE, max_sse) if max_sse is not None else (capi.QT_RD_LEAVES, max_leaves))
@@ -376,11 +275,8 @@ class QuadtreeEncoder:
         if any(not 0 <= x < 1 << 64 for x in vals):
             raise FicError(-3, f"{('lam', 'max_leaves', 'max_sse')[goal]}: a value outside 0 .. 2^64 - 1")
         u = np.array(vals, np.uint64)
-        capi.check(L.fic_qt_ctx_encode_rd(self._h, goal, capi.ptr(u, C.c_uint64), s))
+        capi.check(self._encode_rd(self._h, goal, capi.ptr(u, C.c_uint64), s))
         self._threshold_rule = False
-
-    def sync(self):
-        capi.check(capi.lib().fic_qt_ctx_sync(self._h))
 
     # ---- results ---------------------------------------------------------------------------
     def results_host(self):
