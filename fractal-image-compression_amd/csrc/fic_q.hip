@@ -877,6 +877,138 @@ __device__ __forceinline__ void q_finalize_tail(const QArgs& A, int plane, int g
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_sweep_q16<NK, MULTI> : the 1-isometry sweep (the reference algorithm, MODE 0) at B = 8 / 16 on v_mfma_f32_16x16x32_f16.
+// The same body (sweep_body), the same queue, the same exact path (q_flush) as k_sweep_q<NK, 0>; what changes is the matrix
+// instruction and with it the lane layout (QShape16).  Why: the dense sweeps are power-limited (the chip holds 1.6-1.75 GHz under 32x32x16), and it holds a
+// higher clock under the 16x16x32 shape at the same work per output -- tools/mfma_shape.hip, this kernel's fast path on random
+// data: 1.93-1.96 GHz against 1.60-1.76, 7-15 % less time (profiles/r03g_mfma_shape_16x16x32_vs_32x32x16_microbench.txt).
+//   unit = 32 domain blocks x 16 range columns: 2 row tiles x KS = NK/2 chained MFMAs of K = 32 -> two 4-element accumulators;
+//   lane (c = lane & 15, g = lane >> 4) holds column c against rows 16 rt + 4 g + i (rt = accumulator, i = element):
+//   ONE column per lane and unit, so theta stays one VGPR per unit (2 CTW units per wave); the four lanes of a column
+//   (g = 0..3) share raised values by v_permlane16_swap + v_permlane32_swap.  Epilogue per unit: 4 v_max3 + compare.
+//   Fragments come in the [sub-tile][K step][lane] order of frag_slot(shape 1) from k_pool_q / k_range_q*.
+// ---------------------------------------------------------------------------------------------
+typedef float v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ v4f mfma16_f16(v4i a, v4i b, v4f c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ float max8_abs(const v4f& x0, const v4f& x1)
+{
+    const float m0 = max3f(fabsf(x0[0]), fabsf(x0[1]), fabsf(x0[2])), m1 = max3f(fabsf(x0[3]), fabsf(x1[0]), fabsf(x1[1]));
+    return max3f(m0, m1, max3f(fabsf(x1[2]), fabsf(x1[3]), 0.0f));
+}
+// maximum over the four lanes (row groups g = 0..3) that hold the same column.  Every lane of the wave must be active.
+// (The exchange between rows 0/1 and 2/3 goes through ds_bpermute, not v_permlane16_swap: a build with the swap here lost winners
+//  in the units whose prefix seed it computed -- deterministically, on 512x512 pools, with an ISA that reads correctly; every
+//  variant without the swap was right.  Cause not found (DESIGN.md section 7, item 6); this is slow-path code, the LDS crossbar
+//  costs nothing measurable.)
+template <bool SEED = false>
+__device__ __forceinline__ float q16_share_max(float v)
+{
+    const int partner = (int)((threadIdx.x & 63u) ^ 16u) << 2;
+    const float w = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(v))));
+    if constexpr (SEED) return fmaxf(w, __int_as_float(__builtin_amdgcn_ds_bpermute((int)((threadIdx.x & 63u) ^ 32u) << 2, __float_as_int(w))));
+    const uint32_t uw = __float_as_uint(w);
+    const auto q = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);    // the two halves
+    return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
+}
+
+// ---------------------------------------------------------------------------------------------
+// The lane layouts of the two matrix instructions: everything in which the sweeps on them differ, for sweep_body below.
+// A wave's CTW column tiles are NU units of 2^LGUC columns; per unit a lane holds NE test values of ONE column, 4 consecutive
+// rows from 4 * (lane >> LGUC) on in each group of erow(4) rows, in the accumulators x0, x1 (QShape32 uses x1 only when it folds).
+// ---------------------------------------------------------------------------------------------
+template <int NK_, int MODE_> struct QShape32 {              // k_sweep_q / k_sweep_qs: a unit = a 32x32 tile of v_mfma_f32_32x32x16_f16
+    static constexpr int NK = NK_, MODE = MODE_;             // MODE: also q_flush's and q_finalize_tail's
+    static constexpr int CTW = fic_q_ctw(NK), NU = CTW, LGUC = 5, NE = 16;            // LGUC: log2(columns per unit)
+    static constexpr bool FOLD = MODE == 2;
+    static constexpr int NKA = FOLD ? NK / 2 : NK;           // MFMA steps per accumulator
+    typedef v16f Acc;
+    static __device__ __forceinline__ Acc zero() { return {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+    // accumulator(s) of one 32x32 tile: FOLD: even part from steps [0, NK/2), odd part from steps [NK/2, NK)
+    static __device__ __forceinline__ void mfma(const v4i (&at)[NK], const v4i (&rb)[CTW][NK], int u, Acc& x0, Acc& x1)
+    {
+        x0 = zero();
+#pragma unroll
+        for (int m = 0; m < NKA; m++) x0 = mfma_f16(at[m], rb[u][m], x0);
+        if constexpr (FOLD) {
+            x1 = zero();
+#pragma unroll
+            for (int m = NKA; m < NK; m++) x1 = mfma_f16(at[m], rb[u][m], x1);
+        }
+    }
+    static __device__ __forceinline__ float umax(const Acc& x0, const Acc& x1) { return FOLD ? max16_sum(x0, x1) : max16_abs(x0); }
+    // test value of element e: |q| (MODE 0/1) or |even| + |odd| = the larger |q| of the isometry pair (MODE 2)
+    static __device__ __forceinline__ float val(const Acc& x0, const Acc& x1, int e) { return FOLD ? fabsf(x0[e]) + fabsf(x1[e]) : fabsf(x0[e]); }
+    // element e of row group g (the lane's half) is domain block 32 dt + 4 g + (e & 3) + 8 (e >> 2)
+    static __device__ __forceinline__ int erow(int e) { return (e & 3) + 8 * (e >> 2); }
+    template <bool SEED> static __device__ __forceinline__ float share(float v) { return q_share_max<MODE, SEED>(v); }
+    // the next tile's MFMAs interleaved with this tile's epilogue
+    static __device__ __forceinline__ void sched()
+    {
+        if constexpr (NK == 4 && !FOLD) {
+            // M M v v v M v v v M v v v (8 x v_max3 + compare): the epilogue reads a tile whose last MFMA was issued >= 64 cycles ago
+            __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
+        } else if constexpr (NK == 4 && FOLD) {
+#ifndef FIC_Q_SCHED
+#define FIC_Q_SCHED 3
+#endif
+#if FIC_Q_SCHED == 0
+            // 4 MFMAs (two 2-step accumulators), 16 adds + 8 max + compare: M M v*8 M v*8 M v*9
+            __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 9, 0);
+#elif FIC_Q_SCHED == 2
+            __builtin_amdgcn_sched_group_barrier(0x8, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 25, 0);
+#elif FIC_Q_SCHED == 3
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 7, 0);
+#endif
+        }
+    }
+};
+template <int NK_> struct QShape16 {                         // k_sweep_q16 / k_sweep_q16s: a unit = 32 rows x 16 columns of v_mfma_f32_16x16x32_f16
+    static constexpr int NK = NK_, MODE = 0;                 // 1 isometry: a column is its range block
+    static constexpr int CTW = fic_q_ctw(NK), NU = 2 * CTW, LGUC = 4, NE = 8, KS = NK / 2;
+    typedef v4f Acc;
+    static __device__ __forceinline__ Acc zero() { return {0, 0, 0, 0}; }
+    // the two accumulators (row tiles) of unit u against domain fragments at[rt * KS + ks]; rb[ci][sub * KS + ks] holds
+    // columns 16 sub + (lane & 15) of column tile ci
+    static __device__ __forceinline__ void mfma(const v4i (&at)[NK], const v4i (&rb)[CTW][NK], int u, Acc& x0, Acc& x1)
+    {
+        x0 = zero();
+        x1 = zero();
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) x0 = mfma16_f16(at[ks], rb[u >> 1][(u & 1) * KS + ks], x0);
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) x1 = mfma16_f16(at[KS + ks], rb[u >> 1][(u & 1) * KS + ks], x1);
+    }
+    static __device__ __forceinline__ float umax(const Acc& x0, const Acc& x1) { return max8_abs(x0, x1); }
+    // element e of row group g: accumulator e >> 2, element e & 3 = domain block 32 dt + 4 g + (e & 3) + 16 (e >> 2)
+    static __device__ __forceinline__ float val(const Acc& x0, const Acc& x1, int e) { return fabsf(e < 4 ? x0[e] : x1[e - 4]); }
+    static __device__ __forceinline__ int erow(int e) { return (e & 3) + 16 * (e >> 2); }
+    template <bool SEED> static __device__ __forceinline__ float share(float v) { return q16_share_max<SEED>(v); }
+    static __device__ __forceinline__ void sched() {}        // epilogue per unit: 4 v_max3 + compare, left to the compiler
+};
+
+// The sweep, once for both lane layouts (Shape = QShape32<NK, MODE> / QShape16<NK>; "unit" u = 0..NU-1 below).
 // Launch bounds: the register budget is cut for FIC_Q_WAVES_* waves per SIMD (<= 256 VGPRs at B = 4 / 8), which also makes the
 // compiler emit the MFMAs with VGPR destinations whatever the build flags say (the library is built with -mllvm
 // -amdgpu-mfma-vgpr-form; with accumulators in AGPRs every element the epilogue tests costs a v_accvgpr_read first).
@@ -884,13 +1016,12 @@ __device__ __forceinline__ void q_finalize_tail(const QArgs& A, int plane, int g
 // separate instantiation without any of that code, see (3) in slow_tile.
 // GFAST (k_sweep_qs, short pool chunks): theta_g is refreshed in the fast path (refresh_thg) instead of being loaded in every
 // flagged tile.
-template <int NK, int MODE, bool MULTI, bool GFAST>
-__device__ __forceinline__ void sweep_q_body(const QArgs& A)
+template <class S, bool MULTI, bool GFAST>
+__device__ __forceinline__ void sweep_body(const QArgs& A)
 {
-    constexpr int CTW = fic_q_ctw(NK), CT = FIC_Q_WPG * CTW;
+    constexpr int NK = S::NK, MODE = S::MODE, CTW = S::CTW, CT = FIC_Q_WPG * CTW, NU = S::NU;
     constexpr int CSHIFT = QMode<MODE>::CSHIFT;
-    constexpr bool FOLD = MODE == 2;
-    constexpr int NKA = FOLD ? NK / 2 : NK;                  // MFMA steps per accumulator
+    typedef typename S::Acc Acc;
     __shared__ uint32_t sQ[FIC_Q_WPG][FIC_Q_QCAP + 4];         // per wave: domain block | column-in-wave << 24; [QCAP] = fill count
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -898,7 +1029,7 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
     xcd_decode(blockIdx.x, A.nchunks * A.planes, A.nctg, combo_, gx_);
     const int plane = combo_ / A.nchunks;
     const int chunk = combo_ % A.nchunks;
-    const int ctw0 = A.ct_begin + gx_ * CT + wave * CTW;     // first column tile of this wave
+    const int ctw0 = A.ct_begin + gx_ * CT + wave * CTW;     // first column tile (x32 columns) of this wave
     const int dt0 = chunk * A.tiles_per_chunk;               // tiles_per_chunk is a multiple of the loop's unroll factor;
     int dt1 = dt0 + A.tiles_per_chunk;                       // the last chunk runs into the store's zero tiles (flagged flat)
     if (dt1 > A.ndtiles_loop) dt1 = A.ndtiles_loop;
@@ -911,7 +1042,7 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
     int nci = A.ct_end - ctw0;                               // column tiles this wave really owns (wave-uniform)
     if (nci > CTW) nci = CTW;
 
-    const int jcol = lane & 31, half = lane >> 5;
+    const int lcol = lane & ((1 << S::LGUC) - 1), lrows = lane >> S::LGUC;   // the lane's column in a unit, its row group (4 rows per accumulator)
     const FicRngStat* rst = A.rng_st + (size_t)plane * A.Nr_pad;
     uint32_t* const thg = A.theta_g + (size_t)plane * A.Nr_pad;
     uint32_t* const myq = sQ[wave];
@@ -927,31 +1058,29 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
 #pragma unroll
             for (int m = 0; m < NK; m++) rb[ci][m] = rp[(ci * NK + m) * 64];
     }
-    // per lane and column tile: the range behind the column, its theta, its error bound
-    float tau[CTW], E[CTW], lmn[CTW];                        // lmn: L from which a pair of this range prunes in ANY index order (header)
-    float gl[GFAST ? CTW : 1];                               // MULTI: theta_g of the lane's column per column tile, as last loaded (refresh_thg)
+    // per lane and unit: the range behind the lane's column, its theta, its error bound
+    float tau[NU], E[NU], lmn[NU];                           // lmn: L from which a pair of this range prunes in ANY index order (header)
+    float gl[GFAST ? NU : 1];                                // MULTI: theta_g of the lane's column per unit, as last loaded (refresh_thg)
 #pragma unroll
-    for (int ci = 0; ci < (GFAST ? CTW : 1); ci++) gl[ci] = -1.0f;
-    uint32_t okbits = 0, raise = 0;                          // bit ci: the column's range exists / may raise theta (rem != 0)
+    for (int u = 0; u < (GFAST ? NU : 1); u++) gl[u] = -1.0f;
+    uint32_t okbits = 0, raise = 0;                          // bit u: the column's range exists / may raise theta (rem != 0)
 #pragma unroll
-    for (int ci = 0; ci < CTW; ci++) {
-        const int col = (ctw0 + ci) * 32 + jcol;
-        const int j = col >> CSHIFT;
-        const bool ok = j < A.Nr && ci < nci;
+    for (int u = 0; u < NU; u++) {
+        const int j = (ctw0 * 32 + (u << S::LGUC) + lcol) >> CSHIFT;
+        const bool ok = j < A.Nr && u / (NU / CTW) < nci;
         const int rem = ok ? rst[j].rem : 0;
-        E[ci] = ok ? A.rngE[(size_t)plane * A.Nr_pad + j] : 0.0f;
+        E[u] = ok ? A.rngE[(size_t)plane * A.Nr_pad + j] : 0.0f;
         // rem == 0: error 0 for every block (FC:677) -> only candidate 0 can win; padding: never flagged
-        tau[ci] = (ok && rem != 0 && !A.dbg_noflag) ? FIC_Q_TAU_NONE : FIC_Q_TAU_ALL;
-        lmn[ci] = FIC_Q_LMIN * (float)rem;
-        okbits |= ok ? 1u << ci : 0u;
-        raise |= (ok && rem != 0) ? 1u << ci : 0u;
+        tau[u] = (ok && rem != 0 && !A.dbg_noflag) ? FIC_Q_TAU_NONE : FIC_Q_TAU_ALL;
+        lmn[u] = FIC_Q_LMIN * (float)rem;
+        okbits |= ok ? 1u << u : 0u;
+        raise |= (ok && rem != 0) ? 1u << u : 0u;
     }
 
     const v4i* pa = A.poolQ + (size_t)plane * A.ndtiles_alloc * NK * 64 + lane;
     // flat-tile flags through the scalar cache (wave-uniform address; a vector load here would make the slow path wait for
     // the prefetched fragment loads as well: s_waitcnt vmcnt(0))
     const uint32_t AS4* pflat = (const uint32_t AS4*)(uintptr_t)(A.dflat + (size_t)plane * A.ndtiles_alloc);
-    const v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int qn = 0;                                              // queued entries (wave-uniform)
     unsigned st_slow = 0, st_pairs = 0;                      // instrumentation (wave-uniform; reported when A.stats is set)
 
@@ -961,23 +1090,20 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
         if (lane == 0) *myqn = 0u;
         __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): atomics left in flight here make the compiler tighten the
     };                                                       // fast path's waits for the prefetched fragments
-    // test value of element e: |q| (MODE 0/1) or |even| + |odd| = the larger |q| of the isometry pair (MODE 2)
-    auto val = [&](const v16f& acc, const v16f& acc2, int e) __attribute__((always_inline)) {
-        return FOLD ? fabsf(acc[e]) + fabsf(acc2[e]) : fabsf(acc[e]);
-    };
-    // A tile with flagged entries (or a chunk's first tile): queue the entries, raise theta.
+    // A unit with flagged entries (or a chunk's first tile): queue the entries, raise theta.
     //   theta moves three ways: (1) FIRST: seeded from the tile's largest test value per range -- out of index order, hence
     //   only when that pair's L >= lmn = 0.26 rem (header); (2) from the flagged entries of this tile (they have lower indices than
     //   everything still to come in this chunk); (3) from theta_g, the best level any wave has published for the range --
     //   other chunks, any index order, hence published only for pairs with L >= lmn.
-    auto slow_tile = [&](const v16f& acc, const v16f& acc2, float mx, int ci, int dt, bool first) __attribute__((always_inline)) {
+    auto slow_tile = [&](const Acc& x0, const Acc& x1, float mx, int u, int dt, bool first) __attribute__((always_inline)) {
         // only zeros flagged (theta still "none"): an all-flat tile seen before anything was evaluated needs nothing
         if (!first && __builtin_amdgcn_ballot_w64(mx > 0.0f) == 0 && pflat[dt] != 0u) return;
         st_slow++;
-        const bool ok = (okbits >> ci) & 1u;
-        const bool mayraise = (raise >> ci) & 1u;
-        const int colw = ci * 32 + jcol;                     // column in wave
-        const int jg = ((ctw0 + ci) * 32 + jcol) >> CSHIFT;  // the column's range block (valid when ok)
+        const bool ok = (okbits >> u) & 1u;
+        const bool mayraise = (raise >> u) & 1u;
+        const int colw = (u << S::LGUC) + lcol;              // column in wave
+        // the column's range block (valid when ok).  (Summed in this order: in the init loop's order k_sweep_q16<4, true> takes 211 VGPRs, not 197)
+        const int jg = (ctw0 * 32 + colw) >> CSHIFT;
         // (3): a load, waited for at the end of the tile -- a memory round trip, 1.1 us per flagged tile against 0.4 us without
         // (tools/phases.py; merging it a flagged tile later is no cheaper: the vector-memory counter is in-order, the next wait
         // for domain fragments waits for it too).  Fine where flagged tiles are rare (long chunks); with short chunks -- one
@@ -985,19 +1111,19 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
         // instead (refresh_thg in step(): +3..11 % on long chunks, hence not there).  The one-chunk instantiation -- no other wave
         // sees this range -- has no vector memory operation in a flagged tile at all.
         const uint32_t g = (MULTI && !GFAST && mayraise) ? thg[jg] : FIC_Q_THG_NONE;
-        const uint32_t ent0 = (uint32_t)(dt * 32 + 4 * half) | ((uint32_t)colw << 24);   // entry of element 0; element e adds its row
+        const uint32_t ent0 = (uint32_t)(dt * 32 + 4 * lrows) | ((uint32_t)colw << 24);   // entry of element 0; element e adds its row
         if (first) {                                         // (1)
-            const float lo = __fsub_rn(q_share_max<MODE>(ok ? mx : 0.0f), E[ci]);
-            if (mayraise && lo >= lmn[ci]) tau[ci] = fmaxf(tau[ci], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[ci]));
+            const float lo = __fsub_rn(S::template share<false>(ok ? mx : 0.0f), E[u]);
+            if (mayraise && lo >= lmn[u]) tau[u] = fmaxf(tau[u], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[u]));
         }
         // candidate 0 = (block 0, copy 0): always evaluated (MODE 2: with its partner, copy 2)
-        const bool cand0 = first && dt == 0 && half == 0 && ok && (jcol & ((1 << CSHIFT) - 1)) == 0;
+        const bool cand0 = first && dt == 0 && lrows == 0 && ok && (lcol & ((1 << CSHIFT) - 1)) == 0;
         // Per-lane mask of the elements above theta, built without scalar branches: bit e = sign(theta - value_e), shifted in by
         // v_alignbit.  (Strict '>': value == theta gives +0.  theta = "none" (-1) flags everything, zeros included.)
         uint32_t hm = 0;
 #pragma unroll
-        for (int e = 15; e >= 0; e--)
-            hm = __builtin_amdgcn_alignbit(hm, __float_as_uint(__fsub_rn(tau[ci], val(acc, acc2, e))), 31);
+        for (int e = S::NE - 1; e >= 0; e--)
+            hm = __builtin_amdgcn_alignbit(hm, __float_as_uint(__fsub_rn(tau[u], S::val(x0, x1, e))), 31);   // (NE elements shifted in: bits 0..NE-1)
         if (!ok) hm = 0;
         if (cand0) hm |= 1u;
         const int cnt = __builtin_popcount(hm);
@@ -1008,45 +1134,34 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
             uint32_t w;
             asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(myqn_lds), "v"((uint32_t)cnt) : "memory");
             int e = __builtin_ctz(hm);
-            myq[w] = ent0 + (uint32_t)((e & 3) + 8 * (e >> 2));
+            myq[w] = ent0 + (uint32_t)S::erow(e);
             for (uint32_t h = hm & (hm - 1); h; h &= h - 1) {
                 e = __builtin_ctz(h);
-                myq[++w] = ent0 + (uint32_t)((e & 3) + 8 * (e >> 2));
+                myq[++w] = ent0 + (uint32_t)S::erow(e);
             }
         }
         // a lane with flagged elements has its largest element among them: that is mx
         const float mp = cnt != 0 ? mx : -1.0f;
         // (2): level of the best flagged entry, shared by the lanes of the range
-        const float lo2 = q_share_max<MODE>((mayraise && mp >= 0.0f) ? __fsub_rn(mp, E[ci]) : -1.0f);
+        const float lo2 = S::template share<false>((mayraise && mp >= 0.0f) ? __fsub_rn(mp, E[u]) : -1.0f);
         if (mayraise && lo2 >= 0.0f) {
-            const float lb = __fsub_rn(__fmul_rn(lo2, FIC_Q_LEVEL), E[ci]);
-            tau[ci] = fmaxf(tau[ci], lb);
-            if (MULTI && lo2 >= lmn[ci] && lb > 0.0f && half == 0 && (jcol & ((1 << CSHIFT) - 1)) == 0) atomicMax((int*)&thg[jg], __float_as_int(lb));
+            const float lb = __fsub_rn(__fmul_rn(lo2, FIC_Q_LEVEL), E[u]);
+            tau[u] = fmaxf(tau[u], lb);
+            if (MULTI && lo2 >= lmn[u] && lb > 0.0f && lrows == 0 && (lcol & ((1 << CSHIFT) - 1)) == 0) atomicMax((int*)&thg[jg], __float_as_int(lb));
         }
-        if (MULTI && !GFAST && mayraise) tau[ci] = fmaxf(tau[ci], __uint_as_float(g));
+        if (MULTI && !GFAST && mayraise) tau[u] = fmaxf(tau[u], __uint_as_float(g));
         // the fill count after this tile (LDS operations of a wave complete in order); one tile adds at most 1024 entries
         const int tot = __builtin_amdgcn_readfirstlane((int)*(volatile __attribute__((address_space(3))) uint32_t*)(__attribute__((address_space(3))) uint32_t*)myqn);   // ds_read, not a flat load
         st_pairs += (unsigned)(tot - qn);
         qn = tot;
         if (qn > FIC_Q_QFLUSH) flush();
     };
-    // accumulator(s) of one 32x32 tile: FOLD: even part from steps [0, NK/2), odd part from steps [NK/2, NK)
-    auto tile_mfma = [&](const v4i (&at)[NK], const v4i (&bt)[NK], v16f& acc, v16f& acc2) __attribute__((always_inline)) {
-        acc = zero;
-#pragma unroll
-        for (int m = 0; m < NKA; m++) acc = mfma_f16(at[m], bt[m], acc);
-        if constexpr (FOLD) {
-            acc2 = zero;
-#pragma unroll
-            for (int m = NKA; m < NK; m++) acc2 = mfma_f16(at[m], bt[m], acc2);
-        }
-    };
 
-    // Two fragment buffers.  A step computes on `ac` (domain tile dt) and finishes with the first tile of `an` (tile dt + 1);
-    // as soon as the last MFMAs that read `ac` have been issued (column tile CTW-1), `ac` is reloaded with tile dt + 2, which
-    // is first needed at the end of the NEXT step: every load has CTW + 1 tile epilogues (a step and a quarter) to land.
+    // Two fragment buffers.  A step computes on `ac` (domain tile dt) and finishes with the first unit of `an` (tile dt + 1);
+    // as soon as the last MFMAs that read `ac` have been issued (unit NU-1), `ac` is reloaded with tile dt + 2, which
+    // is first needed at the end of the NEXT step: every load has NU + 1 unit epilogues (a step and a quarter) to land.
     v4i a0[NK], a1[NK];
-    v16f acc, acc2 = zero;
+    Acc x0, x1 = S::zero();
     // Prefix seed (pool chunks after the first).  theta may be the level of ANY pair X with a LOWER index than the pairs it
     // prunes, evaluated or not: if X was pruned itself, then by a pair that beats or ties-and-precedes it, and that pair beats a
     // later Y with L(Y) <= (1 - 2^-18) L(X) all the same (header, "Invariant").  Domain tile 0 holds the lowest indices of the
@@ -1058,12 +1173,12 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
 #pragma unroll
             for (int m = 0; m < NK; m++) a0[m] = pa[(size_t)m * 64];
 #pragma unroll
-            for (int ci = 0; ci < CTW; ci++) {
-                tile_mfma(a0, rb[ci], acc, acc2);
-                const float mx = FOLD ? max16_sum(acc, acc2) : max16_abs(acc);
-                const bool ok = (okbits >> ci) & 1u, mayraise = (raise >> ci) & 1u;
-                const float lo = __fsub_rn(q_share_max<MODE, true>(ok ? mx : 0.0f), E[ci]);
-                if (mayraise && lo > 0.0f) tau[ci] = fmaxf(tau[ci], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[ci]));
+            for (int u = 0; u < NU; u++) {
+                S::mfma(a0, rb, u, x0, x1);
+                const float mx = S::umax(x0, x1);
+                const bool ok = (okbits >> u) & 1u, mayraise = (raise >> u) & 1u;
+                const float lo = __fsub_rn(S::template share<true>(ok ? mx : 0.0f), E[u]);
+                if (mayraise && lo > 0.0f) tau[u] = fmaxf(tau[u], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[u]));
             }
         }
     }
@@ -1071,74 +1186,41 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
     for (int m = 0; m < NK; m++) a0[m] = pa[((size_t)dt0 * NK + m) * 64];
 #pragma unroll
     for (int m = 0; m < NK; m++) a1[m] = pa[((size_t)(dt0 + 1) * NK + m) * 64];
-    tile_mfma(a0, rb[0], acc, acc2);
+    S::mfma(a0, rb, 0, x0, x1);
 
     // one domain tile (the fragment store has spare zero tiles behind the pool for the loop's overrun and the prefetch)
     // (3) theta_g, the best level any wave has published for the lane's ranges (other pool chunks): every step merges the levels of
-    // half of the column tiles -- loaded two steps ago, next to the fragment loads, so nobody waits for them -- and requests
-    // them again: a load and a v_max per column tile and two domain tiles.  PH = which half (the loop alternates two steps).
+    // half of the units -- loaded two steps ago, next to the fragment loads, so nobody waits for them -- and requests
+    // them again: a load and a v_max per unit and two domain tiles.  PH = which half (the loop alternates two steps).
     auto refresh_thg = [&](auto ph) __attribute__((always_inline)) {
         if constexpr (MULTI && GFAST) {
-            constexpr int PH = decltype(ph)::value, H = CTW / 2;
+            constexpr int PH = decltype(ph)::value, H = NU / 2;
 #pragma unroll
             for (int c = PH * H; c < PH * H + H; c++) {
                 tau[c] = fmaxf(tau[c], gl[c]);               // (columns that never raise hold TAU_ALL; "nothing published" is -1)
-                gl[c] = __uint_as_float(thg[((ctw0 + c) * 32 + jcol) >> CSHIFT]);
+                gl[c] = __uint_as_float(thg[(ctw0 * 32 + (c << S::LGUC) + lcol) >> CSHIFT]);
             }
         }
     };
     auto step = [&](int dt, v4i (&ac)[NK], const v4i (&an)[NK], const bool first, auto ph) __attribute__((always_inline)) {
 #pragma unroll
-        for (int ci = 0; ci < CTW; ci++) {
-            // the next tile's MFMAs: column tile ci+1 of this domain tile, or column tile 0 of the next domain tile
-            v16f nacc, nacc2 = zero;
-            if (ci + 1 < CTW) tile_mfma(ac, rb[ci + 1], nacc, nacc2);
-            else tile_mfma(an, rb[0], nacc, nacc2);
-            if (ci == CTW - 2) {
+        for (int u = 0; u < NU; u++) {
+            // the next unit's MFMAs: unit u+1 of this domain tile, or unit 0 of the next domain tile
+            Acc n0, n1 = S::zero();
+            if (u + 1 < NU) S::mfma(ac, rb, u + 1, n0, n1);
+            else S::mfma(an, rb, 0, n0, n1);
+            if (u == NU - 2) {
 #pragma unroll
                 for (int m = 0; m < NK; m++) ac[m] = pa[((size_t)(dt + 2) * NK + m) * 64];
                 refresh_thg(ph);
             }
-            const float mx = FOLD ? max16_sum(acc, acc2) : max16_abs(acc);
-            const bool hit = mx > tau[ci];
-            if constexpr (NK == 4 && !FOLD) {
-                // M M v v v M v v v M v v v (8 x v_max3 + compare): the epilogue reads a tile whose last MFMA was issued >= 64 cycles ago
-                __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
-            } else if constexpr (NK == 4 && FOLD) {
-#ifndef FIC_Q_SCHED
-#define FIC_Q_SCHED 3
-#endif
-#if FIC_Q_SCHED == 0
-                // 4 MFMAs (two 2-step accumulators), 16 adds + 8 max + compare: M M v*8 M v*8 M v*9
-                __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 9, 0);
-#elif FIC_Q_SCHED == 2
-                __builtin_amdgcn_sched_group_barrier(0x8, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 25, 0);
-#elif FIC_Q_SCHED == 3
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 6, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x2, 7, 0);
-#endif
-            }
+            const float mx = S::umax(x0, x1);
+            const bool hit = mx > tau[u];
+            S::sched();
             // a chunk's first tile always takes the slow path: theta is seeded there and candidate 0 is queued
-            if (__builtin_expect((__builtin_amdgcn_ballot_w64(hit) != 0) | first, 0)) slow_tile(acc, acc2, mx, ci, dt, first);
-            acc = nacc;
-            if constexpr (FOLD) acc2 = nacc2;
+            if (__builtin_expect((__builtin_amdgcn_ballot_w64(hit) != 0) | first, 0)) slow_tile(x0, x1, mx, u, dt, first);
+            x0 = n0;
+            x1 = n1;
         }
     };
 #ifdef FIC_Q_PHASES
@@ -1180,257 +1262,26 @@ __device__ __forceinline__ void sweep_q_body(const QArgs& A)
     if (A.fin_count) q_finalize_tail<NK, MODE>(A, plane, gx_, &s_wdone, lane);
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_sweep_q16<NK, MULTI> : the 1-isometry sweep (the reference algorithm, MODE 0) at B = 8 / 16 on v_mfma_f32_16x16x32_f16.
-// Same search, same queue, same exact path (q_flush) as k_sweep_q<NK, 0>; what changes is the matrix instruction and with it
-// the lane layout.  Why: the dense sweeps are power-limited (the chip holds 1.6-1.75 GHz under 32x32x16), and it holds a
-// higher clock under the 16x16x32 shape at the same work per output -- tools/mfma_shape.hip, this kernel's fast path on random
-// data: 1.93-1.96 GHz against 1.60-1.76, 7-15 % less time (profiles/r03g_mfma_shape_16x16x32_vs_32x32x16_microbench.txt).
-//   unit = 32 domain blocks x 16 range columns: 2 row tiles x KS = NK/2 chained MFMAs of K = 32 -> two 4-element accumulators;
-//   lane (c = lane & 15, g = lane >> 4) holds column c against rows 16 rt + 4 g + i (rt = accumulator, i = element):
-//   ONE column per lane and unit, so theta stays one VGPR per unit (2 CTW units per wave); the four lanes of a column
-//   (g = 0..3) share raised values by v_permlane16_swap + v_permlane32_swap.  Epilogue per unit: 4 v_max3 + compare.
-//   Fragments come in the [sub-tile][K step][lane] order of frag_slot(shape 1) from k_pool_q / k_range_q*.
-// ---------------------------------------------------------------------------------------------
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4f mfma16_f16(v4i a, v4i b, v4f c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float max8_abs(const v4f& x0, const v4f& x1)
-{
-    const float m0 = max3f(fabsf(x0[0]), fabsf(x0[1]), fabsf(x0[2])), m1 = max3f(fabsf(x0[3]), fabsf(x1[0]), fabsf(x1[1]));
-    return max3f(m0, m1, max3f(fabsf(x1[2]), fabsf(x1[3]), 0.0f));
-}
-// maximum over the four lanes (row groups g = 0..3) that hold the same column.  Every lane of the wave must be active.
-// (The exchange between rows 0/1 and 2/3 goes through ds_bpermute, not v_permlane16_swap: a build with the swap here lost winners
-//  in the units whose prefix seed it computed -- deterministically, on 512x512 pools, with an ISA that reads correctly; every
-//  variant without the swap was right.  Cause not found (DESIGN.md section 7, item 6); this is slow-path code, the LDS crossbar
-//  costs nothing measurable.)
-template <bool SEED = false>
-__device__ __forceinline__ float q16_share_max(float v)
-{
-    const int partner = (int)((threadIdx.x & 63u) ^ 16u) << 2;
-    const float w = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(v))));
-    if constexpr (SEED) return fmaxf(w, __int_as_float(__builtin_amdgcn_ds_bpermute((int)((threadIdx.x & 63u) ^ 32u) << 2, __float_as_int(w))));
-    const uint32_t uw = __float_as_uint(w);
-    const auto q = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);    // the two halves
-    return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
-}
-template <int NK, bool MULTI, bool GFAST>
-__device__ __forceinline__ void sweep_q16_body(const QArgs& A)
-{
-    constexpr int CTW = fic_q_ctw(NK), CT = FIC_Q_WPG * CTW, CU = 2 * CTW, KS = NK / 2;
-    __shared__ uint32_t sQ[FIC_Q_WPG][FIC_Q_QCAP + 4];         // per wave: domain block | column-in-wave << 24; [QCAP] = fill count
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int combo_, gx_;
-    xcd_decode(blockIdx.x, A.nchunks * A.planes, A.nctg, combo_, gx_);
-    const int plane = combo_ / A.nchunks;
-    const int chunk = combo_ % A.nchunks;
-    const int ctw0 = A.ct_begin + gx_ * CT + wave * CTW;     // first column tile (x32 columns) of this wave
-    const int dt0 = chunk * A.tiles_per_chunk;
-    int dt1 = dt0 + A.tiles_per_chunk;
-    if (dt1 > A.ndtiles_loop) dt1 = A.ndtiles_loop;
-    __shared__ int s_wdone;                                  // fused finalise: "this workgroup is its column group's last" (q_finalize_tail)
-    if (dt0 >= A.ndtiles || ctw0 >= A.ct_end) {              // (waves are independent: no barrier in the sweep itself)
-        if (A.fin_count) q_finalize_tail<NK, 0>(A, plane, gx_, &s_wdone, lane);
-        return;
-    }
-    const unsigned long long clk0 = A.stats ? clock64() : 0ull, tick0 = A.stats ? wall_clock64() : 0ull;
-    int nci = A.ct_end - ctw0;                               // column tiles this wave really owns (wave-uniform)
-    if (nci > CTW) nci = CTW;
-
-    const int c16 = lane & 15, g4 = lane >> 4;
-    const FicRngStat* rst = A.rng_st + (size_t)plane * A.Nr_pad;
-    uint32_t* const thg = A.theta_g + (size_t)plane * A.Nr_pad;
-    uint32_t* const myq = sQ[wave];
-    uint32_t* const myqn = myq + FIC_Q_QCAP;
-    const uint32_t myqn_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)myqn;
-    if (lane == 0) *myqn = 0u;
-
-    v4i rb[CTW][NK];                                         // rb[ci][sub * KS + ks]: columns 16 sub + (lane & 15) of column tile ci
-    {
-        const v4i* rp = A.rngQ + ((size_t)plane * A.nct_alloc + ctw0) * NK * 64 + lane;
-#pragma unroll
-        for (int ci = 0; ci < CTW; ci++)
-#pragma unroll
-            for (int m = 0; m < NK; m++) rb[ci][m] = rp[(ci * NK + m) * 64];
-    }
-    float tau[CU], E[CU], lmn[CU];
-    float gl[GFAST ? CU : 1];
-#pragma unroll
-    for (int cj = 0; cj < (GFAST ? CU : 1); cj++) gl[cj] = -1.0f;
-    uint32_t okbits = 0, raise = 0;
-#pragma unroll
-    for (int cj = 0; cj < CU; cj++) {
-        const int j = ctw0 * 32 + cj * 16 + c16;             // the lane's column of unit cj = its range block
-        const bool ok = j < A.Nr && (cj >> 1) < nci;
-        const int rem = ok ? rst[j].rem : 0;
-        E[cj] = ok ? A.rngE[(size_t)plane * A.Nr_pad + j] : 0.0f;
-        tau[cj] = (ok && rem != 0 && !A.dbg_noflag) ? FIC_Q_TAU_NONE : FIC_Q_TAU_ALL;
-        lmn[cj] = FIC_Q_LMIN * (float)rem;
-        okbits |= ok ? 1u << cj : 0u;
-        raise |= (ok && rem != 0) ? 1u << cj : 0u;
-    }
-    const v4i* pa = A.poolQ + (size_t)plane * A.ndtiles_alloc * NK * 64 + lane;
-    const uint32_t AS4* pflat = (const uint32_t AS4*)(uintptr_t)(A.dflat + (size_t)plane * A.ndtiles_alloc);
-    const v4f zero = {0, 0, 0, 0};
-    int qn = 0;
-    unsigned st_slow = 0, st_pairs = 0;
-
-    auto flush = [&]() __attribute__((always_inline)) {
-        q_flush<NK, 0>(A, myq, qn, plane, ctw0, lane);
-        qn = 0;
-        if (lane == 0) *myqn = 0u;
-        __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0), as in k_sweep_q
-    };
-    // element e of the lane's unit: accumulator e >> 2, element e & 3 = row 16 (e >> 2) + 4 g + (e & 3)
-    auto val = [&](const v4f& x0, const v4f& x1, int e) __attribute__((always_inline)) { return fabsf(e < 4 ? x0[e] : x1[e - 4]); };
-    // A unit with flagged entries (or a chunk's first tile): exactly slow_tile of k_sweep_q with this kernel's lane layout
-    auto slow_unit = [&](const v4f& x0, const v4f& x1, float mx, int cj, int dt, bool first) __attribute__((always_inline)) {
-        if (!first && __builtin_amdgcn_ballot_w64(mx > 0.0f) == 0 && pflat[dt] != 0u) return;
-        st_slow++;
-        const bool ok = (okbits >> cj) & 1u;
-        const bool mayraise = (raise >> cj) & 1u;
-        const int colw = cj * 16 + c16;                      // column in wave
-        const int jg = ctw0 * 32 + colw;                     // the column's range block (valid when ok)
-        const uint32_t g = (MULTI && !GFAST && mayraise) ? thg[jg] : FIC_Q_THG_NONE;    // (3); GFAST: in the fast path (refresh_thg)
-        const uint32_t ent0 = (uint32_t)(dt * 32 + 4 * g4) | ((uint32_t)colw << 24);     // entry of element 0; element e adds 16 (e >> 2) + (e & 3)
-        if (first) {                                         // (1) out-of-order seed, only from a pair with L >= lmn
-            const float lo = __fsub_rn(q16_share_max<>(ok ? mx : 0.0f), E[cj]);
-            if (mayraise && lo >= lmn[cj]) tau[cj] = fmaxf(tau[cj], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[cj]));
-        }
-        const bool cand0 = first && dt == 0 && g4 == 0 && ok;                // candidate 0 = block 0: always evaluated
-        uint32_t hm = 0;
-#pragma unroll
-        for (int e = 7; e >= 0; e--)
-            hm = __builtin_amdgcn_alignbit(hm, __float_as_uint(__fsub_rn(tau[cj], val(x0, x1, e))), 31);
-                                                                             // (8 elements shifted in: bits 0..7)
-        if (!ok) hm = 0;
-        if (cand0) hm |= 1u;
-        const int cnt = __builtin_popcount(hm);
-        if (cnt != 0) {
-            uint32_t w;
-            asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(myqn_lds), "v"((uint32_t)cnt) : "memory");
-            int e = __builtin_ctz(hm);
-            myq[w] = ent0 + (uint32_t)((e & 3) + 16 * (e >> 2));
-            for (uint32_t h = hm & (hm - 1); h; h &= h - 1) {
-                e = __builtin_ctz(h);
-                myq[++w] = ent0 + (uint32_t)((e & 3) + 16 * (e >> 2));
-            }
-        }
-        const float mp = cnt != 0 ? mx : -1.0f;
-        const float lo2 = q16_share_max<>((mayraise && mp >= 0.0f) ? __fsub_rn(mp, E[cj]) : -1.0f);   // (2)
-        if (mayraise && lo2 >= 0.0f) {
-            const float lb = __fsub_rn(__fmul_rn(lo2, FIC_Q_LEVEL), E[cj]);
-            tau[cj] = fmaxf(tau[cj], lb);
-            if (MULTI && lo2 >= lmn[cj] && lb > 0.0f && g4 == 0) atomicMax((int*)&thg[jg], __float_as_int(lb));
-        }
-        if (MULTI && !GFAST && mayraise) tau[cj] = fmaxf(tau[cj], __uint_as_float(g));       // (3)
-        const int tot = __builtin_amdgcn_readfirstlane((int)*(volatile __attribute__((address_space(3))) uint32_t*)(__attribute__((address_space(3))) uint32_t*)myqn);
-        st_pairs += (unsigned)(tot - qn);
-        qn = tot;
-        if (qn > FIC_Q_QFLUSH) flush();
-    };
-    // the two accumulators of unit cj against domain fragments at[rt * KS + ks]
-    auto unit_mfma = [&](const v4i (&at)[NK], int cj, v4f& x0, v4f& x1) __attribute__((always_inline)) {
-        x0 = zero;
-        x1 = zero;
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) x0 = mfma16_f16(at[ks], rb[cj >> 1][(cj & 1) * KS + ks], x0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) x1 = mfma16_f16(at[KS + ks], rb[cj >> 1][(cj & 1) * KS + ks], x1);
-    };
-
-    v4i a0[NK], a1[NK];
-    v4f x0, x1;
-    if constexpr (MULTI && FIC_Q_SEED) {                     // prefix seed from domain tile 0, as in k_sweep_q
-        if (dt0 != 0) {
-#pragma unroll
-            for (int m = 0; m < NK; m++) a0[m] = pa[(size_t)m * 64];
-#pragma unroll
-            for (int cj = 0; cj < CU; cj++) {
-                unit_mfma(a0, cj, x0, x1);
-                const float mx = max8_abs(x0, x1);
-                const bool ok = (okbits >> cj) & 1u, mayraise = (raise >> cj) & 1u;
-                const float lo = __fsub_rn(q16_share_max<true>(ok ? mx : 0.0f), E[cj]);
-                if (mayraise && lo > 0.0f) tau[cj] = fmaxf(tau[cj], __fsub_rn(__fmul_rn(lo, FIC_Q_LEVEL), E[cj]));
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < NK; m++) a0[m] = pa[((size_t)dt0 * NK + m) * 64];
-#pragma unroll
-    for (int m = 0; m < NK; m++) a1[m] = pa[((size_t)(dt0 + 1) * NK + m) * 64];
-    unit_mfma(a0, 0, x0, x1);
-    auto refresh_thg = [&](auto ph) __attribute__((always_inline)) {      // as in k_sweep_q: half of the units per step
-        if constexpr (MULTI && GFAST) {
-            constexpr int PH = decltype(ph)::value, H = CU / 2;
-#pragma unroll
-            for (int c = PH * H; c < PH * H + H; c++) {
-                tau[c] = fmaxf(tau[c], gl[c]);
-                gl[c] = __uint_as_float(thg[ctw0 * 32 + c * 16 + c16]);
-            }
-        }
-    };
-    auto step = [&](int dt, v4i (&ac)[NK], const v4i (&an)[NK], const bool first, auto ph) __attribute__((always_inline)) {
-#pragma unroll
-        for (int cj = 0; cj < CU; cj++) {
-            v4f n0, n1;
-            if (cj + 1 < CU) unit_mfma(ac, cj + 1, n0, n1);
-            else unit_mfma(an, 0, n0, n1);
-            if (cj == CU - 2) {
-#pragma unroll
-                for (int m = 0; m < NK; m++) ac[m] = pa[((size_t)(dt + 2) * NK + m) * 64];
-                refresh_thg(ph);
-            }
-            const float mx = max8_abs(x0, x1);
-            const bool hit = mx > tau[cj];
-            if (__builtin_expect((__builtin_amdgcn_ballot_w64(hit) != 0) | first, 0)) slow_unit(x0, x1, mx, cj, dt, first);
-            x0 = n0;
-            x1 = n1;
-        }
-    };
-    for (int dt = dt0; dt < dt1; dt += 2) {
-        step(dt, a0, a1, dt == dt0, std::integral_constant<int, 0>());
-        step(dt + 1, a1, a0, false, std::integral_constant<int, 1>());
-    }
-    flush();
-    if (A.stats && lane == 0) {
-        atomicAdd(&A.stats[0], (unsigned long long)(dt1 - dt0) * (unsigned)nci);
-        atomicAdd(&A.stats[1], (unsigned long long)st_slow);
-        atomicAdd(&A.stats[2], (unsigned long long)st_pairs);
-        atomicAdd(&A.stats[3], 1ull);
-        if ((blockIdx.x & 15) == 0 && wave == 0) {
-            atomicAdd(&A.stats[4], (unsigned long long)(clock64() - clk0));
-            atomicAdd(&A.stats[5], (unsigned long long)(wall_clock64() - tick0));
-            atomicAdd(&A.stats[6], 1ull);
-        }
-    }
-    if (A.fin_count) q_finalize_tail<NK, 0>(A, plane, gx_, &s_wdone, lane);
-}
-
 // The kernels: one pool chunk / several (theta_g shared between the waves of a range) / several SHORT ones (k_sweep_qs).
 template <int NK, int MODE, bool MULTI>
 __global__ __launch_bounds__(64 * FIC_Q_WPG, NK == 4 ? FIC_Q_WAVES_B8 : (NK < 4 ? FIC_Q_WAVES_B4 : 1)) void k_sweep_q(QArgs A)
 {
-    sweep_q_body<NK, MODE, MULTI, false>(A);
+    sweep_body<QShape32<NK, MODE>, MULTI, false>(A);
 }
 template <int NK, int MODE>
 __global__ __launch_bounds__(64 * FIC_Q_WPG, NK == 4 ? FIC_Q_WAVES_B8 : (NK < 4 ? FIC_Q_WAVES_B4 : 1)) void k_sweep_qs(QArgs A)
 {
-    sweep_q_body<NK, MODE, true, true>(A);
+    sweep_body<QShape32<NK, MODE>, true, true>(A);
 }
 template <int NK, bool MULTI>
 __global__ __launch_bounds__(64 * FIC_Q_WPG, NK == 4 ? FIC_Q_WAVES_B8 : 1) void k_sweep_q16(QArgs A)
 {
-    sweep_q16_body<NK, MULTI, false>(A);
+    sweep_body<QShape16<NK>, MULTI, false>(A);
 }
 template <int NK>
 __global__ __launch_bounds__(64 * FIC_Q_WPG, NK == 4 ? FIC_Q_WAVES_B8 : 1) void k_sweep_q16s(QArgs A)
 {
-    sweep_q16_body<NK, true, true>(A);
+    sweep_body<QShape16<NK>, true, true>(A);
 }
 
 // ---------------------------------------------------------------------------------------------
