@@ -18,7 +18,7 @@ XCHECK_SOURCES = ["fic_mfma.hip", "fic_bf16.hip"]
 
 def xcheck():
     return os.environ.get("FIC_BUILD_XCHECK", "1") != "0"
-HEADERS = ["fic_device.h", "fic_launch.h", "fic_devfn.h", "fic_internal.h", "fic_stream.h", "fic_devmem.h", "fic_lsq_fit.h", "fic_lsq_rgb_fit.h", "fic_lsq_q_chunks.h", "fic_sweep_chunks.h", "fic_qt_batch_plan.h", "fic_ctx_options.h", "fic_lsq_q_tile.h", "fic_d4_tables.h", os.path.join("..", "..", "include", "fic.h")]
+HEADERS = ["fic_device.h", "fic_launch.h", "fic_devfn.h", "fic_internal.h", "fic_stream.h", "fic_devmem.h", "fic_lsq_fit.h", "fic_lsq_rgb_fit.h", "fic_lsq_q_chunks.h", "fic_sweep_chunks.h", "fic_qt_batch_plan.h", "fic_qt_decode_plan.h", "fic_ctx_options.h", "fic_lsq_q_tile.h", "fic_d4_tables.h", os.path.join("..", "..", "include", "fic.h")]
 # -ffp-contract=off: the Java reference never fuses a*b+c (FractalCompression.java:641,683);
 # hipcc's device default is "fast".  No fast-math: f32 divide/sqrt stay correctly rounded.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

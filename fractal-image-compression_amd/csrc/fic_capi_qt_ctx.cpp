@@ -25,6 +25,7 @@ struct fic_qt_ctx : ficd::CtxCore {
     int next_slot = 0;
     uint8_t* gray_own = nullptr;         // a host input's device copy (grey), the staging of an ARGB upload to a grey context
     int32_t* argb_own = nullptr;
+    char* dec_store = nullptr;           // decode and collage (QtDecodePlan, fic_qt_decode_plan.h): on first use
     template <typename T>
     T* at(QtArea a) const { return (T*)(store + plan.a[a].off); }
 };
@@ -105,6 +106,108 @@ void qt_ctx_free(fic_qt_ctx* c)
         if (c->rgb[l]) fic_rgb_ctx_destroy(c->rgb[l]);
     }
     delete c;
+}
+
+// ---- decode and collage of the last encode's tables ---------------------------------------------------------
+// What both entries check and set up behind their null checks, holding c->mu: an encode has run, the levels at `zoom`
+// (make_decode_geometry refuses another zoom and a side above 64), room in `out`, the decode store.  D: the kernels' view of
+// the context; W: where the areas of the store lie.
+int qt_ctx_decode_begin(fic_qt_ctx* c, const char* who, int zoom, int64_t capacity_pixels, FicQtDecode* D, QtDecodePlan* W)
+{
+    if (!c->encoded_any) return fail(FIC_E_STATE, "%s: nothing encoded yet", who);
+    const QtLevels& L = c->L;
+    const FicGeom& top = L.g[0];
+    *D = FicQtDecode{};
+    for (int l = 0; l < L.nl; l++)
+        if (int rc = make_decode_geometry(top.W, top.H, L.g[l].B, L.g[l].wK, c->n_iso, c->planes, zoom, &D->g[l])) return rc;
+    D->nl = L.nl;
+    D->zoom = zoom;
+    D->B_max = c->B_max;
+    D->B_min = c->B_min;
+    D->W = top.W;
+    D->H = top.H;
+    D->Rw_top = top.Rw;
+    D->Rw_min = L.g[L.nl - 1].Rw;
+    D->Nr_min = c->plan.Nr_min;
+    D->n_iso = c->n_iso;
+    D->leaf_stride = c->plan.a[kQtLeaves].stride;
+    const size_t P = (size_t)c->planes, npix = (size_t)top.W * top.H;
+    const char* why = "";
+    if (qt_decode_plan(c->planes, top.W, top.H, c->B_min, c->colour ? 4 : 1, zoom, sizeof(FicDecodeState), fic_decode_sq_words(P, npix), W, &why))
+        return fail(FIC_E_GEOMETRY, "%s: %d planes of %dx%d at zoom %d: %s would pass 2^31 - 1", who, c->planes, top.W, top.H, zoom, why);
+    const long long need = (long long)P * D->g[0].W * D->g[0].H;
+    if (capacity_pixels < need) return fail(FIC_E_CAPACITY, "%s: output needs %lld pixels, have %lld", who, need, (long long)capacity_pixels);
+    HIP_TRY(hipSetDevice(c->device));
+    return c->mem.ensure(c->dec_store, W->total);
+}
+
+// the decoder's message for a marked plane, under the entry's name
+int qt_ctx_bad_table(const char* who, int rc)
+{
+    if (rc != FIC_E_ARGUMENT) return rc;
+    return fail(FIC_E_ARGUMENT, "%s: the leaf table on the device is not a tiling this context's levels can decode (%s)", who, std::string(g_err).c_str());
+}
+
+template <typename Dev>
+int qt_ctx_decode(fic_qt_ctx* c, const char* who, const FicQtDecode& D, const QtDecodePlan& W, void* out, float* avg_error_out, int* iterations_out)
+{
+    using Px = typename Dev::Px;
+    const DecodeKind& kind = sizeof(Px) == 1 ? kDecodeGrey : kDecodeRgb;
+    const FicGeom& g = D.g[0];                             // planes = the context's
+    const hipStream_t s = c->last_stream;
+    auto at = [&](QtDecodeArea a) { return (void*)(c->dec_store + W.a[a].off); };
+    DecodeJob J;
+    if (D.zoom != 1) {                                     // the store holds the encoded size: the loop's areas come from an arena
+        if (int rc = J.open(who, c->device, kind, g, s)) return rc;
+    } else {
+        J.borrow(kind, g, s, at(kQtDecScaled), at(kQtDecImage), (FicDecodeState*)at(kQtDecState), (uint32_t*)at(kQtDecSq));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    int32_t *entries = (int32_t*)at(kQtDecEntries), *cells = (int32_t*)at(kQtDecCells), *cover = (int32_t*)at(kQtDecCover);
+    // one iteration: before the first, the tables resolved (the loop has put its initial state on s by then); scale the
+    // current image of every plane, one paint of all leaves of all planes, loop control
+    const int rc = J.run(who, nullptr, avg_error_out, iterations_out, nullptr, out, [&](int counter) {
+        if (counter == 0 && fic_launch_qt_resolve<Dev>(c->at<int32_t>(kQtLeaves), c->at<int>(kQtNLeaves), D, g.planes, entries, cells, cover, J.state, s))
+            return -1;
+        if constexpr (sizeof(Px) == 1) {
+            if (fic_launch_scale((const uint8_t*)J.image, (uint8_t*)J.scaled, g, s)) return -1;
+        } else {
+            if (fic_launch_scale_rgb_planes((const int32_t*)J.image, (int32_t*)J.scaled, g, s)) return -1;
+        }
+        if (fic_launch_qt_paint_planes<Dev>((const Px*)J.scaled, (Px*)J.image, entries, cells, cover, J.state, J.sq, counter, false, D, g.planes, s))
+            return -1;
+        return fic_launch_decode_step(J.state, J.sq, counter, g.W * g.H, g.planes, s);
+    });
+    return qt_ctx_bad_table(who, rc);
+}
+
+template <typename Dev>
+int qt_ctx_collage(fic_qt_ctx* c, const char* who, const FicQtDecode& D, const QtDecodePlan& W, void* out)
+{
+    using Px = typename Dev::Px;
+    const FicGeom& g = D.g[0];
+    const size_t P = (size_t)g.planes, npix = (size_t)g.W * g.H;
+    const hipStream_t s = c->last_stream;
+    auto at = [&](QtDecodeArea a) { return (void*)(c->dec_store + W.a[a].off); };
+    FicDecodeState* d_state = (FicDecodeState*)at(kQtDecState);
+    int32_t *entries = (int32_t*)at(kQtDecEntries), *cells = (int32_t*)at(kQtDecCells), *cover = (int32_t*)at(kQtDecCover);
+    // the 2:1 copy of the input the level encodes made: the top grey context's for every level, the top colour context's own
+    const Px* scaled;
+    if constexpr (sizeof(Px) == 1) scaled = c->grey[0]->b.scaled;
+    else scaled = c->rgb[0]->scaled;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemsetAsync(d_state, 0, P * sizeof(FicDecodeState), s));
+    if (fic_launch_qt_resolve<Dev>(c->at<int32_t>(kQtLeaves), c->at<int>(kQtNLeaves), D, g.planes, entries, cells, cover, d_state, s) ||
+        fic_launch_qt_paint_planes<Dev>(scaled, (Px*)at(kQtDecImage), entries, cells, cover, d_state, nullptr, 0, true, D, g.planes, s))
+        return fail(FIC_E_HIP, "%s: launch failed", who);
+    std::vector<FicDecodeState> st(P);
+    HIP_TRY(hipMemcpyAsync(st.data(), d_state, P * sizeof(FicDecodeState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t p = 0; p < P; p++)
+        if (st[p].bad_index)
+            return fail(FIC_E_ARGUMENT, "%s: the leaf table of plane %zu on the device is not a tiling this context's levels can decode", who, p);
+    HIP_TRY(hipMemcpy(out, at(kQtDecImage), P * npix * sizeof(Px), hipMemcpyDeviceToHost));
+    return FIC_OK;
 }
 
 }  // namespace
@@ -330,6 +433,29 @@ int fic_qt_ctx_result_device_ptrs(fic_qt_ctx* c, void** leaves, void** n_leaves,
     if (param) *param = c->at<void>(kQtParam);
     if (stats) *stats = c->at<void>(kQtStats);
     return FIC_OK;
+}
+
+int fic_qt_ctx_decode_zoom_host(fic_qt_ctx* c, int zoom, void* out, int64_t capacity_pixels, float* avg_error_out, int* iterations_out)
+{
+    const char* who = "fic_qt_ctx_decode_zoom_host";
+    if (!c || !out) return fail(FIC_E_ARGUMENT, "%s: null argument", who);
+    std::lock_guard<std::mutex> lk(c->mu);
+    FicQtDecode D;
+    QtDecodePlan W;
+    if (int rc = qt_ctx_decode_begin(c, who, zoom, capacity_pixels, &D, &W)) return rc;
+    return c->colour ? qt_ctx_decode<QtRgbIso>(c, who, D, W, out, avg_error_out, iterations_out)
+                     : qt_ctx_decode<QtGrey>(c, who, D, W, out, avg_error_out, iterations_out);
+}
+
+int fic_qt_ctx_collage_host(fic_qt_ctx* c, void* out, int64_t capacity_pixels)
+{
+    const char* who = "fic_qt_ctx_collage_host";
+    if (!c || !out) return fail(FIC_E_ARGUMENT, "%s: null argument", who);
+    std::lock_guard<std::mutex> lk(c->mu);
+    FicQtDecode D;
+    QtDecodePlan W;
+    if (int rc = qt_ctx_decode_begin(c, who, 1, capacity_pixels, &D, &W)) return rc;
+    return c->colour ? qt_ctx_collage<QtRgbIso>(c, who, D, W, out) : qt_ctx_collage<QtGrey>(c, who, D, W, out);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fic_device.h"
+#include "fic_qt_decode_plan.h"
 
 // Device-resident working set of one context (all planes of the batch).
 //   pool_pix : u8  [planes][Nd_pad][n]    expanded domain pool, block pixels row-major (FC:1036), 64-B aligned
@@ -380,3 +381,25 @@ int fic_launch_qt_tree_stats_rd(const uint32_t* const* sse, const int* Rw, int n
 template <typename Fmt>
 int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt::Px* image, const typename Fmt::Leaf* lv, int n,
                                    FicDecodeState* state, uint32_t* sqbuf, int counter, const FicGeom& g, hipStream_t s);
+// Decode and collage of a batch from the encoder's leaf table on the device (QtGrey and QtRgbIso, the batched
+// handle's formats).  What the two kernels know of the context: its levels at the decode's zoom (the same block counts, sides
+// and image times zoom: make_decode_geometry) and the ladder and image of the encode.
+struct FicQtDecode {
+    FicGeom g[3];
+    int nl, zoom;
+    int B_max, B_min, W, H;  // of the encode
+    int Rw_top, Rw_min, Nr_min, n_iso;
+    size_t leaf_stride;      // ints between the tables of two planes
+};
+// Checks and resolves the table of every plane: entries int32 [planes][Nr_min][kQtEntryInts], cells int32 [planes][Nr_min], cover
+// int32 [planes] (fic_qt_decode_plan.h); a plane whose table is not a valid tiling gets state[p].bad_index here or in the paint.
+// state [planes] must hold the loop's initial state (bad_index 0) on s before this.
+template <typename Fmt>
+int fic_launch_qt_resolve(const int32_t* leaves, const int* n_leaves, const FicQtDecode& D, int planes, int32_t* entries, int32_t* cells,
+                          int32_t* cover, FicDecodeState* state, hipStream_t s);
+// One paint of all leaves of all planes from scaled [planes][zH / 2][zW / 2] into image [planes][zH][zW]; collage: scaled is the
+// input's 2:1 copy, the paint runs once, sqbuf and counter are not used.
+template <typename Fmt>
+int fic_launch_qt_paint_planes(const typename Fmt::Px* scaled, typename Fmt::Px* image, const int32_t* entries, const int32_t* cells,
+                               const int32_t* cover, FicDecodeState* state, uint32_t* sqbuf, int counter, bool collage, const FicQtDecode& D,
+                               int planes, hipStream_t s);

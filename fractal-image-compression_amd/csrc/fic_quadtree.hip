@@ -21,6 +21,9 @@
 //   k_qt_rd_keys / k_qt_select_hist_w / k_qt_select_final_w
 //                            encode by rate-distortion pruning: the keys e(v) and gains G_v of min D + lambda N,
 //                            and the select of the key at which the summed gain reaches an SSE target
+//   k_qt_resolve<Fmt> / k_qt_paint_planes<Fmt, S, kCollage>
+//                            decode and collage of a batch from the encoder's leaf table as it stands on the device (DESIGN.md
+//                            4.25): every row checked and resolved, then one paint of all levels and planes per iteration
 // The walkers (k_qt_count, k_qt_scatter, k_qt_tree_stats) take the split rule as a type: QtByThreshold (4.13) or QtByKey (4.23).
 // Every encoder kernel takes a batch of planes (FicQtPlanes in fic_launch.h): the plane is a grid dimension, so no
 // workgroup spans two planes, and every parameter of a split rule -- threshold, rank, SSE target, lambda -- is read per plane
@@ -773,6 +776,187 @@ __global__ __launch_bounds__(256) void k_decode_paint_leaves(const typename Fmt:
 }
 
 // ---------------------------------------------------------------------------------------------
+// Decode and collage of a batch straight from the encoder's leaf table: rows {x, y, B, idx_local, q.., iso} in
+// stream order, leaves [planes][leaf_stride] ints, n_leaves [planes], both where the caller can write them.
+//
+// k_qt_resolve<Fmt>: one thread per leaf of a plane (blockIdx.y).  It checks the row before any address is formed from it -- the
+// side in the ladder, x and y multiples of the side inside the image, idx_local inside the level's window, the isometry below
+// n_iso, the domain block inside the level's pool, 1 <= n_leaves <= Nr_min -- writes the resolved entry (QtEntryWord,
+// fic_qt_decode_plan.h: the stream decoder's leaf at the decode's zoom, sqoff from the closed form qt_decode_sqoff) and claims
+// the leaf's (B / B_min)^2 cells of side B_min in the plane's cell map (filled with -1 by the launcher) with the leaf's index.
+// A failed check or a cell that is taken already marks state[p].bad_index; the cells a plane's leaves did claim are counted in
+// cover[p] (zeroed by the launcher), and k_qt_paint_planes paints a plane only if nothing is marked and cover[p] == Nr_min:
+// every cell then belongs to exactly one leaf that passed every check and whose entry was written by this launch.
+// ---------------------------------------------------------------------------------------------
+template <typename Fmt>
+__global__ __launch_bounds__(256) void k_qt_resolve(const int32_t* __restrict__ leaves, const int* __restrict__ n_leaves, FicQtDecode D,
+                                                    int32_t* __restrict__ entries, int32_t* __restrict__ cells, int32_t* __restrict__ cover,
+                                                    FicDecodeState* __restrict__ state)
+{
+    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    FicDecodeState* st = state + p;
+    const int n = n_leaves[p];
+    if (n < 1 || n > D.Nr_min) {                            // uniform per plane
+        if (i == 0) st->bad_index = 1;
+        return;
+    }
+    int claimed = 0;
+    if (i < n) {
+        const int32_t* r = leaves + (size_t)p * D.leaf_stride + (size_t)i * Fmt::kLeafInts;
+        const int x = r[0], y = r[1], B = r[2], idx = r[3];
+        int iso = 0;
+        if constexpr (Fmt::kIso) iso = r[3 + Fmt::QW];
+        int l = -1;
+#pragma unroll
+        for (int v = 0; v < 3; v++)
+            if (v < D.nl && B == (D.B_max >> v)) l = v;
+        bool ok = l >= 0;
+        // W and H are multiples of B_max: a multiple of B below W leaves room for the whole leaf
+        ok = ok && x >= 0 && y >= 0 && x < D.W && y < D.H && (x % B) == 0 && (y % B) == 0;
+        int gi = -1;
+        const FicGeom g = qt_lv(D.g, ok ? l : 0);           // the level at the decode's zoom: the block counts of the encode
+        if (ok) {
+            ok = idx >= 0 && idx < g.wK * g.wK && iso >= 0 && iso < D.n_iso;
+            if (ok) gi = window_to_global(g, (y / B) * g.Rw + x / B, idx);
+            ok = ok && gi >= 0 && gi < g.Nd;
+        }
+        if (ok) {
+            const int nb = B / D.B_min, c0 = (y / D.B_min) * D.Rw_min + x / D.B_min;
+            int32_t* cp = cells + (size_t)p * D.Nr_min;
+            for (int cy = 0; cy < nb; cy++)
+                for (int cx = 0; cx < nb; cx++) {
+                    if (atomicCAS(&cp[c0 + cy * D.Rw_min + cx], -1, i) == -1) claimed++;
+                    else ok = false;
+                }
+        }
+        if (ok) {
+            int4* e = (int4*)(entries + ((size_t)p * D.Nr_min + i) * kQtEntryInts);
+            const int sqoff = (int)qt_decode_sqoff(x, y, B, D.B_max, D.Rw_top, D.zoom);
+            int4 q;
+            if constexpr (Fmt::QW == 3) q = make_int4(r[4], r[5], iso, 0);
+            else q = make_int4(r[4], r[5], r[6], r[7]);
+            e[0] = make_int4(D.zoom * x, D.zoom * y, gi, sqoff);
+            e[1] = q;
+            e[2] = make_int4(iso, D.zoom * B, 0, 0);
+        } else {
+            st->bad_index = 1;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) claimed += __shfl_xor(claimed, off, 64);
+    if ((threadIdx.x & 63) == 0 && claimed) atomicAdd(&cover[p], claimed);
+}
+
+// The collage of one segment: the values of the quantised row from the scaled copy of the input, nothing read from the image
+// and no squares -- the arithmetic k_leaf_sse sums, through the same functions.
+template <int B, int S>
+__device__ __forceinline__ void qt_collage_row(uint8_t* __restrict__ prow, const uint8_t* __restrict__ scaled, const FicGeom& g,
+                                               const FicQtLeaf& e, int ry, int x0)
+{
+    int value[S];
+    qt_row_values<B, S>(scaled, g, e.gi, e.q[2], ry, x0, __fdiv_rn((float)e.q[0], 100.0f), (float)e.q[1], value);
+    uint32_t neu[S / 4];
+#pragma unroll
+    for (int q = 0; q < S / 4; q++) neu[q] = 0u;
+#pragma unroll
+    for (int x = 0; x < S; x++) neu[x >> 2] |= (uint32_t)value[x] << (8 * (x & 3));
+    __builtin_memcpy(prow, neu, S);
+}
+template <int B, int S, typename Leaf>
+__device__ __forceinline__ void qt_collage_row(int32_t* __restrict__ prow, const int32_t* __restrict__ scaled, const FicGeom& g,
+                                               const Leaf& e, int ry, int x0)
+{
+    const FicRgbCoef cf = rgb_row_coef(e.q[0], e.q[1], e.q[2], e.q[3]);
+    int32_t cur[S], dom[S];
+    rgb_domain_seg<B, S>(scaled, g, e.gi, qt_leaf_iso(e), ry, x0, dom);
+#pragma unroll
+    for (int x = 0; x < S; x++) {
+        int vR, vG, vB;
+        rgb_paint_px(cf, dom[x], vR, vG, vB);
+        cur[x] = (int32_t)(0xff000000u | ((uint32_t)vR << 16) | ((uint32_t)vG << 8) | (uint32_t)vB);
+    }
+    __builtin_memcpy(prow, cur, 4 * S);
+}
+
+// One segment of a leaf of side B through the row code above (qt_paint_row / qt_collage_row): the sum of its squares, 0 for the
+// collage.  A segment is never wider than its leaf (S <= zoom B_min).
+template <int B, int S, bool kCollage, typename Px, typename Leaf>
+__device__ __forceinline__ uint32_t qt_plane_seg(Px* __restrict__ prow, uint32_t* __restrict__ srow, const Px* __restrict__ scaled,
+                                                 const FicGeom& g, const Leaf& e, int ry, int x0)
+{
+    if constexpr (S > B) {
+        return 0;
+    } else if constexpr (kCollage) {
+        qt_collage_row<B, S>(prow, scaled, g, e, ry, x0);
+        return 0;
+    } else {
+        return qt_paint_row<B, S>(prow, srow, scaled, g, e, ry, x0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_qt_paint_planes<Fmt, S, kCollage>: one decoder paint of every leaf of every plane (blockIdx.y), pixel-centric.  One thread
+// per image segment of S pixels, threads in image order (row, segment): a wave writes consecutive bytes of the image.  S is 4
+// packed ARGB pixels, or min(16, zoom B_min) grey ones (16 bytes, or the 4 / 8 that a cell of side zoom B_min = 4 / 8 holds), so
+// a segment never leaves its cell, and the cell map names its leaf.  The squares go to sqbuf at the leaf's offset (Java's order:
+// leaf by leaf, pixel rows within a leaf), the plane's exact sum to state[p].ssd[counter] as in k_decode_paint_leaves.  The
+// row code is the stream decoder's, dispatched on the leaf's side: the lanes of a wave whose leaves differ in side take their
+// case in turn (an image has at most three sides).
+// kCollage: the one paint of the collage -- `scaled` is the 2:1 copy of the input, the image is only written, no squares.
+// zW, zH: the image at the decode's zoom; cs = zoom B_min; scaled [planes][zH / 2][zW / 2]; Dw[l]: domain blocks per row of the
+// level of side B_max >> l.
+// ---------------------------------------------------------------------------------------------
+struct FicQtPaint {
+    int zW, zH, cs, Rw_min, Nr_min;
+    int zB_max;              // zoom B_max
+    int Dw[3];
+};
+template <typename Fmt, int S, bool kCollage>
+__global__ __launch_bounds__(256) void k_qt_paint_planes(const typename Fmt::Px* __restrict__ scaled, typename Fmt::Px* __restrict__ image,
+                                                         const int32_t* __restrict__ entries, const int32_t* __restrict__ cells,
+                                                         const int32_t* __restrict__ cover, FicDecodeState* __restrict__ state,
+                                                         uint32_t* __restrict__ sqbuf, int counter, FicQtPaint A)
+{
+    using Px = typename Fmt::Px;
+    const int p = blockIdx.y;
+    FicDecodeState* st = state + p;
+    if (st->done || st->bad_index) return;                 // uniform per plane: a finished or refused plane is not touched
+    if (cover[p] != A.Nr_min) {                            // (uniform) the leaves do not tile the image
+        if (threadIdx.x == 0) st->bad_index = 1;
+        return;
+    }
+    const int segs = A.zW / S, t = blockIdx.x * 256 + threadIdx.x;
+    uint32_t sq = 0;
+    if (t < segs * A.zH) {
+        const int px = (t % segs) * S, py = t / segs;
+        const int i = cells[(size_t)p * A.Nr_min + (py / A.cs) * A.Rw_min + px / A.cs];
+        const int4* ep = (const int4*)(entries + ((size_t)p * A.Nr_min + i) * kQtEntryInts);
+        const int4 e0 = ep[0], e1 = ep[1], e2 = ep[2];
+        typename Fmt::Leaf e;
+        e.x = e0.x; e.y = e0.y; e.gi = e0.z; e.sqoff = e0.w;
+        e.q[0] = e1.x; e.q[1] = e1.y; e.q[2] = e1.z; e.q[3] = e1.w;
+        if constexpr (sizeof(e) > sizeof(FicQtLeaf)) e.k = e2.x;
+        const int side = e2.y, ry = py - e.y, x0 = px - e.x;
+        FicGeom g{};                                       // what the row code takes from a level's geometry
+        g.Ws = A.zW / 2;
+        g.Dw = side == A.zB_max ? A.Dw[0] : (2 * side == A.zB_max ? A.Dw[1] : A.Dw[2]);
+        g.abstand = side / 4;
+        const size_t npix = (size_t)A.zW * A.zH;
+        Px* prow = image + p * npix + (size_t)py * A.zW + px;
+        uint32_t* srow = kCollage ? nullptr : sqbuf + p * npix + (size_t)e.sqoff + (size_t)ry * side + x0;
+        const Px* sc = scaled + p * (npix / 4);
+        switch (side) {
+        case 4: sq = qt_plane_seg<4, S, kCollage>(prow, srow, sc, g, e, ry, x0); break;
+        case 8: sq = qt_plane_seg<8, S, kCollage>(prow, srow, sc, g, e, ry, x0); break;
+        case 16: sq = qt_plane_seg<16, S, kCollage>(prow, srow, sc, g, e, ry, x0); break;
+        case 32: sq = qt_plane_seg<32, S, kCollage>(prow, srow, sc, g, e, ry, x0); break;
+        default: sq = qt_plane_seg<64, S, kCollage>(prow, srow, sc, g, e, ry, x0); break;
+        }
+    }
+    if constexpr (!kCollage) qt_ssd_add(sq, &st->ssd[counter]);
+}
+
+// ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
 template <typename Fmt>
@@ -922,7 +1106,57 @@ int fic_launch_decode_paint_leaves(const typename Fmt::Px* scaled, typename Fmt:
     return 0;
 }
 
-#define FIC_QT_INSTANTIATE(Fmt)                                                                                                       \
+template <typename Fmt>
+int fic_launch_qt_resolve(const int32_t* leaves, const int* n_leaves, const FicQtDecode& D, int planes, int32_t* entries, int32_t* cells,
+                          int32_t* cover, FicDecodeState* state, hipStream_t s)
+{
+    if (hipMemsetAsync(cells, 0xFF, (size_t)planes * D.Nr_min * sizeof(int32_t), s) != hipSuccess) return -1;      // every cell -1
+    if (hipMemsetAsync(cover, 0, (size_t)planes * sizeof(int32_t), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_qt_resolve<Fmt>, dim3((D.Nr_min + 255) / 256, planes), dim3(256), 0, s, leaves, n_leaves, D, entries, cells, cover, state);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename Fmt, int S>
+static int qt_paint_planes(const typename Fmt::Px* scaled, typename Fmt::Px* image, const int32_t* entries, const int32_t* cells,
+                           const int32_t* cover, FicDecodeState* state, uint32_t* sqbuf, int counter, bool collage, const FicQtDecode& D,
+                           int planes, hipStream_t s)
+{
+    const FicGeom& g = D.g[0];
+    const FicQtPaint A{g.W, g.H, D.zoom * D.B_min, D.Rw_min, D.Nr_min, D.zoom * D.B_max, {D.g[0].Dw, D.g[1].Dw, D.g[2].Dw}};
+    auto k = collage ? k_qt_paint_planes<Fmt, S, true> : k_qt_paint_planes<Fmt, S, false>;
+    const int threads = g.W / S * g.H;
+    hipLaunchKernelGGL(k, dim3((threads + 255) / 256, planes), dim3(256), 0, s, scaled, image, entries, cells, cover, state, sqbuf, counter, A);
+    FIC_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename Fmt>
+int fic_launch_qt_paint_planes(const typename Fmt::Px* scaled, typename Fmt::Px* image, const int32_t* entries, const int32_t* cells,
+                               const int32_t* cover, FicDecodeState* state, uint32_t* sqbuf, int counter, bool collage, const FicQtDecode& D,
+                               int planes, hipStream_t s)
+{
+    const int cs = D.zoom * D.B_min;                       // a segment stays inside a cell: 4 ARGB pixels, min(16, cs) grey ones
+    if constexpr (sizeof(typename Fmt::Px) == 4)
+        return qt_paint_planes<Fmt, 4>(scaled, image, entries, cells, cover, state, sqbuf, counter, collage, D, planes, s);
+    else if (cs == 4)
+        return qt_paint_planes<Fmt, 4>(scaled, image, entries, cells, cover, state, sqbuf, counter, collage, D, planes, s);
+    else if (cs == 8)
+        return qt_paint_planes<Fmt, 8>(scaled, image, entries, cells, cover, state, sqbuf, counter, collage, D, planes, s);
+    else
+        return qt_paint_planes<Fmt, 16>(scaled, image, entries, cells, cover, state, sqbuf, counter, collage, D, planes, s);
+}
+
+// the batched handle's two formats
+#define FIC_QT_INSTANTIATE_DECODE(Fmt)                                                                                                \
+    template int fic_launch_qt_resolve<Fmt>(const int32_t*, const int*, const FicQtDecode&, int, int32_t*, int32_t*, int32_t*,        \
+                                            FicDecodeState*, hipStream_t);                                                            \
+    template int fic_launch_qt_paint_planes<Fmt>(const Fmt::Px*, Fmt::Px*, const int32_t*, const int32_t*, const int32_t*,            \
+                                                 FicDecodeState*, uint32_t*, int, bool, const FicQtDecode&, int, hipStream_t);
+FIC_QT_INSTANTIATE_DECODE(QtGrey)
+FIC_QT_INSTANTIATE_DECODE(QtRgbIso)
+
+#define FIC_QT_INSTANTIATE(Fmt)                                                                                                      \
     template int fic_launch_leaf_sse<Fmt>(const Fmt::Px*, const Fmt::Px*, const int32_t*, const int32_t*, uint32_t*, const FicGeom&,  \
                                           hipStream_t, const FicQtPlanes&);                                                           \
     template int fic_launch_qt_compact<Fmt>(const uint32_t* const*, const int32_t* const*, const int32_t* const*, const int*, int,    \

@@ -212,7 +212,8 @@ class QuadtreeEncoder(capi.Handle):
         self.cols = 9 if colour else 7
         self.tag = 6 if colour else 2
         h = capi.lib().fic_qt_ctx_create(device, 1 if colour else 0, width, height, B_max, B_min, wK, n_iso, planes)
-        self._encode_threshold, self._encode_budget, self._encode_rd = self._open(h, "encode_threshold", "encode_budget", "encode_rd")
+        (self._encode_threshold, self._encode_budget, self._encode_rd, self._decode, self._collage_host) = self._open(
+            h, "encode_threshold", "encode_budget", "encode_rd", "decode_zoom_host", "collage_host")
         self.max_leaves = (width // B_min) * (height // B_min)      # rows per plane of the device leaf table
 
     # ---- input -----------------------------------------------------------------------------
@@ -316,6 +317,27 @@ class QuadtreeEncoder(capi.Handle):
         P = self.planes
         return {"leaves": t(p[0], (P, self.max_leaves, self.cols), "<i4"), "n_leaves": t(p[1], (P,), "<i4"),
                 "param": t(p[2], (P,), "<i4"), "stats": t(p[3], (P, 4), "<i8")}
+
+    # ---- decode and collage -------------------------------------------------
+    def decode(self, zoom=1):
+        """The decoder's loop on every plane of the last encode at once, from the tables on the device
+        (fic_qt_ctx_decode_zoom_host).  Returns (images [planes, zoom*H, zoom*W], uint8 for a grey context and packed ARGB int32
+        for a colour one, avgError float32 [planes], iterations int32 [planes]); plane p is what the one-shot decoder
+        (capi.decode_quadtree_run / decode_rgb_quadtree_iso_run) returns for write_runs()[p] at that zoom."""
+        if zoom not in (1, 2, 4):                             # the output is sized from it: refused here, as the library would
+            raise FicError(-3, f"zoom={zoom}: only 1, 2 or 4")
+        z = int(zoom)
+        out = np.zeros((self.planes, z * self.height, z * self.width), np.int32 if self.colour else np.uint8)
+        avg, it = np.zeros(self.planes, np.float32), np.zeros(self.planes, np.int32)
+        capi.check(self._decode(self._h, z, out.ctypes.data_as(C.c_void_p), out.size, capi.ptr(avg, C.c_float), capi.ptr(it, C.c_int)))
+        return out, avg, it
+
+    def collage(self):
+        """[planes, H, W] (dtype as decode's): one paint of every plane's leaves from the 2:1 copy of its input image
+        (fic_qt_ctx_collage_host) -- the image whose squared distance from the input is stats[p][0]."""
+        out = np.zeros((self.planes, self.height, self.width), np.int32 if self.colour else np.uint8)
+        capi.check(self._collage_host(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     def write_runs(self):
         """One stream per plane from the last encode's tables, through the existing writers (tag 2 / tag 6)."""

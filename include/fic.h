@@ -539,6 +539,22 @@ FIC_API int fic_qt_ctx_get_leaves_host(fic_qt_ctx* ctx, int plane, int32_t* leav
 /* Device pointers of the same, stable for the life of the context: leaves int32 [planes][(w / B_min) * (h / B_min)][7 or 9]
  * (a fixed stride per plane; the rows of a plane beyond its n_leaves are unspecified), n_leaves, param, stats as above. */
 FIC_API int fic_qt_ctx_result_device_ptrs(fic_qt_ctx* ctx, void** leaves, void** n_leaves, void** param, void** stats);
+/* Decode and collage of every plane of the last encode at once, from the tables as they stand on the device
+ * -- leaves and n_leaves above, the context's geometry, wK and n_iso -- never through a stream or the host.
+ *   out      [planes][zoom h][zoom w]: uint8_t for a grey context, packed int32_t ARGB for a colour one; capacity_pixels counts
+ *            the pixels of all planes
+ *   decode   zoom 1, 2 or 4 (every leaf {x, y, B} painted as {zoom x, zoom y, zoom B}); plane p is, bit for bit, what
+ *            fic_decode_quadtree_run_zoom (grey) / fic_decode_rgb_quadtree_iso_run (colour) returns for plane p's stream at
+ *            that zoom with avgError 0 carried in: the image, avg_error_out[p], iterations_out[p] (either may be NULL)
+ *   collage  plane p is one paint of its leaves from the 2:1 copy of the input image: the image whose squared distance from the
+ *            input, summed over a leaf, is that leaf's collage SSE, and over the plane stats[p][0]
+ * FIC_E_ARGUMENT for a null argument or a zoom outside {1, 2, 4}, FIC_E_STATE before the first encode, FIC_E_CAPACITY when out
+ * is too small, FIC_E_GEOMETRY for a block side above 64 at that zoom; FIC_E_ARGUMENT, naming the plane, when a plane's table
+ * on the device is no longer a tiling of the image by valid rows (the caller can write it): nothing is read through such a row,
+ * `out` is not written, and the context takes the next encode as ever.  Both wait for the last encode's stream. */
+FIC_API int fic_qt_ctx_decode_zoom_host(fic_qt_ctx* ctx, int zoom, void* out, int64_t capacity_pixels, float* avg_error_out,
+                                        int* iterations_out);
+FIC_API int fic_qt_ctx_collage_host(fic_qt_ctx* ctx, void* out, int64_t capacity_pixels);
 
 /* Tuning / instrumentation knobs:
  *   "sweep"       0 auto: windowed search -> generic kernel; full search -> the VALU sweep (k_sweep_d4, the
